@@ -1,9 +1,24 @@
 #!/usr/bin/env python3
 """bench.py -- MPC QP solves/sec on MI355X (BASELINE.json metric), one JSON line on rank 0.
 
-    python bench.py [--gpus N --steps K --warmup W]            (N=1)
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]            (N=1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, runs W warmup steps, times K steps and prints the headline line: `metric`, `value`
+(solves/s over the K timed steps), `unit`, `higher_is_better`, `dtype`, `ms_per_step` (wall time of one
+timed step), the configuration, the build and `kernel_ms` (the library's HIP events around the two kernels,
+below).  Everything else described below -- the two repeat regions behind `value_median_of`,
+the per-rank records, `kernel_ms_serial`, iteration and lane statistics, `roofline`, `alu`, the CPU
+baseline and the comparisons with dlib, and the side legs (`bit_exact`, `pipelined`, `fp32`, `config1`,
+`config2`, `config4_one_gpu`, `config5`, `mid_batch`) -- runs only with `--full`.  The `--no-*` options
+switch single legs of a `--full` run off.
+
+`--dump-outputs DIR` writes what the last timed step computed -- the controls a caller of the timed path
+receives -- as DIR/front.npy and DIR/rear.npy (float64 for `--dtype f64`, float32 for f32; for N>1 the
+whole gathered batch, from rank 0).  The inputs are the seeded synthetic stream, the same in every run with
+the same arguments, so two builds can be compared output for output.  Above 64 MB in all, the same fixed,
+seeded sample of instances is written from each array.
 
 A "step" is one pass of the hot path over one batch of synthetic instances per GPU: the compact
 (reference call pattern) form, horizon 20, 2 inputs, 262 144 instances per GPU (BASELINE config 3;
@@ -21,14 +36,14 @@ H = 20.  It is not the default because the HIP events that time each kernel then
 its workgroups wait for CUs and stop agreeing with rocprofv3's dispatch timestamps.  "kernel_ms" is
 the average over the timed region of the library's events around each kernel (last solve of each
 handle), "kernel_ms_serial" the same measured right after the timed region with one batch in flight.
-A one-GPU run with the default one batch in flight also times the same K steps with two in flight and
-reports that figure under "pipelined" (value, ms_per_step, alu_frac), next to `value`.
-The default one-GPU run also times BASELINE config 2 (4 096 instances, N = 10, the WAVE family) and config 5
+A `--full` one-GPU run with the default one batch in flight also times the same K steps with two in flight
+and reports that figure under "pipelined" (value, ms_per_step, alu_frac), next to `value`.
+A `--full` one-GPU run at the default size also times BASELINE config 2 (4 096 instances, N = 10, the WAVE family) and config 5
 (65 536 instances of mixed horizons through one call) and reports them under "config2" and "config5".
 
 `value` is measured in fp64, the only dtype that meets the 1e-6 parity target (SURVEY.md section 0
 fact 3), through AUTO, i.e. the LANE_FMA family (unit-box coordinates, fused multiply-adds: dlib's
-iteration on quantities that differ from dlib's by rounding).  Its outputs are compared with real dlib
+iteration on quantities that differ from dlib's by rounding).  Under `--full` its outputs are compared with real dlib
 run on the host in the same run ("max_abs_du_vs_dlib", "max_rel_du_vs_dlib": north_star's bar is 1e-6
 relative) and, over the whole batch, with the bit-exact LANE family ("vs_bit_exact": fraction of equal
 iteration counts, max |du|).  The bit-exact family's own rate is timed right after and reported under
@@ -60,13 +75,34 @@ if ROOT not in sys.path:
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 FP64_VECTOR_PEAK_TF = 78.6     # MI355X vendor FP64 vector peak
 FP32_VECTOR_PEAK_TF = 157.3
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs: at most this much in all (files, headers included)
+DUMP_SAMPLE_SEED = 0
+
+
+def positive_int(s):
+    k = int(s)
+    if k < 1:
+        raise argparse.ArgumentTypeError(f"must be >= 1, got {k}")
+    return k
+
+
+def non_negative_int(s):
+    k = int(s)
+    if k < 0:
+        raise argparse.ArgumentTypeError(f"must be >= 0, got {k}")
+    return k
 
 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=positive_int, default=20, help="timed steps")
+    ap.add_argument("--warmup", type=non_negative_int, default=3, help="untimed steps before them")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: repeat regions, per-rank records, roofline / alu, "
+                         "CPU baseline and dlib comparisons, and the side legs (bit-exact, pipelined, fp32, configs 1/2/4/5, mid batch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/front.npy and DIR/rear.npy")
     ap.add_argument("--batch", type=int, default=262144, help="instances per GPU")
     ap.add_argument("--horizon", type=int, default=20)
     ap.add_argument("--algo", default="auto", choices=["auto", "lane", "lane_fma", "wave", "group"])
@@ -127,6 +163,21 @@ def library_sha256():
         return hashlib.sha256(open(path, "rb").read()).hexdigest()
     except OSError:
         return None
+
+
+def dump_outputs(path, arrays):
+    """Write each 1-D array of `arrays` (name -> numpy) as path/<name>.npy.  Above DUMP_LIMIT_BYTES in all, every
+    array is cut to the same fixed, seeded sample of indices (kept in ascending order)."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(x.nbytes for x in arrays.values())
+    budget = DUMP_LIMIT_BYTES - 1024 * len(arrays)   # (an .npy header is 128 bytes)
+    idx = None
+    if total > budget:
+        count = len(next(iter(arrays.values())))
+        keep = count * budget // total
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(count, size=keep, replace=False))
+    for name, x in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), x if idx is None else x[idx])
 
 
 def cpu_baseline(H, v, dy, dphi, budget_s):
@@ -308,10 +359,16 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     local_elapsed = elapsed
-    # the same K-step region twice more (same bracket): box-to-box and run-to-run noise is +-4 %, so a 3 % kernel change is
-    # only visible in the median; `value` stays the FIRST region, the one the contract describes
+    # what the last timed step computed, copied to the host before anything else runs (outside the timed region)
+    last = (a.steps - 1) % slots
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        fo, ro = (front_all[last], rear_all[last]) if world > 1 else (fronts[last], rears[last])
+        dumped = {"front": fo.cpu().numpy(), "rear": ro.cpu().numpy()}
+    # (--full) the same K-step region twice more (same bracket): box-to-box and run-to-run noise is +-4 %, so a 3 % kernel
+    # change is only visible in the median; `value` stays the FIRST region, the one the contract describes
     region_s = [elapsed]
-    for _ in range(2):
+    for _ in range(2 if a.full else 0):
         torch.cuda.synchronize()
         barrier()
         torch.cuda.synchronize()
@@ -347,41 +404,29 @@ def main():
         gather_ok = None
         chk = lambda t: t.view(torch.int64 if t.dtype == torch.float64 else torch.int32).bitwise_and(0xFFFFF).sum()
 
-    # One record per rank, in the line: device, shard, iteration total (= the rank's share of the work; the projected-
-    # gradient kernel's time follows it), kernel times, wall time, checksum of its block of the outputs -- so that the first
-    # run on a multi-GPU node can be diagnosed from its one line.  Outside the timed region.
-    _, _, it_r = solver.solve_batch_compact(tv, ty, tp, want_iters=True)
-    torch.cuda.synchronize()
-    rec = {"rank": rank, "device": local_rank, "device_name": torch.cuda.get_device_name(dev),
-           "shard": {"first": my.start, "stride": my.step or 1, "count": n},
-           "iterations_total": int(it_r.sum().item()), "cd_kernel_ms": k1, "pg_kernel_ms": k2,
-           "ms_per_step_local": local_elapsed / a.steps * 1e3,
-           "block_checksum": [int(chk(front).item()), int(chk(rear).item())], "gather_verified": gather_ok}
-    recs = [rec]
-    if world > 1:
-        recs = [None] * world
-        dist.all_gather_object(recs, rec)
-    it_tot = [r["iterations_total"] for r in recs]
-    imbalance = {"iterations_max_over_mean": max(it_tot) / (sum(it_tot) / len(it_tot)), "split": a.split,
-                 "sorted_by_speed": bool(a.sorted_by_speed)}
+    recs = imbalance = None
+    if a.full:
+        # One record per rank, in the line: device, shard, iteration total (= the rank's share of the work; the projected-
+        # gradient kernel's time follows it), kernel times, wall time, checksum of its block of the outputs -- so that the first
+        # run on a multi-GPU node can be diagnosed from its one line.  Outside the timed region.
+        _, _, it_r = solver.solve_batch_compact(tv, ty, tp, want_iters=True)
+        torch.cuda.synchronize()
+        rec = {"rank": rank, "device": local_rank, "device_name": torch.cuda.get_device_name(dev),
+               "shard": {"first": my.start, "stride": my.step or 1, "count": n},
+               "iterations_total": int(it_r.sum().item()), "cd_kernel_ms": k1, "pg_kernel_ms": k2,
+               "ms_per_step_local": local_elapsed / a.steps * 1e3,
+               "block_checksum": [int(chk(front).item()), int(chk(rear).item())], "gather_verified": gather_ok}
+        recs = [rec]
+        if world > 1:
+            recs = [None] * world
+            dist.all_gather_object(recs, rec)
+        it_tot = [r["iterations_total"] for r in recs]
+        imbalance = {"iterations_max_over_mean": max(it_tot) / (sum(it_tot) / len(it_tot)), "split": a.split,
+                     "sorted_by_speed": bool(a.sorted_by_speed)}
 
     if rank == 0:
-        # iteration statistics of this rank's shard (for the algorithmic-flop figure)
-        s1 = s2 = 0.0
-        for _ in range(3):   # one batch in flight: kernel durations without any overlap
-            _, _, iters_t = solver.solve_batch_compact(tv, ty, tp, want_iters=True)
-            y1, y2, _ = solver.last_kernel_times()
-            s1 += y1 / 3
-            s2 += y2 / 3
-        torch.cuda.synchronize()
-        mean_iters = float(iters_t.double().mean().item())
-        lane_stats = None
-        if algo_ran in (2, 3, 4):
-            wi, rb = solver.last_lane_stats()
-            pg_iters = float((iters_t.double() - 50.0).clamp(min=0).sum().item())
-            lane_stats = {"wave_iterations": wi, "refill_blocks": rb}
-            if algo_ran != 4:   # (a GROUP wavefront carries 64 / G instances: the figure has no such meaning there)
-                lane_stats["lane_utilisation"] = pg_iters / (64.0 * wi) if wi else None
+        if dumped is not None:
+            dump_outputs(a.dump_outputs, dumped)
         esz = 8 if a.dtype == "f64" else 4
         total = world * n * a.steps
         value = total / elapsed
@@ -390,55 +435,75 @@ def main():
         dom_name = {1: "wave_kernel", 2: "lane_pg_fused_kernel" if k2 >= k1 else "lane_cd_kernel",
                     3: ("ub_pg_asm_kernel" if (a.dtype == "f64" and H == 20) else "ub_pg_kernel") if k2 >= k1 else "ub_cd_kernel",   # (fp64 N = 20: the hand-written kernel, csrc/mpc_ub_asm.h)
                     4: "group_pg_kernel" if k2 >= k1 else "ub_cd_kernel"}[algo_ran]
-        alg_bytes = 5 * esz * n                       # 3 in + 2 out scalars per solve
-        # the PG kernel also reads what the CD kernel left per instance (not algorithmic traffic)
-        hbm_gbs = alg_bytes / (dom_ms * 1e-3) / 1e9
-        alg_flops = (46 * H - 16) * mean_iters * n
-        tfl = alg_flops / (elapsed / a.steps) / 1e12                 # what a whole step delivers
-        tfl_serial = alg_flops / ((s1 + s2) * 1e-3) / 1e12             # the two kernels on their own
-        peak_tf = FP64_VECTOR_PEAK_TF if a.dtype == "f64" else FP32_VECTOR_PEAK_TF
-        # HBM bytes per launch of the dominant kernel from the PMC passes (scripts/profile.sh ->
-        # scripts/make_traffic.py).  rocprofv3 cannot run inside this process, so the figure is taken from
-        # profiles/traffic.json -- but only if that file was made from THIS binary (sha256 of the .so).
-        traffic, traffic_note = None, "no profiles/traffic.json entry for this kernel"
-        tj = os.path.join(ROOT, "profiles", "traffic.json")
-        if os.path.exists(tj):
-            try:
-                tdata = json.load(open(tj))
-                entry = tdata.get(f"{dom_name}_{a.dtype}_H{H}_n{n}")
-                if entry is not None and tdata.get("_library_sha256") == library_sha256():
-                    traffic, traffic_note = entry, "PMC passes of this binary (profiles/traffic.json)"
-                elif entry is not None:
-                    traffic_note = ("profiles/traffic.json was measured on a different build of libtpc_mpc.so "
-                                    f"({entry} B per launch there): not reported for this binary")
-            except Exception as exc:   # noqa: BLE001
-                traffic_note = f"profiles/traffic.json unreadable: {exc}"
         out = {
             "metric": "MPC QP solves/sec (horizon N=20, 2 inputs) at 1/2/4/8 MI355X; max|du| vs dlib",
             "value": value, "unit": "solves/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": elapsed / a.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "value_median_of": {"repeats": len(region_s), "value": total / sorted(region_s)[len(region_s) // 2],
-                                "values": [total / t for t in region_s]},
+            "ms_per_step": elapsed / a.steps * 1e3, "higher_is_better": True, "scaling": "weak"}
+        if a.full:
+            out["value_median_of"] = {"repeats": len(region_s), "value": total / sorted(region_s)[len(region_s) // 2],
+                                      "values": [total / t for t in region_s]}
+        out.update({
             "vs_baseline": None, "dtype": a.dtype, "data": "synthetic", "gather": gather_word,
             "config": {"workload": f"batch {n} trajectories per GPU, N={H}, 2 inputs, compact "
                                    f"(mpcControllerTobi) form, cold start, eps 0.01, max_iter 10000",
                        "global_batch": world * n, "horizon": H, "algo": {1: "wave", 2: "lane", 3: "lane_fma", 4: "group"}[algo_ran],
                        "parallelism": f"batch-sharded x{world}", "batches_in_flight": slots,
                        "gather": gather_path, "gather_verified": gather_ok},
-            "build": MpcSolver.build_info(),
-            "ranks": recs, "imbalance": imbalance,
-            "kernel_ms": {"first": k1, "second": k2, "dominant": dom_name},
-            "kernel_ms_serial": {"first": s1, "second": s2},
-            "mean_iterations": mean_iters, "lane_stats": lane_stats,
-            "roofline": {"bound": "hbm", "achieved": hbm_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": hbm_gbs / HBM_PEAK_GBS, "traffic": traffic, "traffic_note": traffic_note,
-                         "note": "40 B/solve algorithmic: this path is issue-bound, not HBM-bound; see alu"},
-            "alu": {"bound": "fp64 vector issue" if a.dtype == "f64" else "fp32 vector issue",
-                    "achieved": tfl, "peak": peak_tf, "unit": "TFLOP/s", "frac": tfl / peak_tf,
-                    "serial_kernels_frac": tfl_serial / peak_tf,
-                    "flops_per_solve": (46 * H - 16) * mean_iters},
-        }
-        if not a.no_cpu and world == 1:   # (the CPU baseline and the side legs below belong to the N = 1 line only)
+            "build": MpcSolver.build_info()})
+        if a.full:
+            out.update({"ranks": recs, "imbalance": imbalance})
+        out["kernel_ms"] = {"first": k1, "second": k2, "dominant": dom_name}
+        if a.full:
+            # iteration statistics of this rank's shard (for the algorithmic-flop figure)
+            s1 = s2 = 0.0
+            for _ in range(3):   # one batch in flight: kernel durations without any overlap
+                _, _, iters_t = solver.solve_batch_compact(tv, ty, tp, want_iters=True)
+                y1, y2, _ = solver.last_kernel_times()
+                s1 += y1 / 3
+                s2 += y2 / 3
+            torch.cuda.synchronize()
+            mean_iters = float(iters_t.double().mean().item())
+            lane_stats = None
+            if algo_ran in (2, 3, 4):
+                wi, rb = solver.last_lane_stats()
+                pg_iters = float((iters_t.double() - 50.0).clamp(min=0).sum().item())
+                lane_stats = {"wave_iterations": wi, "refill_blocks": rb}
+                if algo_ran != 4:   # (a GROUP wavefront carries 64 / G instances: the figure has no such meaning there)
+                    lane_stats["lane_utilisation"] = pg_iters / (64.0 * wi) if wi else None
+            alg_bytes = 5 * esz * n                       # 3 in + 2 out scalars per solve
+            # the PG kernel also reads what the CD kernel left per instance (not algorithmic traffic)
+            hbm_gbs = alg_bytes / (dom_ms * 1e-3) / 1e9
+            alg_flops = (46 * H - 16) * mean_iters * n
+            tfl = alg_flops / (elapsed / a.steps) / 1e12                 # what a whole step delivers
+            tfl_serial = alg_flops / ((s1 + s2) * 1e-3) / 1e12             # the two kernels on their own
+            peak_tf = FP64_VECTOR_PEAK_TF if a.dtype == "f64" else FP32_VECTOR_PEAK_TF
+            # HBM bytes per launch of the dominant kernel from the PMC passes (scripts/profile.sh ->
+            # scripts/make_traffic.py).  rocprofv3 cannot run inside this process, so the figure is taken from
+            # profiles/traffic.json -- but only if that file was made from THIS binary (sha256 of the .so).
+            traffic, traffic_note = None, "no profiles/traffic.json entry for this kernel"
+            tj = os.path.join(ROOT, "profiles", "traffic.json")
+            if os.path.exists(tj):
+                try:
+                    tdata = json.load(open(tj))
+                    entry = tdata.get(f"{dom_name}_{a.dtype}_H{H}_n{n}")
+                    if entry is not None and tdata.get("_library_sha256") == library_sha256():
+                        traffic, traffic_note = entry, "PMC passes of this binary (profiles/traffic.json)"
+                    elif entry is not None:
+                        traffic_note = ("profiles/traffic.json was measured on a different build of libtpc_mpc.so "
+                                        f"({entry} B per launch there): not reported for this binary")
+                except Exception as exc:   # noqa: BLE001
+                    traffic_note = f"profiles/traffic.json unreadable: {exc}"
+            out.update({
+                "kernel_ms_serial": {"first": s1, "second": s2},
+                "mean_iterations": mean_iters, "lane_stats": lane_stats,
+                "roofline": {"bound": "hbm", "achieved": hbm_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": hbm_gbs / HBM_PEAK_GBS, "traffic": traffic, "traffic_note": traffic_note,
+                             "note": "40 B/solve algorithmic: this path is issue-bound, not HBM-bound; see alu"},
+                "alu": {"bound": "fp64 vector issue" if a.dtype == "f64" else "fp32 vector issue",
+                        "achieved": tfl, "peak": peak_tf, "unit": "TFLOP/s", "frac": tfl / peak_tf,
+                        "serial_kernels_frac": tfl_serial / peak_tf,
+                        "flops_per_solve": (46 * H - 16) * mean_iters}})
+        if a.full and not a.no_cpu and world == 1:   # (the CPU baseline and the side legs below belong to the N = 1 line only)
             cb, ns, cf, cr = cpu_baseline(H, v, dy, dphi, a.cpu_seconds)
             gf, gr = front[:ns].cpu().numpy().astype(np.float64), rear[:ns].cpu().numpy().astype(np.float64)
             out["cpu_baseline"] = cb
@@ -450,7 +515,7 @@ def main():
             out["max_rel_du_vs_dlib"] = float(max((np.abs(gf - cf) / den_f).max(), (np.abs(gr - cr) / den_r).max()))
             out["dlib_sample"] = ns
             out["gpu_over_cpu"] = value / cb["value"]
-        if world == 1 and a.dtype == "f64" and algo_ran == 3 and not a.no_bit_exact:
+        if a.full and world == 1 and a.dtype == "f64" and algo_ran == 3 and not a.no_bit_exact:
             # the bit-exact LANE family on the same K steps, and the whole batch of the two families side by side
             with MpcSolver(horizon=H, device=local_rank, dtype="f64", algo="lane") as sl:
                 sl.set_profiling(True)
@@ -478,7 +543,7 @@ def main():
                 "instances": n,
                 "iteration_counts_equal": float((iters_t == lit).double().mean().item()),
                 "max_abs_du": float(torch.maximum((front - lf).abs().max(), (rear - lr).abs().max()).item())}
-        if world == 1 and slots == 1 and not a.no_pipelined:
+        if a.full and world == 1 and slots == 1 and not a.no_pipelined:
             # the same K steps with two batches in flight (two handles, two streams): the next batch's
             # coordinate-descent kernel and queue sort run while the previous batch's last long instances
             # finish.  Reported beside `value`, which stays the one-batch-at-a-time figure whose kernel
@@ -505,7 +570,7 @@ def main():
                                 "ms_per_step": dp / a.steps * 1e3, "outputs_identical_to_serial": same,
                                 "alu_frac": alg_flops / (dp / a.steps) / 1e12 / peak_tf}
             s2.close()
-        if world == 1 and not a.no_fp32 and a.dtype == "f64":
+        if a.full and world == 1 and not a.no_fp32 and a.dtype == "f64":
             s32 = MpcSolver(horizon=H, device=local_rank, dtype="f32", algo=a.algo)
             s32.set_profiling(True)
             s32.reserve(n)
@@ -552,7 +617,7 @@ def main():
                            "note": "fp32 has no reference (dlib is fp64-only): errors are against this run's fp64 outputs",
                            "max_abs_du_vs_fp64": float(err.max().item())}
             s32.close()
-        if world == 1 and not a.no_config2 and a.dtype == "f64" and n == 262144 and H == 20:
+        if a.full and world == 1 and not a.no_config2 and a.dtype == "f64" and n == 262144 and H == 20:
             # BASELINE config 2 beside the headline: 4 096 instances at N = 10 through the WAVE family (the same
             # workload `--batch 4096 --horizon 10 --algo wave` times on its own; profiles/r02_config2_*)
             c2 = [torch.from_numpy(x).to(dev) for x in compact_inputs(10, 4096)]
@@ -567,7 +632,7 @@ def main():
                 d2 = time.perf_counter() - t1
             out["config2"] = {"workload": "batch 4096, N=10, fp64, WAVE family", "value": 4096 * 50 / d2,
                               "unit": "solves/s", "ms_per_step": d2 / 50 * 1e3}
-        if world == 1 and not a.no_mid and a.dtype == "f64" and n == 262144 and H == 20:
+        if a.full and world == 1 and not a.no_mid and a.dtype == "f64" and n == 262144 and H == 20:
             # A mid-size batch beside the headline: 16 384 instances of the same workload through AUTO -- too many for a
             # wavefront each, too few to fill the chip one lane each: the GROUP family's place (G lanes per instance)
             cm = [torch.from_numpy(x).to(dev) for x in compact_inputs(20, 16384)]
@@ -599,7 +664,7 @@ def main():
                     sb.solve_batch_compact(*cm, want_flags=False)
                 torch.cuda.synchronize()
                 out["mid_batch"]["bit_exact_ms_per_step"] = (time.perf_counter() - t1) / 10 * 1e3
-        if world == 1 and not a.no_config5 and a.dtype == "f64" and n == 262144 and H == 20:
+        if a.full and world == 1 and not a.no_config5 and a.dtype == "f64" and n == 262144 and H == 20:
             # BASELINE config 5 beside the headline: 65 536 instances split evenly over N in {5, 10, 20, 40}, interleaved,
             # ONE tpc_mpc_solve_batch_compact_mixed call per step (binned on the device; under AUTO the bins run one after
             # another, each with the whole chip: tpc_mpc_mixed.hip)
@@ -663,7 +728,7 @@ def main():
             c5["solves_per_s_f64"] = len(hz) / (c5["f64"] * 1e-3)
             c5["solves_per_s_f64_fast_capped"] = len(hz) / (c5["f64_fast_capped"] * 1e-3)
             out["config5"] = c5
-        if world == 1 and not a.no_config1 and not a.no_cpu and a.dtype == "f64" and n == 262144 and H == 20:
+        if a.full and world == 1 and not a.no_config1 and not a.no_cpu and a.dtype == "f64" and n == 262144 and H == 20:
             # BASELINE config 1 beside the headline: ONE trajectory, N=10 -- the call the reference's cycle() makes
             # (mpcControllerTobi -> tpc_mpc_solve_one), with a new speed in every call: on the calling thread (the host
             # path, TPC_MPC_OPT_HOST_SOLVE_ONE), through the resident wavefront, and real dlib on one host core beside
@@ -700,7 +765,7 @@ def main():
                 df, dr = ref1.solve_compact(10, np.array([2.0]), np.array([0.1]), np.array([0.05]), nthreads=1)
                 c1["max_abs_du_vs_dlib"] = float(max(abs(gres[0] - df[0]), abs(gres[1] - dr[0]), abs(hres[0] - df[0]), abs(hres[1] - dr[0])))
             out["config1"] = c1
-        if world == 1 and not a.no_config4 and a.dtype == "f64" and n == 262144 and H == 20:
+        if a.full and world == 1 and not a.no_config4 and a.dtype == "f64" and n == 262144 and H == 20:
             # BASELINE config 4's workload beside the headline: its WHOLE batch -- 2 097 152 trajectories, N=20, fp32 as
             # written -- on this ONE GPU.  Not a scaling number (that is `--gpus 8`, eight of these blocks side by side plus
             # the all-gather of 2 x 8 MiB per rank): what the eight ranks' arithmetic costs when one card does all of it.

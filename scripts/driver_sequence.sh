@@ -11,3 +11,6 @@ echo "== __graft_entry__.smoke()"
 python -c "import __graft_entry__ as g; g.smoke()" || exit 1
 echo "== python bench.py --gpus 1 --steps 20 --warmup 5"
 python bench.py --gpus 1 --steps 20 --warmup 5 2> gpurun_out/bench_default.err | tee gpurun_out/bench_default.json
+[ $? -eq 0 ] || exit 1
+echo "== python bench.py --gpus 1 --steps 20 --warmup 5 --full"
+timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full

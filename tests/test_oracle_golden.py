@@ -131,11 +131,19 @@ def test_float_oracle_tracks_the_pinned_one(oracle, oracle32):
     assert np.median(err) < 1e-4 and err.max() < 0.1
 
 
-def test_oracle_vs_live_dlib(oracle, dlibref):
-    """Where the real-dlib build exists, check fresh (non-fixture) inputs too."""
+def test_oracle_vs_live_dlib(oracle):
+    """Fresh inputs (beyond the compact_H* fixtures' instances) against real dlib: its recorded answers
+    (compact_fresh.npz, tests/golden/make_golden_fresh.py) always, and the live build too where it exists."""
+    from oracle.bindings import DlibRef
     from trajectory_controller_amd.synth import compact_inputs
+    g = load_golden("compact_fresh.npz")
+    live = DlibRef() if DlibRef.available() else None
     for H in (4, 10, 20):
         v, dy, dphi = compact_inputs(H, 512, first=5000)
-        f0, r0 = dlibref.solve_compact(H, v, dy, dphi, nthreads=4)
+        assert bits_equal(v, g[f"v_H{H}"]) and bits_equal(dy, g[f"dy_H{H}"]) and bits_equal(dphi, g[f"dphi_H{H}"])
+        f0, r0 = g[f"front_H{H}"], g[f"rear_H{H}"]
+        if live is not None:
+            lf, lr = live.solve_compact(H, v, dy, dphi, nthreads=4)
+            assert bits_equal(lf, f0) and bits_equal(lr, r0)
         f1, r1, _ = oracle.solve_compact(H, v, dy, dphi, nthreads=4)
         assert bits_equal(f0, f1) and bits_equal(r0, r1)
