@@ -31,6 +31,43 @@ def hard(r):
 def op(name): return Reg(f"%[{name}]")
 
 
+# ---- single steps of csrc/mpc_ub_model.h, shared by the projected-gradient iteration below and by
+#      scripts/gen_ub_cd_asm.py (the coordinate-descent iteration): operands are register / operand strings
+def fwd_step(z, y, zp, yp, x0, x1, ca, cas, ccs):
+    """Unit::fwd: (Z, Y) of step i into z, y from step i-1's (zp, yp)"""
+    return [f"v_fma_f64 {z}, {ca}, {yp}, {zp}",
+            f"v_fma_f64 {y}, -{ccs}, {x1}, {yp}",
+            f"v_fma_f64 {z}, {cas}, {x1}, {z}",
+            f"v_fma_f64 {y}, {ccs}, {x0}, {y}"]
+
+
+def bwd_last(n0, n1, pz, py, sgq0, sgq1, cq):
+    """Unit::bwd_last"""
+    return [f"v_mul_f64 {n0}, {sgq0}, {pz}",
+            f"v_fma_f64 {n1}, {sgq1}, {py}, -{cq}"]
+
+
+def bwd_step(n0, n1, pz, py, sgq0, sgq1, cq, ca):
+    """Unit::bwd (py is overwritten by e1)"""
+    return [f"v_fma_f64 {py}, {sgq1}, {py}, -{cq}",     # e1
+            f"v_fma_f64 {n1}, {ca}, {n0}, {n1}",
+            f"v_add_f64 {n1}, {n1}, {py}",              # t1 = fma(a, n0, n1) + e1
+            f"v_fma_f64 {n0}, {sgq0}, {pz}, {n0}"]
+
+
+def df0(d, x0, n1, sgrs0, cgl0, cc):
+    """Unit::df0 into d"""
+    return [f"v_fma_f64 {d}, {sgrs0}, {x0}, {cgl0}",
+            f"v_fma_f64 {d}, {cc}, {n1}, {d}"]
+
+
+def df1(d, x1, n0, n1, sgrs1, cgl1, cc, ca):
+    """Unit::df1 into d"""
+    return [f"v_fma_f64 {d}, {sgrs1}, {x1}, {cgl1}",
+            f"v_fma_f64 {d}, -{cc}, {n1}, {d}",
+            f"v_fma_f64 {d}, {ca}, {n0}, {d}"]
+
+
 class Plan:
     def __init__(self, H=20, NA=4, batch=3, all_hard=False, order="plain"):
         self.H, self.NA, self.NREG, self.BATCH = H, NA, H - NA, batch
@@ -77,17 +114,11 @@ class Plan:
             z, y = self.zy(half, i)
             x0, x1 = self.X[2 * i], self.X[2 * i + 1]
             if i == 0:
-                o += [f"v_accvgpr_read_b32 {t0.lo}, {A['z0lo']}", f"v_accvgpr_read_b32 {t0.hi}, {A['z0hi']}",   # Z[-1] = z0
-                      f"v_fma_f64 {z}, {C['ca']}, {S['slo1']}, {t0}",           # fma(a, Y[-1] = lo1, Z[-1])
-                      f"v_fma_f64 {y}, {C['ccs'].neg()}, {x1}, {S['slo1']}",
-                      f"v_fma_f64 {z}, {C['cas']}, {x1}, {z}",
-                      f"v_fma_f64 {y}, {C['ccs']}, {x0}, {y}"]
+                o += [f"v_accvgpr_read_b32 {t0.lo}, {A['z0lo']}", f"v_accvgpr_read_b32 {t0.hi}, {A['z0hi']}"]   # Z[-1] = z0
+                o += fwd_step(z, y, t0, S['slo1'], x0, x1, C['ca'], C['cas'], C['ccs'])   # Y[-1] = lo1
             else:
                 zp, yp = self.zy(half, i - 1)
-                o += [f"v_fma_f64 {z}, {C['ca']}, {yp}, {zp}",
-                      f"v_fma_f64 {y}, {C['ccs'].neg()}, {x1}, {yp}",
-                      f"v_fma_f64 {z}, {C['cas']}, {x1}, {z}",
-                      f"v_fma_f64 {y}, {C['ccs']}, {x0}, {y}"]
+                o += fwd_step(z, y, zp, yp, x0, x1, C['ca'], C['cas'], C['ccs'])
         return o
 
     # ---- the backward sweep: Unit::bwd_last / bwd (mpc.h:278-281), gradient (mpc.h:283), projected step (mpc.h:342),
@@ -119,17 +150,11 @@ class Plan:
             s0, s1 = (t0, t1) if last else (x0, x1)     # step 0 keeps x[0], x[1] for the lanes that stop
             d1 = t0 if last else o0                     # where df1 is formed
             if i == self.H - 1:
-                bw = [f"v_mul_f64 {n0}, {S['sgq0']}, {pz}",
-                      f"v_fma_f64 {n1}, {S['sgq1']}, {py}, {C['cq'].neg()}"]
+                o += bwd_last(n0, n1, pz, py, S['sgq0'], S['sgq1'], C['cq'])
             else:
-                bw = [f"v_fma_f64 {py}, {S['sgq1']}, {py}, {C['cq'].neg()}",     # e1
-                      f"v_fma_f64 {n1}, {C['ca']}, {n0}, {n1}",
-                      f"v_add_f64 {n1}, {n1}, {py}",                            # t1 = fma(a, n0, n1) + e1
-                      f"v_fma_f64 {n0}, {S['sgq0']}, {pz}, {n0}"]
-            o += bw
-            o += [f"v_fma_f64 {py}, {S['sgrs0']}, {x0}, {C['cgl0']}",
-                  f"v_fma_f64 {py}, {C['cc']}, {n1}, {py}",                 # df0
-                  f"v_fma_f64 {pz}, {C['cil'].neg()}, {py}, {x0} clamp"]    # vn0
+                o += bwd_step(n0, n1, pz, py, S['sgq0'], S['sgq1'], C['cq'], C['ca'])
+            o += df0(py, x0, n1, S['sgrs0'], C['cgl0'], C['cc'])
+            o += [f"v_fma_f64 {pz}, {C['cil'].neg()}, {py}, {x0} clamp"]    # vn0
             if test:
                 o += [f"v_add_f64 {s0}, {x0}, {pz.neg()}"]
                 if first:
@@ -142,10 +167,8 @@ class Plan:
                       f"v_fma_f64 {x0}, {C['cb']}, {o0}, {pz} clamp"]
                 if agpr:
                     o += [f"v_accvgpr_write_b32 {A[f'av{2 * i}lo']}, {pz.lo}", f"v_accvgpr_write_b32 {A[f'av{2 * i}hi']}, {pz.hi}"]
-            o += [f"v_fma_f64 {d1}, {S['sgrs1']}, {x1}, {C['cgl1']}",
-                  f"v_fma_f64 {d1}, {C['cc'].neg()}, {n1}, {d1}",
-                  f"v_fma_f64 {d1}, {C['ca']}, {n0}, {d1}",                 # df1
-                  f"v_fma_f64 {py}, {C['cil'].neg()}, {d1}, {x1} clamp"]    # vn1
+            o += df1(d1, x1, n0, n1, S['sgrs1'], C['cgl1'], C['cc'], C['ca'])
+            o += [f"v_fma_f64 {py}, {C['cil'].neg()}, {d1}, {x1} clamp"]    # vn1
             if test:
                 o += [f"v_add_f64 {s1}, {x1}, {py.neg()}",
                       f"v_min_f64 {s1}, {d1.abs()}, {s1.abs()}",

@@ -16,6 +16,7 @@
 
 #include "mpc_lane.h"
 #include "mpc_ub_model.h"
+#include "mpc_ub_cd_asm.h"
 
 namespace tpc {
 
@@ -53,6 +54,17 @@ template <typename T, int H> struct UbCdPlan {
     static constexpr bool fast = true;   // (the select-free sweep wherever the screen allows it)
 };
 
+// fp64, N = 20, both inputs sharing their bounds (the headline workload): the fast build's iteration loop is the generated
+// asm statement of mpc_ub_cd_asm.h (scripts/gen_ub_cd_asm.py) -- same arithmetic, same decisions, same bits; 627 instructions
+// per iteration against the compiler's 730, and x read ahead of its use.  TPC_UB_CD_NO_ASM: the compiled loop (A/B builds).
+template <typename T, int H, bool EQB> struct UbCdAsm {
+#ifdef TPC_UB_CD_NO_ASM
+    static constexpr bool value = false;
+#else
+    static constexpr bool value = sizeof(T) == 8 && H == kUbCdAsmH && EQB && UbCdPlan<T, H>::x_in_lds;
+#endif
+};
+
 TPC_DEV double cd_ldexp(double x, int e) { return __builtin_ldexp(x, e); }
 TPC_DEV float cd_ldexp(float x, int e) { return __builtin_ldexpf(x, e); }
 
@@ -65,8 +77,10 @@ __global__ __launch_bounds__(64, (CdOcc<T, H>::value)) void ub_cd_kernel(Compact
     using P = UbCdPlan<T, H>;
     constexpr int RL = LaneRec<T, H>::kLen;
     constexpr bool MIRROR = P::mirror, XL = P::x_in_lds;
-    __shared__ T s_iqd[2 * H][kWave];
-    __shared__ T s_x[MIRROR ? 2 * H : 1][kWave];
+    // one array: 1 / (Q_diag s) in rows [0, 2H), x in the rows after (the asm loop reads a winner's pair with one instruction)
+    __shared__ T s_cd[2 * H + (MIRROR ? 2 * H : 1)][kWave];
+    T (*const s_iqd)[kWave] = s_cd;
+    T (*const s_x)[kWave] = s_cd + 2 * H;
     const int lane = threadIdx.x;
     const int64_t k = (int64_t)blockIdx.x * kWave + lane;
     if (k >= g.n) return;
@@ -171,10 +185,21 @@ __global__ __launch_bounds__(64, (CdOcc<T, H>::value)) void ub_cd_kernel(Compact
         iter += act ? 1u : 0u;
     };
     if (P::fast && failing == 0ull) {
+        if constexpr (UbCdAsm<T, H, EQB>::value) {
+            static_assert(kUbCdAsmXRow == 2 * H, "LDS layout the generated loop reads");
+            const UbCdAsmUniform u = {m.gq0, m.gq1, m.grs0, m.grs1, m.lo1, (double)kn.eps};
+            uint64_t live = __ballot(!stopped);
+            uint32_t lu = 0;
+            const uint32_t vaddr = (uint32_t)(uintptr_t)&s_cd[0][lane];   // (the low half of a generic LDS address is the LDS offset)
+            ub_cd_asm_loop(u, m.a, m.c, m.as1, m.cs0, m.z0, m.q1th, m.grl0, m.grl1, vaddr, cd_iters, live, iter, lu);
+            stopped = ((live >> lane) & 1ull) == 0ull;
+            vinit = lu != 0u && lu == kn.smo_iters;
+        } else {
 #pragma unroll 1
-        for (uint32_t it = 0; it < cd_iters; ++it) {
-            if (__ballot(!stopped) == 0ull) break;
-            iteration(std::true_type{}, it);
+            for (uint32_t it = 0; it < cd_iters; ++it) {
+                if (__ballot(!stopped) == 0ull) break;
+                iteration(std::true_type{}, it);
+            }
         }
     } else {
 #pragma unroll 1
