@@ -32,7 +32,9 @@
 extern "C" {
 #endif
 
-#define TPC_MPC_ABI_VERSION 5   /* 5 = 4 + new symbols only (the split-named sharded entries); 4 broke 3: tpc_mpc_params.reserved became .options and must be zero-initialised */
+#define TPC_MPC_ABI_VERSION 5   /* 5 = 4 + new symbols only (the split-named sharded entries; later additions, such as
+                                   tpc_mpc_solve_batch_general_backward, are new symbols and structs only and keep 5);
+                                   4 broke 3: tpc_mpc_params.reserved became .options and must be zero-initialised */
 
 typedef struct tpc_mpc_context* tpc_mpc_handle;
 
@@ -179,8 +181,9 @@ int tpc_mpc_default_params(tpc_mpc_params* p, int horizon);
  * is tpc_mpc_solve_one -- on the calling thread, in the LANE_FMA family's arithmetic (csrc/tpc_mpc_host.cpp; fp64, the
  * specialised horizons, finite bounds with upper > lower, a CPU with fused multiply-add) -- which is what a host that
  * solves one short-horizon problem per cycle wants ("usable from any single thread without a GPU"): at
- * the reference's N = 4 a core needs ~3 us where the GPU round trip needs ~10.  Every batch entry point returns
- * TPC_MPC_ERR_NO_DEVICE on such a handle.  AUTO's re-solve of capped instances needs the GPU: a host-only handle
+ * the reference's N = 4 a core needs ~3 us where the GPU round trip needs ~10.  The one other call it serves is
+ * tpc_mpc_solve_batch_general_backward with TPC_MPC_HOST memory, also on the calling thread.  Every other batch entry
+ * point returns TPC_MPC_ERR_NO_DEVICE on such a handle.  AUTO's re-solve of capped instances needs the GPU: a host-only handle
  * returns the tolerance answer and raises TPC_MPC_FLAG_MAX_ITER. */
 #define TPC_MPC_DEVICE_NONE (-1)
 int tpc_mpc_create(int device, tpc_mpc_handle* out);
@@ -285,6 +288,41 @@ typedef struct tpc_mpc_general_io {
 int tpc_mpc_solve_batch_general(tpc_mpc_handle h, const tpc_mpc_params* p,
                                 const tpc_mpc_general_io* io, uint32_t* flags_out, int mem,
                                 void* stream);
+
+/* Inputs and outputs of tpc_mpc_solve_batch_general_backward, SoA with the io's leading dimension ld:
+ *   controls[H*I]       the solved sequence, as tpc_mpc_solve_batch_general returns it in controls_inout
+ *   grad_controls[H*I]  dL/du: the gradient of the caller's loss with respect to those controls
+ *   dA[4] dB[2*I] dC[2] dQ[2] dR[I] dlower[I] dupper[I] dx0[2] dtargets[H*2]
+ *                       optional outputs, dL/d(the io array of the same name and shape); overwritten; NULL = not computed
+ *   kkt_residual[1]     optional output: max |df| over the free components at `controls` (0 when none is free) */
+typedef struct tpc_mpc_general_grad {
+    const void *controls, *grad_controls;
+    void *dA, *dB, *dC, *dQ, *dR, *dlower, *dupper, *dx0, *dtargets;
+    void* kkt_residual;
+} tpc_mpc_general_grad;
+
+/* No reference counterpart (dlib::mpc has no derivative).  The backward pass of tpc_mpc_solve_batch_general: for n
+ * instances, the gradient of a loss L(u) with respect to every model input, given the controls u and dL/du.
+ *   Definition.  Component (t, j) of u is ACTIVE iff u[t,j] <= lower[j] or u[t,j] >= upper[j] (the comparisons of
+ *   mpc.h:298-299 without the sign of the gradient; lower == upper is always active); the others form F.  The map
+ *   differentiated holds the active components on their bounds and the free ones at the stationary point of dlib's QP
+ *   on F: u_F = -H_FF^-1 (MM_F + H_FA u_A), with H and MM as in mpc.h:255-283.  If u is the exact optimum this is the
+ *   derivative of the optimum; dlib's default eps (0.01) leaves a loose u, for which it is the derivative of the optimum
+ *   on u's active set -- a small eps gives accurate gradients, and kkt_residual says how close u is.
+ *   Method.  The adjoint direction w = H_FF^-1 dL/du_F (w = 0 on the active set) comes from a masked Riccati (LQR)
+ *   sweep over the horizon, not from a dense Hessian: O(H) per instance, one lane each (csrc/mpc_grad_model.h).
+ *   The per-step factors live in device scratch of the handle.
+ * io: as for tpc_mpc_solve_batch_general; its controls_inout, v_inout, u0 and iters are ignored.  p is checked as for
+ * the solve; what the backward pass uses of it is the horizon (1..64) and the dtype, which must be TPC_MPC_F64
+ * (TPC_MPC_ERR_BAD_ARG otherwise).  Supported: every horizon 1..64, one or two inputs.
+ * An instance with NaN / Inf inputs, controls or grad_controls (bounds may be infinite) raises TPC_MPC_FLAG_NONFINITE,
+ * one that breaks dlib's requires clause TPC_MPC_FLAG_BAD_MODEL; such an instance gets all-zero gradients and a zero
+ * residual.  Memory, stream and flags as tpc_mpc_solve_batch_general (HOST arrays are staged; with DEVICE memory the
+ * call is asynchronous on `stream` unless flags_out != NULL).  A host-only handle (TPC_MPC_DEVICE_NONE) runs HOST
+ * batches on the calling thread, in the same arithmetic bit for bit, and returns TPC_MPC_ERR_NO_DEVICE for DEVICE. */
+int tpc_mpc_solve_batch_general_backward(tpc_mpc_handle h, const tpc_mpc_params* p,
+                                         const tpc_mpc_general_io* io, const tpc_mpc_general_grad* g,
+                                         uint32_t* flags_out, int mem, void* stream);
 
 /* Closed loop on device: `steps` successive operator() calls per controller with warm start and
  * target shift (mpc.h:229-239), plant update x <- A x + B u + C between calls (the loop of

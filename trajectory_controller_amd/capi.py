@@ -38,7 +38,8 @@ EXPORTS = ("tpc_mpc_default_params", "tpc_mpc_create", "tpc_mpc_destroy", "tpc_m
            "tpc_mpc_comm_destroy", "tpc_mpc_group_begin", "tpc_mpc_group_end", "tpc_mpc_shard_range",
            "tpc_mpc_solve_batch_compact_sharded", "tpc_mpc_comm_test_mode",
            "tpc_mpc_solve_batch_general_sharded", "tpc_mpc_last_flags", "tpc_mpc_gather_shards",
-           "tpc_mpc_shard_map", "tpc_mpc_solve_batch_compact_sharded_split", "tpc_mpc_gather_shards_split")
+           "tpc_mpc_shard_map", "tpc_mpc_solve_batch_compact_sharded_split", "tpc_mpc_gather_shards_split",
+           "tpc_mpc_solve_batch_general_backward")
 SPLIT_BLOCK, SPLIT_INTERLEAVED = 0, 1
 SPLITS = {"block": SPLIT_BLOCK, "interleaved": SPLIT_INTERLEAVED}
 
@@ -60,6 +61,13 @@ class GeneralIO(C.Structure):
                 ("R", C.c_void_p), ("lower", C.c_void_p), ("upper", C.c_void_p),
                 ("x0", C.c_void_p), ("targets", C.c_void_p), ("controls_inout", C.c_void_p),
                 ("v_inout", C.c_void_p), ("u0", C.c_void_p), ("iters", C.c_void_p)]
+
+
+class GeneralGrad(C.Structure):
+    """struct tpc_mpc_general_grad"""
+    _fields_ = [("controls", C.c_void_p), ("grad_controls", C.c_void_p), ("dA", C.c_void_p), ("dB", C.c_void_p),
+                ("dC", C.c_void_p), ("dQ", C.c_void_p), ("dR", C.c_void_p), ("dlower", C.c_void_p),
+                ("dupper", C.c_void_p), ("dx0", C.c_void_p), ("dtargets", C.c_void_p), ("kkt_residual", C.c_void_p)]
 
 
 class Trajectories(C.Structure):
@@ -114,6 +122,8 @@ def load_library(path: str | None = None) -> C.CDLL:
                                                 vp, u32p, C.c_int, vp]
     lib.tpc_mpc_solve_batch_general.argtypes = [vp, C.POINTER(Params), C.POINTER(GeneralIO), u32p,
                                                 C.c_int, vp]
+    lib.tpc_mpc_solve_batch_general_backward.argtypes = [vp, C.POINTER(Params), C.POINTER(GeneralIO),
+                                                         C.POINTER(GeneralGrad), u32p, C.c_int, vp]
     lib.tpc_mpc_solve_batch_general_sharded.argtypes = [vp, C.POINTER(Params), C.POINTER(GeneralIO), u32p, vp]
     lib.tpc_mpc_rollout.argtypes = [vp, C.POINTER(Params), C.POINTER(GeneralIO), C.c_int32, vp, vp, vp,
                                     vp, u32p, C.c_int, vp]

@@ -1,10 +1,12 @@
 // C ABI of libtpc_mpc.so (include/tpc_mpc.h): argument validation, host<->device staging, kernel
 // family selection.  No solver arithmetic lives here and there is no CPU solve path: every entry
 // point ends in a gfx950 kernel launch or fails.  (Mixed-horizon batches: tpc_mpc_mixed.hip; sharded
-// solves over RCCL: tpc_mpc_comm.cpp; the resident single-solve kernel: tpc_mpc_one.hip.)
+// solves over RCCL: tpc_mpc_comm.cpp; the resident single-solve kernel: tpc_mpc_one.hip; the gradient kernel and its
+// host path for a host-only handle: mpc_grad.hip.)
 #include "tpc_mpc_context.h"
 #include "tpc_mpc_experimental.h"
 #include "auto_table.h"
+#include "mpc_grad_model.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -38,6 +40,11 @@ TPC_DECL_H(4) TPC_DECL_H(5) TPC_DECL_H(10) TPC_DECL_H(20)
 #define TPC_DECL_H(h) hipError_t group_compact_h##h(int, int, int, const CompactArgs&, const Knobs&, const Workspace&, hipStream_t);
 TPC_DECL_H(10) TPC_DECL_H(20) TPC_DECL_H(30) TPC_DECL_H(40)
 #undef TPC_DECL_H
+
+// the backward pass of the general form (mpc_grad.hip)
+int64_t grad_scratch_bytes(int I, int H, int64_t n);
+hipError_t grad_general(int I, int H, const grad::Args& a, void* ws, uint32_t* flags, hipStream_t s);
+uint32_t grad_general_host(int I, int H, const grad::Args& a);
 
 thread_local char g_create_error[kTpcErrLen] = "";
 }  // namespace tpc
@@ -865,6 +872,7 @@ int tpc_mpc_destroy(tpc_mpc_handle h) {
         if (h->stage) (void)hipFree(h->stage);
         if (h->roll) (void)hipFree(h->roll);
         if (h->cap_iters) (void)hipFree(h->cap_iters);
+        if (h->grad_ws) (void)hipFree(h->grad_ws);
         if (h->mix) (void)hipFree(h->mix);
         if (h->gather) (void)hipFree(h->gather);
         if (h->pre_stream) { (void)hipStreamSynchronize(h->pre_stream); (void)hipStreamDestroy(h->pre_stream); }
@@ -1072,6 +1080,95 @@ int tpc_mpc_solve_batch_general(tpc_mpc_handle h, const tpc_mpc_params* p,
                 HIP_TRY(h, copy_rows(io->controls_inout, hp, a.controls, dp, w, H * I, hipMemcpyDeviceToHost, s));
             if (io->v_inout) HIP_TRY(h, copy_rows(io->v_inout, hp, a.v, dp, w, H * I, hipMemcpyDeviceToHost, s));
             if (io->iters) HIP_TRY(h, hipMemcpyAsync(io->iters, a.iters, n * 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(h, hipStreamSynchronize(s));
+        }
+        rc = order.end();
+        if (rc) return rc;
+        return finish_flags(h, flags_out, s);
+    });
+}
+
+int tpc_mpc_solve_batch_general_backward(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io,
+                                         const tpc_mpc_general_grad* g, uint32_t* flags_out, int mem, void* stream) {
+    return guarded(h, [&]() -> int {
+        int rc = check_common(h, p, true);
+        if (rc) return rc;
+        if (p->dtype != TPC_MPC_F64)
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "tpc_mpc_solve_batch_general_backward is fp64 only: p->dtype must be TPC_MPC_F64");
+        rc = check_general_io(h, io, mem);
+        if (rc) return rc;
+        if (!g) return fail(h, TPC_MPC_ERR_BAD_ARG, "null gradient struct");
+        if (h->host_only && mem == TPC_MPC_DEVICE)
+            return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): the backward pass takes HOST memory only");
+        if (io->n == 0) { if (flags_out) *flags_out = 0; return TPC_MPC_OK; }
+        if (!io->A || !io->B || !io->C || !io->Q || !io->R || !io->lower || !io->upper || !io->x0 || !io->targets)
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "null batch pointer");
+        if (!g->controls || !g->grad_controls) return fail(h, TPC_MPC_ERR_BAD_ARG, "null controls / grad_controls");
+        const int I = io->inputs, H = p->horizon;
+        const int64_t n = io->n;
+        // the io's and g's arrays in order: 11 inputs, then 10 outputs, with their component counts
+        const void* src[11] = {io->A, io->B, io->C, io->Q, io->R, io->lower, io->upper, io->x0, io->targets,
+                               g->controls, g->grad_controls};
+        void* dst[10] = {g->dA, g->dB, g->dC, g->dQ, g->dR, g->dlower, g->dupper, g->dx0, g->dtargets, g->kkt_residual};
+        const int comps[21] = {4, 2 * I, 2, 2, I, I, I, 2, 2 * H, H * I, H * I,
+                               4, 2 * I, 2, 2, I, I, I, 2, 2 * H, 1};
+        auto bind = [](grad::Args* a, const void* const* in, void* const* out) {
+            a->A = (const double*)in[0]; a->B = (const double*)in[1]; a->C = (const double*)in[2];
+            a->Q = (const double*)in[3]; a->R = (const double*)in[4]; a->lo = (const double*)in[5];
+            a->hi = (const double*)in[6]; a->x0 = (const double*)in[7]; a->targets = (const double*)in[8];
+            a->u = (const double*)in[9]; a->g = (const double*)in[10];
+            a->dA = (double*)out[0]; a->dB = (double*)out[1]; a->dC = (double*)out[2]; a->dQ = (double*)out[3];
+            a->dR = (double*)out[4]; a->dlo = (double*)out[5]; a->dhi = (double*)out[6]; a->dx0 = (double*)out[7];
+            a->dtargets = (double*)out[8]; a->kkt = (double*)out[9];
+        };
+        grad::Args a;
+        std::memset(&a, 0, sizeof(a));
+        a.n = n;
+        if (h->host_only) {   // on the calling thread, straight from and into the caller's arrays
+            a.ld = io->ld;
+            bind(&a, src, dst);
+            const uint32_t f = grad_general_host(I, H, a);
+            if (flags_out) *flags_out = f;
+            return TPC_MPC_OK;
+        }
+        HIP_TRY(h, hipSetDevice(h->device));
+        hipStream_t s = (hipStream_t)stream;
+        StreamOrderScope order(h, s);
+        rc = order.begin();
+        if (rc) return rc;
+        rc = ensure(h, &h->grad_ws, &h->grad_ws_bytes, pad256(grad_scratch_bytes(I, H, n)));
+        if (rc) return rc;
+        const int64_t lds = (n + 63) / 64 * 64;
+        int64_t off[21] = {0};
+        if (mem == TPC_MPC_DEVICE) {
+            a.ld = io->ld;
+            bind(&a, src, dst);
+        } else {
+            // HOST arrays: every component row copied on its own (n elements, never ld), as tpc_mpc_solve_batch_general
+            int64_t total = 0;
+            for (int c = 0; c < 21; ++c) { off[c] = total; total += pad256((int64_t)comps[c] * lds * 8); }
+            rc = ensure(h, &h->stage, &h->stage_bytes, total);
+            if (rc) return rc;
+            char* b = (char*)h->stage;
+            const void* sin[11];
+            void* sout[10];
+            for (int c = 0; c < 11; ++c) {
+                HIP_TRY(h, copy_rows(b + off[c], lds * 8, src[c], io->ld * 8, n * 8, comps[c], hipMemcpyHostToDevice, s));
+                sin[c] = b + off[c];
+            }
+            for (int c = 0; c < 10; ++c) sout[c] = dst[c] ? b + off[11 + c] : nullptr;
+            a.ld = lds;
+            bind(&a, sin, sout);
+        }
+        HIP_TRY(h, hipMemsetAsync(h->ws_words + 1, 0, sizeof(uint32_t), s));
+        hipError_t e = grad_general(I, H, a, h->grad_ws, h->ws_words + 1, s);
+        if (e != hipSuccess) return hip_fail(h, e, "kernel launch");
+        if (mem == TPC_MPC_HOST) {
+            const char* b = (const char*)h->stage;
+            for (int c = 0; c < 10; ++c)
+                if (dst[c])
+                    HIP_TRY(h, copy_rows(dst[c], io->ld * 8, b + off[11 + c], lds * 8, n * 8, comps[11 + c],
+                                         hipMemcpyDeviceToHost, s));
             HIP_TRY(h, hipStreamSynchronize(s));
         }
         rc = order.end();

@@ -44,6 +44,9 @@ struct tpc_mpc_context {
     // iteration counts of a tolerance family's pass when the caller asked for none (AUTO re-solves what ended on the cap)
     void* cap_iters = nullptr;
     int64_t cap_iters_bytes = 0;
+    // per-step factors and states of tpc_mpc_solve_batch_general_backward (mpc_grad_model.h: [quantity][step][n])
+    void* grad_ws = nullptr;
+    int64_t grad_ws_bytes = 0;
     // AUTO's presolve (tpc_mpc_api.cpp, presolve_begin): the instances predicted to end on the iteration cap are solved
     // bit-exactly on a stream of the handle's own BESIDE the tolerance family's pass: LANE scratch + side outputs, stream, events
     void* pre = nullptr;

@@ -407,6 +407,77 @@ class MpcSolver:
         self.last_flags = flags.value
         return (u0, iters) if want_iters else u0
 
+    GRAD_NAMES = ("A", "B", "C", "Q", "R", "lower", "upper", "x0", "targets", "kkt_residual")
+
+    def solve_batch_general_backward(self, A, B, Cc, Q, R, lower, upper, x0, targets, controls, grad_controls,
+                                     inputs: Optional[int] = None, want=GRAD_NAMES, want_flags: bool = True, **over):
+        """Backward pass of solve_batch_general (tpc_mpc_solve_batch_general_backward), fp64 only.
+
+        Arrays as in solve_batch_general (numpy: HOST memory, CUDA torch tensors: DEVICE memory on the current stream);
+        `controls` [H*I, n] is the solved sequence, `grad_controls` [H*I, n] is dL/d(controls).  Returns a dict of
+        dL/d(input) of the input's shape, keyed "A", "B", "C", "Q", "R", "lower", "upper", "x0", "targets", plus
+        "kkt_residual" [n] (max |gradient| over the free components); `want` names the outputs to compute.
+        Instances with non-finite data or a model that breaks dlib's requires clause get zeros and raise last_flags
+        (want_flags=False leaves last_flags at 0 and keeps a DEVICE call asynchronous)."""
+        p = self._params(**over)
+        H = p.horizon
+        unknown = set(want) - set(self.GRAD_NAMES)
+        if unknown:
+            raise ValueError(f"unknown gradient names {sorted(unknown)}")
+        if _is_torch(A):
+            import torch
+            n = A.shape[-1]
+            I = inputs or R.shape[0]
+
+            def ptr(t, rows):
+                if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == (rows, n)):
+                    raise ValueError(f"expected contiguous fp64 CUDA tensor [{rows},{n}]")
+                return t.data_ptr()
+
+            def new(rows):
+                return torch.empty((rows, n), dtype=torch.float64, device=A.device)
+            stream = C.c_void_p(torch.cuda.current_stream(A.device).cuda_stream)
+            mem = capi.DEVICE
+        else:
+            A = np.ascontiguousarray(A, dtype=np.float64)
+            n = A.shape[-1]
+            I = inputs or np.asarray(R).shape[0]
+            keep = []
+
+            def ptr(a, rows):
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.shape != (rows, n):
+                    raise ValueError(f"expected an array [{rows},{n}]")
+                keep.append(a)
+                return a.ctypes.data
+
+            def new(rows):
+                return np.empty((rows, n), dtype=np.float64)
+            stream = None
+            mem = capi.HOST
+        rows = {"A": 4, "B": 2 * I, "C": 2, "Q": 2, "R": I, "lower": I, "upper": I, "x0": 2, "targets": 2 * H,
+                "kkt_residual": 1}
+        out = {k: new(rows[k]) for k in want}
+
+        def optr(k):
+            if k not in out:
+                return None
+            return out[k].data_ptr() if mem == capi.DEVICE else out[k].ctypes.data
+        io = capi.GeneralIO(inputs=I, n=n, ld=n, A=ptr(A, 4), B=ptr(B, 2 * I), C=ptr(Cc, 2), Q=ptr(Q, 2),
+                            R=ptr(R, I), lower=ptr(lower, I), upper=ptr(upper, I), x0=ptr(x0, 2),
+                            targets=ptr(targets, 2 * H), controls_inout=None, v_inout=None, u0=None, iters=None)
+        g = capi.GeneralGrad(controls=ptr(controls, H * I), grad_controls=ptr(grad_controls, H * I),
+                             dA=optr("A"), dB=optr("B"), dC=optr("C"), dQ=optr("Q"), dR=optr("R"),
+                             dlower=optr("lower"), dupper=optr("upper"), dx0=optr("x0"), dtargets=optr("targets"),
+                             kkt_residual=optr("kkt_residual"))
+        flags = C.c_uint32(0)
+        self._check(self._lib.tpc_mpc_solve_batch_general_backward(self._h, C.byref(p), C.byref(io), C.byref(g),
+                                                                   C.byref(flags) if want_flags else None, mem, stream))
+        self.last_flags = flags.value
+        if "kkt_residual" in out:
+            out["kkt_residual"] = out["kkt_residual"].reshape(n)
+        return out
+
     def rollout(self, steps: int, A, B, Cc, Q, R, lower, upper, x0, targets, new_last_targets=None,
                 controls=None, v_state=None, inputs: Optional[int] = None, want_states: bool = True,
                 want_iters: bool = False, **over):
