@@ -33,7 +33,8 @@ extern "C" {
 #endif
 
 #define TPC_MPC_ABI_VERSION 5   /* 5 = 4 + new symbols only (the split-named sharded entries; later additions, such as
-                                   tpc_mpc_solve_batch_general_backward, are new symbols and structs only and keep 5);
+                                   tpc_mpc_solve_batch_general_backward and tpc_mpc_rollout_record / _backward,
+                                   are new symbols and structs only and keep 5);
                                    4 broke 3: tpc_mpc_params.reserved became .options and must be zero-initialised */
 
 typedef struct tpc_mpc_context* tpc_mpc_handle;
@@ -335,6 +336,59 @@ int tpc_mpc_rollout(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_gen
                     int32_t steps, const void* new_last_targets, void* controls_out,
                     void* states_out, int32_t* iters_out, uint32_t* flags_out, int mem,
                     void* stream);
+
+/* tpc_mpc_rollout that also records every step's solved sequence, for tpc_mpc_rollout_backward.
+ * sequences_out (required): SoA [steps*H*I]; step k's sequence U_k (what controls_inout holds after the k-th
+ * operator() call, mpc.h:229-239) is rows k*H*I .. (k+1)*H*I-1 in the controls_inout order.  Everything else, the bits
+ * of every output included, is tpc_mpc_rollout's (one implementation; tpc_mpc_rollout records nothing). */
+int tpc_mpc_rollout_record(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io,
+                           int32_t steps, const void* new_last_targets, void* controls_out,
+                           void* states_out, int32_t* iters_out, void* sequences_out, uint32_t* flags_out,
+                           int mem, void* stream);
+
+/* Inputs and outputs of tpc_mpc_rollout_backward, SoA with the io's leading dimension ld:
+ *   sequences[steps*H*I]  the recorded sequences, as tpc_mpc_rollout_record returns them (required)
+ *   states[steps*2]       the recorded states_out of the same call (required)
+ *   grad_controls[steps*I], grad_states[steps*2]
+ *                         dL/dcontrols_out, dL/dstates_out; optional, NULL = zero
+ *   dA[4] dB[2*I] dC[2] dQ[2] dR[I] dlower[I] dupper[I] dx0[2] dtargets[H*2]
+ *                         optional outputs, dL/d(the io array of the same name and shape); overwritten; NULL = not computed
+ *   dnew_last_targets[steps*2]  optional output, dL/dnew_last_targets (row 0, never read by the rollout, is 0)
+ *   kkt_residual[1]       optional output: max over the steps of the single solve's residual */
+typedef struct tpc_mpc_rollout_grad {
+    const void *sequences, *states, *grad_controls, *grad_states;
+    void *dA, *dB, *dC, *dQ, *dR, *dlower, *dupper, *dx0, *dtargets, *dnew_last_targets;
+    void* kkt_residual;
+} tpc_mpc_rollout_grad;
+
+/* No reference counterpart.  The backward pass of tpc_mpc_rollout (the closed loop of test/mpc.cpp:301-316): for n
+ * instances, the gradient of a loss L(controls_out, states_out) with respect to every model input, the initial state,
+ * the initial targets and new_last_targets.
+ *   Definition.  S = steps.  x_0 = io->x0; step k solves from x_k with the targets T_k and returns U_k (its row 0 is
+ *   u0_k = controls_out[k]); x_{k+1} = A x_k + B u0_k + C = states_out[k].  The target shift of operator()
+ *   (mpc.h:236-237) and set_last_target give T_k[t] = targets[t+k] for t + k <= H-1, else, with m = t + k - (H-1),
+ *   new_last_targets[m] (targets[H-1] when new_last_targets is NULL).  Each step is differentiated as
+ *   tpc_mpc_solve_batch_general_backward defines it (active set read off U_k, the free components at the stationary
+ *   point); the warm start (controls_inout, v_inout) gets no gradient.  x_k for k >= 1 is read from `states`, not
+ *   recomputed, so the derivative is taken at the forward's bits.
+ *   Method.  One reverse sweep per instance, lambda = 0:
+ *     for k = S-1 .. 0:  mu = lambda + dL/dstates_out[k];  dA += mu x_k', dB += mu u0_k', dC += mu;
+ *                        the single-solve backward of step k with dL/dU_k = (dL/dcontrols_out[k] + B' mu) on row 0,
+ *                        0 elsewhere, which adds to dA .. dupper, gives dL/dT_k (added into dtargets /
+ *                        dnew_last_targets through the map above) and dL/dx_k of the solve, d;
+ *                        lambda = A' mu + d
+ *     dx0 = lambda;  kkt_residual = max over the steps.
+ *   One lane per instance runs the whole sweep in one launch; lambda and the sums stay in registers, the per-step
+ *   Riccati workspace of the handle (slots * H doubles per instance) is reused by every step.
+ * io, p, steps and new_last_targets: as for the tpc_mpc_rollout call that recorded sequences and states (io's
+ * controls_inout, v_inout, u0 and iters are ignored).  fp64 only, horizons 1..64, one or two inputs.
+ * dnew_last_targets without new_last_targets is TPC_MPC_ERR_BAD_ARG.  Flags, memory, stream and the host-only
+ * handle as tpc_mpc_solve_batch_general_backward: an instance with non-finite data, sequences, states or gradients
+ * (TPC_MPC_FLAG_NONFINITE) or a model that breaks dlib's requires clause (TPC_MPC_FLAG_BAD_MODEL) gets all-zero
+ * outputs. */
+int tpc_mpc_rollout_backward(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io,
+                             int32_t steps, const void* new_last_targets, const tpc_mpc_rollout_grad* g,
+                             uint32_t* flags_out, int mem, void* stream);
 
 /* ---- batched cycle(): raw trajectories in, CarCommand fields out -------------------------------- */
 

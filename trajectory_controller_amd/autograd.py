@@ -1,4 +1,5 @@
-"""torch autograd over the batched general-form solve: `mpc_general` and the reference controller's `mpc_compact`.
+"""torch autograd over the batched general-form solve: `mpc_general` and the reference controller's `mpc_compact`,
+and over the closed loop: `mpc_rollout` (forward MpcSolver.rollout_record, backward tpc_mpc_rollout_backward).
 
 Forward is MpcSolver.solve_batch_general from a fresh controller (zero controls); backward is
 tpc_mpc_solve_batch_general_backward on torch's current stream (include/tpc_mpc.h gives the definition of the
@@ -52,6 +53,49 @@ def mpc_general(solver, A, B, Cc, Q, R, lower, upper, x0, targets, **over):
         if not (t.is_cuda and t.dtype == torch.float64):
             raise ValueError("mpc_general takes CUDA fp64 tensors")
     return _MpcGeneral.apply(solver, over, A, B, Cc, Q, R, lower, upper, x0, targets)
+
+
+class _MpcRollout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, solver, steps, over, A, B, Cc, Q, R, lower, upper, x0, targets, new_last_targets):
+        I = R.shape[0]
+        ins = [t.detach().contiguous() for t in (A, B, Cc, Q, R, lower, upper, x0, targets)]
+        nlt = None if new_last_targets is None else new_last_targets.detach().contiguous()
+        controls, states, sequences, _ = solver.rollout_record(steps, *ins, nlt, inputs=I, **over)
+        ctx.solver, ctx.steps, ctx.over, ctx.I = solver, steps, over, I
+        ctx.has_nlt = nlt is not None
+        ctx.save_for_backward(*ins, *(() if nlt is None else (nlt,)), states, sequences)
+        return controls, states
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_controls, grad_states):
+        saved = list(ctx.saved_tensors)
+        ins, rest = saved[:9], saved[9:]
+        nlt = rest.pop(0) if ctx.has_nlt else None
+        states, sequences = rest
+        names = ("A", "B", "C", "Q", "R", "lower", "upper", "x0", "targets", "new_last_targets")
+        want = tuple(k for k, need in zip(names, ctx.needs_input_grad[3:]) if need)
+        if not want:
+            return (None,) * 13
+        g = ctx.solver.rollout_backward(ctx.steps, *ins, nlt, sequences=sequences, states=states,
+                                        grad_controls=None if grad_controls is None else grad_controls.contiguous(),
+                                        grad_states=None if grad_states is None else grad_states.contiguous(),
+                                        inputs=ctx.I, want=want, want_flags=False, **ctx.over)
+        return (None, None, None) + tuple(g.get(k) for k in names)
+
+
+def mpc_rollout(solver, steps, A, B, Cc, Q, R, lower, upper, x0, targets, new_last_targets=None, **over):
+    """The closed loop of n fresh dlib::mpc<2,I,H> controllers (MpcSolver.rollout: `steps` warm-started operator()
+    calls with the target shift and the plant update x <- A x + B u + C between them) as a differentiable function.
+    Returns (controls [steps*I, n], states [steps*2, n]); gradients reach A, B, C, Q, R, lower, upper, x0, targets and
+    new_last_targets [steps*2, n] (component-major CUDA fp64 tensors, solve_batch_general's layout).  Each step is
+    differentiated on the active set of its solved sequence (tpc_mpc_rollout_backward, include/tpc_mpc.h); the warm
+    start gets no gradient.  Pass a small eps for accurate gradients.  `over` overrides the solver's parameters."""
+    for t in (A, B, Cc, Q, R, lower, upper, x0, targets) + (() if new_last_targets is None else (new_last_targets,)):
+        if not (t.is_cuda and t.dtype == torch.float64):
+            raise ValueError("mpc_rollout takes CUDA fp64 tensors")
+    return _MpcRollout.apply(solver, int(steps), over, A, B, Cc, Q, R, lower, upper, x0, targets, new_last_targets)
 
 
 def mpc_compact(solver, v, delta_y, delta_phi, weights, step_size=0.1, wheelbase=0.21,

@@ -39,7 +39,7 @@ EXPORTS = ("tpc_mpc_default_params", "tpc_mpc_create", "tpc_mpc_destroy", "tpc_m
            "tpc_mpc_solve_batch_compact_sharded", "tpc_mpc_comm_test_mode",
            "tpc_mpc_solve_batch_general_sharded", "tpc_mpc_last_flags", "tpc_mpc_gather_shards",
            "tpc_mpc_shard_map", "tpc_mpc_solve_batch_compact_sharded_split", "tpc_mpc_gather_shards_split",
-           "tpc_mpc_solve_batch_general_backward")
+           "tpc_mpc_solve_batch_general_backward", "tpc_mpc_rollout_record", "tpc_mpc_rollout_backward")
 SPLIT_BLOCK, SPLIT_INTERLEAVED = 0, 1
 SPLITS = {"block": SPLIT_BLOCK, "interleaved": SPLIT_INTERLEAVED}
 
@@ -68,6 +68,15 @@ class GeneralGrad(C.Structure):
     _fields_ = [("controls", C.c_void_p), ("grad_controls", C.c_void_p), ("dA", C.c_void_p), ("dB", C.c_void_p),
                 ("dC", C.c_void_p), ("dQ", C.c_void_p), ("dR", C.c_void_p), ("dlower", C.c_void_p),
                 ("dupper", C.c_void_p), ("dx0", C.c_void_p), ("dtargets", C.c_void_p), ("kkt_residual", C.c_void_p)]
+
+
+class RolloutGrad(C.Structure):
+    """struct tpc_mpc_rollout_grad"""
+    _fields_ = [("sequences", C.c_void_p), ("states", C.c_void_p), ("grad_controls", C.c_void_p),
+                ("grad_states", C.c_void_p), ("dA", C.c_void_p), ("dB", C.c_void_p), ("dC", C.c_void_p),
+                ("dQ", C.c_void_p), ("dR", C.c_void_p), ("dlower", C.c_void_p), ("dupper", C.c_void_p),
+                ("dx0", C.c_void_p), ("dtargets", C.c_void_p), ("dnew_last_targets", C.c_void_p),
+                ("kkt_residual", C.c_void_p)]
 
 
 class Trajectories(C.Structure):
@@ -127,6 +136,10 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.tpc_mpc_solve_batch_general_sharded.argtypes = [vp, C.POINTER(Params), C.POINTER(GeneralIO), u32p, vp]
     lib.tpc_mpc_rollout.argtypes = [vp, C.POINTER(Params), C.POINTER(GeneralIO), C.c_int32, vp, vp, vp,
                                     vp, u32p, C.c_int, vp]
+    lib.tpc_mpc_rollout_record.argtypes = [vp, C.POINTER(Params), C.POINTER(GeneralIO), C.c_int32, vp, vp, vp,
+                                           vp, vp, u32p, C.c_int, vp]
+    lib.tpc_mpc_rollout_backward.argtypes = [vp, C.POINTER(Params), C.POINTER(GeneralIO), C.c_int32, vp,
+                                             C.POINTER(RolloutGrad), u32p, C.c_int, vp]
     lib.tpc_mpc_set_profiling.argtypes = [vp, C.c_int]
     lib.tpc_mpc_last_kernel_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                               C.POINTER(C.c_int)]

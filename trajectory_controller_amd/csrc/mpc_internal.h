@@ -116,6 +116,7 @@ struct RolloutStepArgs {
     void* states_out;             // [steps*2] or null (ld_out)
     const int32_t* iters_step;    // [n] or null
     int32_t* iters_out;           // [steps] or null (ld_out)
+    void* sequences_out;          // [steps*H*I] or null (ld_out): every step's solved sequence (tpc_mpc_rollout_record)
 };
 hipError_t launch_rollout_step(int dtype, const RolloutStepArgs& a, hipStream_t s);
 

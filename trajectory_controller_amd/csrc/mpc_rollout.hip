@@ -30,6 +30,11 @@ __global__ void rollout_step_kernel(RolloutStepArgs a) {
         ((T*)a.states_out)[((int64_t)a.step * 2 + 1) * lo + k] = n1;
     }
     if (a.iters_out && a.iters_step) a.iters_out[(int64_t)a.step * lo + k] = a.iters_step[k];
+    if (a.sequences_out) {   // the whole solved sequence U_step, before the next solve shifts it
+        const int64_t hi = (int64_t)a.H * a.I;
+        T* q = (T*)a.sequences_out + (int64_t)a.step * hi * lo + k;
+        for (int64_t c = 0; c < hi; ++c) q[c * lo] = u[c * ld];
+    }
     // operator()'s target shift (mpc.h:236-237), then the caller's set_last_target for the next call
     T* t = (T*)a.targets + k;
     for (int i = 1; i < a.H; ++i) {

@@ -45,6 +45,9 @@ TPC_DECL_H(10) TPC_DECL_H(20) TPC_DECL_H(30) TPC_DECL_H(40)
 int64_t grad_scratch_bytes(int I, int H, int64_t n);
 hipError_t grad_general(int I, int H, const grad::Args& a, void* ws, uint32_t* flags, hipStream_t s);
 uint32_t grad_general_host(int I, int H, const grad::Args& a);
+// ... and of the closed loop (mpc_rollout_grad.hip), on the same per-step workspace
+hipError_t rollout_grad(int I, int H, const grad::RollArgs& a, void* ws, uint32_t* flags, hipStream_t s);
+uint32_t rollout_grad_host(int I, int H, const grad::RollArgs& a);
 
 thread_local char g_create_error[kTpcErrLen] = "";
 }  // namespace tpc
@@ -1177,10 +1180,12 @@ int tpc_mpc_solve_batch_general_backward(tpc_mpc_handle h, const tpc_mpc_params*
     });
 }
 
-int tpc_mpc_rollout(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io,
-                    int32_t steps, const void* new_last_targets, void* controls_out,
-                    void* states_out, int32_t* iters_out, uint32_t* flags_out, int mem,
-                    void* stream) {
+namespace {
+
+// tpc_mpc_rollout, and tpc_mpc_rollout_record when sequences_out != NULL
+int rollout_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io, int32_t steps,
+                 const void* new_last_targets, void* controls_out, void* states_out, int32_t* iters_out,
+                 void* sequences_out, bool record, uint32_t* flags_out, int mem, void* stream) {
     return guarded(h, [&]() -> int {
         int rc = check_common(h, p);
         if (rc) return rc;
@@ -1191,6 +1196,7 @@ int tpc_mpc_rollout(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_gen
         if (!io->A || !io->B || !io->C || !io->Q || !io->R || !io->lower || !io->upper || !io->x0 ||
             !io->targets || !controls_out)
             return fail(h, TPC_MPC_ERR_BAD_ARG, "null batch pointer");
+        if (record && !sequences_out) return fail(h, TPC_MPC_ERR_BAD_ARG, "null sequences_out");
         HIP_TRY(h, hipSetDevice(h->device));
         hipStream_t s = (hipStream_t)stream;
         const int64_t es = (int64_t)esize(p->dtype);
@@ -1227,13 +1233,15 @@ int tpc_mpc_rollout(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_gen
         // HOST mode: new_last_targets in, and the three per-step outputs, go through the staging buffer
         const void* d_nlt = new_last_targets;
         int64_t ld_nlt = ld, ld_out = ld;
-        char *d_ctrl = (char*)controls_out, *d_states = (char*)states_out;
+        char *d_ctrl = (char*)controls_out, *d_states = (char*)states_out, *d_seq = (char*)sequences_out;
         int32_t* d_iters = iters_out;
         if (host) {
             const int64_t s_nlt = 0, s_ctrl = s_nlt + pad256((int64_t)steps * 2 * ldw * es);
             const int64_t s_states = s_ctrl + pad256((int64_t)steps * I * ldw * es);
             const int64_t s_iters = s_states + pad256((int64_t)steps * 2 * ldw * es);
-            rc = ensure(h, &h->stage, &h->stage_bytes, s_iters + pad256((int64_t)steps * ldw * 4));
+            const int64_t s_seq = s_iters + pad256((int64_t)steps * ldw * 4);
+            const int64_t s_end = s_seq + (sequences_out ? pad256((int64_t)steps * H * I * ldw * es) : 0);
+            rc = ensure(h, &h->stage, &h->stage_bytes, s_end);
             if (rc) return rc;
             char* b = (char*)h->stage;
             if (new_last_targets) {
@@ -1245,6 +1253,7 @@ int tpc_mpc_rollout(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_gen
             d_ctrl = b + s_ctrl;
             d_states = states_out ? b + s_states : nullptr;
             d_iters = iters_out ? (int32_t*)(b + s_iters) : nullptr;
+            d_seq = sequences_out ? b + s_seq : nullptr;
         }
 
         GeneralArgs a;
@@ -1262,7 +1271,7 @@ int tpc_mpc_rollout(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_gen
         r.A = a.A; r.B = a.B; r.C = a.C;
         r.x = w + off[7]; r.targets = w + off[8]; r.controls = w + off[9]; r.new_last_targets = d_nlt;
         r.controls_out = d_ctrl; r.states_out = d_states;
-        r.iters_step = a.iters; r.iters_out = d_iters;
+        r.iters_step = a.iters; r.iters_out = d_iters; r.sequences_out = d_seq;
 
         Workspace ws;
         rc = prepare_workspace(h, algo, H, p->dtype, n, &ws, 1);
@@ -1286,6 +1295,130 @@ int tpc_mpc_rollout(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_gen
                 HIP_TRY(h, copy_rows(states_out, ld * es, d_states, ldw * es, n * es, (int64_t)steps * 2, hipMemcpyDeviceToHost, s));
             if (iters_out)
                 HIP_TRY(h, copy_rows(iters_out, ld * 4, d_iters, ldw * 4, n * 4, steps, hipMemcpyDeviceToHost, s));
+            if (sequences_out)
+                HIP_TRY(h, copy_rows(sequences_out, ld * es, d_seq, ldw * es, n * es, (int64_t)steps * H * I,
+                                     hipMemcpyDeviceToHost, s));
+            HIP_TRY(h, hipStreamSynchronize(s));
+        }
+        rc = order.end();
+        if (rc) return rc;
+        return finish_flags(h, flags_out, s);
+    });
+}
+
+}  // namespace
+
+int tpc_mpc_rollout(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io,
+                    int32_t steps, const void* new_last_targets, void* controls_out,
+                    void* states_out, int32_t* iters_out, uint32_t* flags_out, int mem,
+                    void* stream) {
+    return rollout_impl(h, p, io, steps, new_last_targets, controls_out, states_out, iters_out, nullptr, false,
+                        flags_out, mem, stream);
+}
+
+int tpc_mpc_rollout_record(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io,
+                           int32_t steps, const void* new_last_targets, void* controls_out,
+                           void* states_out, int32_t* iters_out, void* sequences_out, uint32_t* flags_out,
+                           int mem, void* stream) {
+    return rollout_impl(h, p, io, steps, new_last_targets, controls_out, states_out, iters_out, sequences_out, true,
+                        flags_out, mem, stream);
+}
+
+int tpc_mpc_rollout_backward(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io, int32_t steps,
+                             const void* new_last_targets, const tpc_mpc_rollout_grad* g, uint32_t* flags_out,
+                             int mem, void* stream) {
+    return guarded(h, [&]() -> int {
+        int rc = check_common(h, p, true);
+        if (rc) return rc;
+        if (p->dtype != TPC_MPC_F64)
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "tpc_mpc_rollout_backward is fp64 only: p->dtype must be TPC_MPC_F64");
+        rc = check_general_io(h, io, mem);
+        if (rc) return rc;
+        if (!g) return fail(h, TPC_MPC_ERR_BAD_ARG, "null gradient struct");
+        if (steps < 0 || steps > (1 << 24)) return fail(h, TPC_MPC_ERR_BAD_ARG, "need 0 <= steps <= 2^24");
+        if (g->dnew_last_targets && !new_last_targets)
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "dnew_last_targets asked for without new_last_targets");
+        if (h->host_only && mem == TPC_MPC_DEVICE)
+            return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): the backward pass takes HOST memory only");
+        if (io->n == 0 || steps == 0) { if (flags_out) *flags_out = 0; return TPC_MPC_OK; }
+        if (!io->A || !io->B || !io->C || !io->Q || !io->R || !io->lower || !io->upper || !io->x0 || !io->targets)
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "null batch pointer");
+        if (!g->sequences || !g->states) return fail(h, TPC_MPC_ERR_BAD_ARG, "null sequences / states");
+        const int I = io->inputs, H = p->horizon;
+        const int64_t n = io->n, S = steps;
+        // the io's and g's arrays in order: 14 inputs (the optional ones may be null), then 11 outputs, with their
+        // component counts
+        const void* src[14] = {io->A, io->B, io->C, io->Q, io->R, io->lower, io->upper, io->x0, io->targets,
+                               new_last_targets, g->sequences, g->states, g->grad_controls, g->grad_states};
+        void* dst[11] = {g->dA, g->dB, g->dC, g->dQ, g->dR, g->dlower, g->dupper, g->dx0, g->dtargets,
+                         g->dnew_last_targets, g->kkt_residual};
+        const int64_t comps[25] = {4, 2 * I, 2, 2, I, I, I, 2, 2 * H, 2 * S, S * H * I, 2 * S, S * I, 2 * S,
+                                   4, 2 * I, 2, 2, I, I, I, 2, 2 * H, 2 * S, 1};
+        auto bind = [](grad::RollArgs* a, const void* const* in, void* const* out) {
+            a->A = (const double*)in[0]; a->B = (const double*)in[1]; a->C = (const double*)in[2];
+            a->Q = (const double*)in[3]; a->R = (const double*)in[4]; a->lo = (const double*)in[5];
+            a->hi = (const double*)in[6]; a->x0 = (const double*)in[7]; a->targets = (const double*)in[8];
+            a->nlt = (const double*)in[9]; a->seq = (const double*)in[10]; a->states = (const double*)in[11];
+            a->gu = (const double*)in[12]; a->gx = (const double*)in[13];
+            a->dA = (double*)out[0]; a->dB = (double*)out[1]; a->dC = (double*)out[2]; a->dQ = (double*)out[3];
+            a->dR = (double*)out[4]; a->dlo = (double*)out[5]; a->dhi = (double*)out[6]; a->dx0 = (double*)out[7];
+            a->dtargets = (double*)out[8]; a->dnlt = (double*)out[9]; a->kkt = (double*)out[10];
+        };
+        grad::RollArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.n = n;
+        a.steps = steps;
+        if (h->host_only) {   // on the calling thread, straight from and into the caller's arrays
+            a.ld = io->ld;
+            bind(&a, src, dst);
+            const uint32_t f = rollout_grad_host(I, H, a);
+            if (flags_out) *flags_out = f;
+            return TPC_MPC_OK;
+        }
+        HIP_TRY(h, hipSetDevice(h->device));
+        hipStream_t s = (hipStream_t)stream;
+        StreamOrderScope order(h, s);
+        rc = order.begin();
+        if (rc) return rc;
+        rc = ensure(h, &h->grad_ws, &h->grad_ws_bytes, pad256(grad_scratch_bytes(I, H, n)));
+        if (rc) return rc;
+        const int64_t lds = (n + 63) / 64 * 64;
+        int64_t off[25] = {0};
+        if (mem == TPC_MPC_DEVICE) {
+            a.ld = io->ld;
+            bind(&a, src, dst);
+        } else {
+            // HOST arrays: every component row copied on its own (n elements, never ld), as tpc_mpc_solve_batch_general;
+            // only the arrays given are staged
+            int64_t total = 0;
+            for (int c = 0; c < 25; ++c) {
+                const bool given = c < 14 ? src[c] != nullptr : dst[c - 14] != nullptr;
+                off[c] = total;
+                if (given) total += pad256(comps[c] * lds * 8);
+            }
+            rc = ensure(h, &h->stage, &h->stage_bytes, total);
+            if (rc) return rc;
+            char* b = (char*)h->stage;
+            const void* sin[14];
+            void* sout[11];
+            for (int c = 0; c < 14; ++c) {
+                sin[c] = src[c] ? b + off[c] : nullptr;
+                if (src[c])
+                    HIP_TRY(h, copy_rows(b + off[c], lds * 8, src[c], io->ld * 8, n * 8, comps[c], hipMemcpyHostToDevice, s));
+            }
+            for (int c = 0; c < 11; ++c) sout[c] = dst[c] ? b + off[14 + c] : nullptr;
+            a.ld = lds;
+            bind(&a, sin, sout);
+        }
+        HIP_TRY(h, hipMemsetAsync(h->ws_words + 1, 0, sizeof(uint32_t), s));
+        hipError_t e = rollout_grad(I, H, a, h->grad_ws, h->ws_words + 1, s);
+        if (e != hipSuccess) return hip_fail(h, e, "kernel launch");
+        if (mem == TPC_MPC_HOST) {
+            const char* b = (const char*)h->stage;
+            for (int c = 0; c < 11; ++c)
+                if (dst[c])
+                    HIP_TRY(h, copy_rows(dst[c], io->ld * 8, b + off[14 + c], lds * 8, n * 8, comps[14 + c],
+                                         hipMemcpyDeviceToHost, s));
             HIP_TRY(h, hipStreamSynchronize(s));
         }
         rc = order.end();

@@ -485,6 +485,23 @@ class MpcSolver:
         (mpc.h:229-239) and the plant update of dlib/test/mpc.cpp:314 between them.  SoA arrays as
         in solve_batch_general; new_last_targets [2*steps, n].  Returns (controls[steps*I, n],
         states[steps*2, n] | None, iters[steps, n] | None)."""
+        c_out, s_out, i_out, _ = self._rollout(False, steps, A, B, Cc, Q, R, lower, upper, x0, targets,
+                                               new_last_targets, controls, v_state, inputs, want_states, want_iters,
+                                               **over)
+        return c_out, s_out, i_out
+
+    def rollout_record(self, steps: int, A, B, Cc, Q, R, lower, upper, x0, targets, new_last_targets=None,
+                       controls=None, v_state=None, inputs: Optional[int] = None, want_iters: bool = False, **over):
+        """rollout that also records every step's solved sequence (tpc_mpc_rollout_record), what rollout_backward
+        differentiates at.  Returns (controls[steps*I, n], states[steps*2, n], sequences[steps*H*I, n],
+        iters[steps, n] | None); the first two and iters are rollout's, bit for bit."""
+        c_out, s_out, i_out, q_out = self._rollout(True, steps, A, B, Cc, Q, R, lower, upper, x0, targets,
+                                                   new_last_targets, controls, v_state, inputs, True, want_iters,
+                                                   **over)
+        return c_out, s_out, q_out, i_out
+
+    def _rollout(self, record, steps, A, B, Cc, Q, R, lower, upper, x0, targets, new_last_targets, controls, v_state,
+                 inputs, want_states, want_iters, **over):
         p = self._params(**over)
         H = p.horizon
         if _is_torch(A):
@@ -502,6 +519,7 @@ class MpcSolver:
             c_out = torch.empty((steps * I, n), dtype=tdt, device=A.device)
             s_out = torch.empty((steps * 2, n), dtype=tdt, device=A.device) if want_states else None
             i_out = torch.empty((steps, n), dtype=torch.int32, device=A.device) if want_iters else None
+            q_out = torch.empty((steps * H * I, n), dtype=tdt, device=A.device) if record else None
             stream = C.c_void_p(torch.cuda.current_stream(A.device).cuda_stream)
             mem = capi.DEVICE
             optr = lambda t: None if t is None else t.data_ptr()
@@ -526,6 +544,7 @@ class MpcSolver:
             c_out = np.empty((steps * I, n), dtype=dt)
             s_out = np.empty((steps * 2, n), dtype=dt) if want_states else None
             i_out = np.empty((steps, n), dtype=np.int32) if want_iters else None
+            q_out = np.empty((steps * H * I, n), dtype=dt) if record else None
             stream = None
             mem = capi.HOST
             optr = lambda a: None if a is None else a.ctypes.data
@@ -534,11 +553,96 @@ class MpcSolver:
                             targets=ptr(targets, 2 * H), controls_inout=ptr(controls, H * I),
                             v_inout=ptr(v_state, H * I), u0=None, iters=None)
         flags = C.c_uint32(0)
-        self._check(self._lib.tpc_mpc_rollout(self._h, C.byref(p), C.byref(io), int(steps),
-                                              ptr(new_last_targets, 2 * steps), optr(c_out), optr(s_out),
-                                              optr(i_out), C.byref(flags), mem, stream))
+        if record:
+            self._check(self._lib.tpc_mpc_rollout_record(self._h, C.byref(p), C.byref(io), int(steps),
+                                                         ptr(new_last_targets, 2 * steps), optr(c_out), optr(s_out),
+                                                         optr(i_out), optr(q_out), C.byref(flags), mem, stream))
+        else:
+            self._check(self._lib.tpc_mpc_rollout(self._h, C.byref(p), C.byref(io), int(steps),
+                                                  ptr(new_last_targets, 2 * steps), optr(c_out), optr(s_out),
+                                                  optr(i_out), C.byref(flags), mem, stream))
         self.last_flags = flags.value
-        return c_out, s_out, i_out
+        return c_out, s_out, i_out, q_out
+
+    ROLLOUT_GRAD_NAMES = GRAD_NAMES[:-1] + ("new_last_targets", "kkt_residual")
+
+    def rollout_backward(self, steps: int, A, B, Cc, Q, R, lower, upper, x0, targets, new_last_targets=None, *,
+                         sequences, states, grad_controls=None, grad_states=None, inputs: Optional[int] = None,
+                         want=None, want_flags: bool = True, **over):
+        """Backward pass of rollout (tpc_mpc_rollout_backward), fp64 only: the gradient of a loss of the rollout's
+        controls and states, taken at what rollout_record returned (`sequences` [steps*H*I, n], `states`
+        [steps*2, n]).  grad_controls [steps*I, n] / grad_states [steps*2, n] are dL/d(controls) / dL/d(states)
+        (None: zero).  Arrays as in rollout (numpy: HOST memory, CUDA torch tensors: DEVICE memory on the current
+        stream).  Returns a dict keyed "A", "B", "C", "Q", "R", "lower", "upper", "x0", "targets",
+        "new_last_targets" (only when new_last_targets is given) and "kkt_residual" [n] (max over the steps); `want`
+        names the outputs to compute.  Flagged instances get zeros (last_flags; want_flags=False leaves it at 0 and
+        keeps a DEVICE call asynchronous)."""
+        p = self._params(**over)
+        H = p.horizon
+        if want is None:
+            want = tuple(k for k in self.ROLLOUT_GRAD_NAMES if k != "new_last_targets" or new_last_targets is not None)
+        unknown = set(want) - set(self.ROLLOUT_GRAD_NAMES)
+        if unknown:
+            raise ValueError(f"unknown gradient names {sorted(unknown)}")
+        if _is_torch(A):
+            import torch
+            n = A.shape[-1]
+            I = inputs or R.shape[0]
+
+            def ptr(t, rows):
+                if t is None:
+                    return None
+                if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == (rows, n)):
+                    raise ValueError(f"expected contiguous fp64 CUDA tensor [{rows},{n}]")
+                return t.data_ptr()
+
+            def new(rows):
+                return torch.empty((rows, n), dtype=torch.float64, device=A.device)
+            stream = C.c_void_p(torch.cuda.current_stream(A.device).cuda_stream)
+            mem = capi.DEVICE
+        else:
+            A = np.ascontiguousarray(A, dtype=np.float64)
+            n = A.shape[-1]
+            I = inputs or np.asarray(R).shape[0]
+            keep = []
+
+            def ptr(a, rows):
+                if a is None:
+                    return None
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.shape != (rows, n):
+                    raise ValueError(f"expected an array [{rows},{n}]")
+                keep.append(a)
+                return a.ctypes.data
+
+            def new(rows):
+                return np.empty((rows, n), dtype=np.float64)
+            stream = None
+            mem = capi.HOST
+        rows = {"A": 4, "B": 2 * I, "C": 2, "Q": 2, "R": I, "lower": I, "upper": I, "x0": 2, "targets": 2 * H,
+                "new_last_targets": 2 * steps, "kkt_residual": 1}
+        out = {k: new(rows[k]) for k in want}
+
+        def optr(k):
+            if k not in out:
+                return None
+            return out[k].data_ptr() if mem == capi.DEVICE else out[k].ctypes.data
+        io = capi.GeneralIO(inputs=I, n=n, ld=n, A=ptr(A, 4), B=ptr(B, 2 * I), C=ptr(Cc, 2), Q=ptr(Q, 2),
+                            R=ptr(R, I), lower=ptr(lower, I), upper=ptr(upper, I), x0=ptr(x0, 2),
+                            targets=ptr(targets, 2 * H), controls_inout=None, v_inout=None, u0=None, iters=None)
+        g = capi.RolloutGrad(sequences=ptr(sequences, steps * H * I), states=ptr(states, 2 * steps),
+                             grad_controls=ptr(grad_controls, steps * I), grad_states=ptr(grad_states, 2 * steps),
+                             dA=optr("A"), dB=optr("B"), dC=optr("C"), dQ=optr("Q"), dR=optr("R"),
+                             dlower=optr("lower"), dupper=optr("upper"), dx0=optr("x0"), dtargets=optr("targets"),
+                             dnew_last_targets=optr("new_last_targets"), kkt_residual=optr("kkt_residual"))
+        flags = C.c_uint32(0)
+        self._check(self._lib.tpc_mpc_rollout_backward(self._h, C.byref(p), C.byref(io), int(steps),
+                                                       ptr(new_last_targets, 2 * steps), C.byref(g),
+                                                       C.byref(flags) if want_flags else None, mem, stream))
+        self.last_flags = flags.value
+        if "kkt_residual" in out:
+            out["kkt_residual"] = out["kkt_residual"].reshape(n)
+        return out
 
     def follow_batch(self, pos_x, pos_y, dir_x, dir_y, velocity, count, car_velocity, look_ahead,
                      lookup=None, want_iters: bool = False, **over):
