@@ -33,7 +33,7 @@ extern "C" {
 #endif
 
 #define TPC_MPC_ABI_VERSION 5   /* 5 = 4 + new symbols only (the split-named sharded entries; later additions, such as
-                                   tpc_mpc_solve_batch_general_backward and tpc_mpc_rollout_record / _backward,
+                                   tpc_mpc_solve_batch_general_backward, tpc_mpc_rollout_record / _backward and tpc_mpc_polish_batch_general,
                                    are new symbols and structs only and keep 5);
                                    4 broke 3: tpc_mpc_params.reserved became .options and must be zero-initialised */
 
@@ -324,6 +324,53 @@ typedef struct tpc_mpc_general_grad {
 int tpc_mpc_solve_batch_general_backward(tpc_mpc_handle h, const tpc_mpc_params* p,
                                          const tpc_mpc_general_io* io, const tpc_mpc_general_grad* g,
                                          uint32_t* flags_out, int mem, void* stream);
+
+/* Parameters and per-instance outputs of tpc_mpc_polish_batch_general:
+ *   tol           the residual a polished sequence must reach: dlib's eps (the same quantity, see below); > 0
+ *   max_rounds    Newton rounds allowed per instance; >= 0 (0 only verifies)
+ *   status        optional, int32 [n]: the rounds the instance used (0 = it already passed), or -1 = not polished
+ *   residual_in   optional, fp64 [n]: res of the clamped input sequence
+ *   residual_out  optional, fp64 [n]: res of the returned sequence (= residual_in for status -1) */
+typedef struct tpc_mpc_polish {
+    double tol;
+    int32_t max_rounds;
+    int32_t reserved;
+    int32_t* status;
+    void *residual_in, *residual_out;
+} tpc_mpc_polish;
+
+/* No reference counterpart.  Polish: moves a control sequence of dlib's box QP -- typically what
+ * tpc_mpc_solve_batch_general left in controls_inout at dlib's default eps -- onto the exact minimiser whenever that
+ * can be reached and VERIFIED in a few Newton rounds, and leaves it as it was otherwise.
+ *   Definition.  With dlib's df = H u + MM (mpc.h:255-283) and its mask (mpc.h:298-299): component (t, j) is BLOCKED
+ *   iff (u <= lower_j && df > 0) || (u >= upper_j && df < 0), or lower_j == upper_j; F is the rest.
+ *   res(u) = max |df| over F (0 when F is empty) -- the quantity dlib's stop test compares with eps.
+ *     u <- clamp(u, lower, upper)
+ *     for round = 0 .. max_rounds:
+ *         df, F, res from u
+ *         if res <= tol: status = round; return u
+ *         if round == max_rounds: break
+ *         safeguard: if the previous round was a regular one and res did not fall below its res, this round is an
+ *                    INNER round: the components on a bound leave F (they stay on the bound); the round after an
+ *                    inner round is regular again
+ *         w = H_FF^-1 df_F  (w = 0 off F);  u_F <- clamp(u_F - w_F, lower, upper)
+ *     status = -1; the caller's sequence is returned bit for bit
+ *   H is positive definite (R > 0), so a u with res(u) <= tol under this mask is a KKT point of the convex QP to that
+ *   tolerance: the acceptance test is the proof, whatever path led there.
+ *   Method.  df by dlib's two recurrences, w by the masked Riccati sweep of the backward pass
+ *   (csrc/mpc_polish_model.h on csrc/mpc_grad_model.h): O(H) per round, one lane per instance, every round in one launch.
+ * io: as for tpc_mpc_solve_batch_general.  controls_inout is required: in = the sequence to polish (NOT shifted), out =
+ * the result; u0 (optional here) receives row 0 of the result; v_inout and iters are ignored.  p: as for the solve;
+ * used are the horizon (1..64) and the dtype, which must be TPC_MPC_F64 (TPC_MPC_ERR_BAD_ARG otherwise); one or two
+ * inputs.  q->tol <= 0 (or NaN) or q->max_rounds < 0: TPC_MPC_ERR_BAD_ARG.
+ * An instance with NaN / Inf data or sequence (TPC_MPC_FLAG_NONFINITE; bounds may be infinite) or a model that breaks
+ * dlib's requires clause (TPC_MPC_FLAG_BAD_MODEL) is not touched: status -1, residuals 0.  Any other instance that
+ * returns -1 raises TPC_MPC_FLAG_NOT_POLISHED.  Memory, stream, flags and the host-only handle as
+ * tpc_mpc_solve_batch_general_backward (HOST arrays are staged; a host-only handle runs HOST batches on the calling
+ * thread with the kernel's bits). */
+#define TPC_MPC_FLAG_NOT_POLISHED 0x8u
+int tpc_mpc_polish_batch_general(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io,
+                                 const tpc_mpc_polish* q, uint32_t* flags_out, int mem, void* stream);
 
 /* Closed loop on device: `steps` successive operator() calls per controller with warm start and
  * target shift (mpc.h:229-239), plant update x <- A x + B u + C between calls (the loop of

@@ -4,8 +4,9 @@ and over the closed loop: `mpc_rollout` (forward MpcSolver.rollout_record, backw
 Forward is MpcSolver.solve_batch_general from a fresh controller (zero controls); backward is
 tpc_mpc_solve_batch_general_backward on torch's current stream (include/tpc_mpc.h gives the definition of the
 derivative: the active set is read off the returned controls, the free components are differentiated through the
-stationarity condition on that set).  The gradient is that of the optimum when the controls are the optimum: pass a
-small eps (e.g. eps=1e-10) for accurate gradients -- dlib's default 0.01 leaves a loose solution.  Inputs are CUDA fp64
+stationarity condition on that set).  The gradient is that of the optimum when the controls are the optimum: dlib's
+default eps 0.01 leaves a loose solution, so either pass polish=True (solve at eps 0.01, then a Newton round or two of
+tpc_mpc_polish_batch_general onto the verified optimum -- the cheap way) or a small eps (e.g. eps=1e-10).  Inputs are CUDA fp64
 tensors; both functions are once-differentiable.  Instances whose data are non-finite or break dlib's requires clause
 get zero gradients.
 """
@@ -21,12 +22,16 @@ _ALPHA_MAX = 22.0 * math.pi / 180.0   # the reference module's steering bounds
 
 class _MpcGeneral(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, solver, over, A, B, Cc, Q, R, lower, upper, x0, targets):
+    def forward(ctx, solver, over, polish, A, B, Cc, Q, R, lower, upper, x0, targets):
         I = R.shape[0]
         H = solver._params(**over).horizon
         ins = [t.detach().contiguous() for t in (A, B, Cc, Q, R, lower, upper, x0, targets)]
         controls = torch.zeros((H * I, A.shape[-1]), dtype=torch.float64, device=A.device)
         solver.solve_batch_general(*ins, controls=controls, inputs=I, **over)   # zeros shifted are zeros: a cold start
+        if polish:   # onto the verified optimum where it is reached; the others keep the solver's sequence
+            tol, rounds = (1e-9, 8) if polish is True else polish
+            keys = {k: v for k, v in over.items() if k == "horizon"}
+            solver.polish_batch_general(*ins, controls, tol=tol, max_rounds=rounds, want_status=False, inputs=I, **keys)
         ctx.solver, ctx.over, ctx.I = solver, over, I
         ctx.save_for_backward(*ins, controls)
         return controls
@@ -36,23 +41,25 @@ class _MpcGeneral(torch.autograd.Function):
     def backward(ctx, grad_controls):
         *ins, controls = ctx.saved_tensors
         names = ("A", "B", "C", "Q", "R", "lower", "upper", "x0", "targets")
-        want = tuple(k for k, need in zip(names, ctx.needs_input_grad[2:]) if need)
+        want = tuple(k for k, need in zip(names, ctx.needs_input_grad[3:]) if need)
         if not want:
-            return (None,) * 11
+            return (None,) * 12
         g = ctx.solver.solve_batch_general_backward(*ins, controls, grad_controls.contiguous(), inputs=ctx.I,
                                                     want=want, want_flags=False, **ctx.over)
-        return (None, None) + tuple(g.get(k) for k in names)
+        return (None, None, None) + tuple(g.get(k) for k in names)
 
 
-def mpc_general(solver, A, B, Cc, Q, R, lower, upper, x0, targets, **over):
+def mpc_general(solver, A, B, Cc, Q, R, lower, upper, x0, targets, polish=False, **over):
     """The solved control sequence [H*I, n] of n fresh dlib::mpc<2,I,H> controllers (rows 0..I-1 are u0), as a
     differentiable function of the component-major CUDA fp64 tensors A[4,n] B[2I,n] C[2,n] Q[2,n] R[I,n] lower[I,n]
     upper[I,n] x0[2,n] targets[2H,n] (solve_batch_general's layout).  `over` overrides the solver's parameters
-    (horizon, eps, max_iter, algo, ...)."""
+    (horizon, eps, max_iter, algo, ...).  polish=True (or a (tol, max_rounds) pair; True is (1e-9, 8)) runs
+    MpcSolver.polish_batch_general on the solved sequence before it is returned and saved, so a solve at dlib's eps
+    0.01 is differentiated at the optimum; an instance the polish cannot verify keeps the solver's sequence."""
     for t in (A, B, Cc, Q, R, lower, upper, x0, targets):
         if not (t.is_cuda and t.dtype == torch.float64):
             raise ValueError("mpc_general takes CUDA fp64 tensors")
-    return _MpcGeneral.apply(solver, over, A, B, Cc, Q, R, lower, upper, x0, targets)
+    return _MpcGeneral.apply(solver, over, polish, A, B, Cc, Q, R, lower, upper, x0, targets)
 
 
 class _MpcRollout(torch.autograd.Function):
@@ -99,7 +106,7 @@ def mpc_rollout(solver, steps, A, B, Cc, Q, R, lower, upper, x0, targets, new_la
 
 
 def mpc_compact(solver, v, delta_y, delta_phi, weights, step_size=0.1, wheelbase=0.21,
-                lower=(-_ALPHA_MAX, -_ALPHA_MAX), upper=(_ALPHA_MAX, _ALPHA_MAX), **over):
+                lower=(-_ALPHA_MAX, -_ALPHA_MAX), upper=(_ALPHA_MAX, _ALPHA_MAX), polish=False, **over):
     """mpcControllerTobi for n instances as a differentiable function: returns (front, rear), each [n].
 
     The model is built with torch ops from the reference controller's (src/trajectory_point_follower.cpp:326-371):
@@ -107,7 +114,7 @@ def mpc_compact(solver, v, delta_y, delta_phi, weights, step_size=0.1, wheelbase
     weight_steering_rear), one target (delta_y, delta_phi) for every step -- and solved by mpc_general, so gradients
     reach v, delta_y, delta_phi, the four weights (a tensor [4] or [4, n]), T, l and the bounds by the chain rule.
     The forward runs the general-form kernels, not solve_batch_compact's family: the controls agree with
-    solve_batch_compact to the solvers' tolerance, not bit for bit."""
+    solve_batch_compact to the solvers' tolerance, not bit for bit.  polish: as in mpc_general."""
     dev, n = v.device, v.shape[-1]
     f64 = dict(dtype=torch.float64, device=dev)
     H = solver._params(**over).horizon
@@ -125,5 +132,5 @@ def mpc_compact(solver, v, delta_y, delta_phi, weights, step_size=0.1, wheelbase
     w = rows(weights, 4)
     targets = torch.stack([delta_y, delta_phi]).repeat(H, 1)
     u = mpc_general(solver, A, B, torch.zeros(2, n, **f64), w[0:2], w[2:4], rows(lower, 2), rows(upper, 2),
-                    torch.zeros(2, n, **f64), targets, **over)
+                    torch.zeros(2, n, **f64), targets, polish=polish, **over)
     return u[0], u[1]

@@ -19,7 +19,7 @@ HOST, DEVICE = 0, 1
 ALGO_AUTO, ALGO_WAVE, ALGO_LANE, ALGO_LANE_FMA, ALGO_GROUP = 0, 1, 2, 3, 4
 OPT_WAVE_GROUP, OPT_MAILBOX_HOST, OPT_GROUP_LANES, OPT_HOST_SOLVE_ONE = 1, 2, 3, 4
 DEVICE_NONE = -1   # tpc_mpc_create: a host-only handle
-FLAG_NONFINITE, FLAG_MAX_ITER, FLAG_BAD_MODEL = 0x1, 0x2, 0x4
+FLAG_NONFINITE, FLAG_MAX_ITER, FLAG_BAD_MODEL, FLAG_NOT_POLISHED = 0x1, 0x2, 0x4, 0x8
 PARAM_FAST_CAPPED = 0x1   # tpc_mpc_params.options
 
 STATUS_NAMES = {0: "OK", 1: "BAD_ARG", 2: "BAD_WEIGHTS", 3: "BAD_BOUNDS", 4: "BAD_HORIZON",
@@ -39,7 +39,8 @@ EXPORTS = ("tpc_mpc_default_params", "tpc_mpc_create", "tpc_mpc_destroy", "tpc_m
            "tpc_mpc_solve_batch_compact_sharded", "tpc_mpc_comm_test_mode",
            "tpc_mpc_solve_batch_general_sharded", "tpc_mpc_last_flags", "tpc_mpc_gather_shards",
            "tpc_mpc_shard_map", "tpc_mpc_solve_batch_compact_sharded_split", "tpc_mpc_gather_shards_split",
-           "tpc_mpc_solve_batch_general_backward", "tpc_mpc_rollout_record", "tpc_mpc_rollout_backward")
+           "tpc_mpc_solve_batch_general_backward", "tpc_mpc_rollout_record", "tpc_mpc_rollout_backward",
+           "tpc_mpc_polish_batch_general")
 SPLIT_BLOCK, SPLIT_INTERLEAVED = 0, 1
 SPLITS = {"block": SPLIT_BLOCK, "interleaved": SPLIT_INTERLEAVED}
 
@@ -68,6 +69,12 @@ class GeneralGrad(C.Structure):
     _fields_ = [("controls", C.c_void_p), ("grad_controls", C.c_void_p), ("dA", C.c_void_p), ("dB", C.c_void_p),
                 ("dC", C.c_void_p), ("dQ", C.c_void_p), ("dR", C.c_void_p), ("dlower", C.c_void_p),
                 ("dupper", C.c_void_p), ("dx0", C.c_void_p), ("dtargets", C.c_void_p), ("kkt_residual", C.c_void_p)]
+
+
+class Polish(C.Structure):
+    """struct tpc_mpc_polish"""
+    _fields_ = [("tol", C.c_double), ("max_rounds", C.c_int32), ("reserved", C.c_int32), ("status", C.c_void_p),
+                ("residual_in", C.c_void_p), ("residual_out", C.c_void_p)]
 
 
 class RolloutGrad(C.Structure):
@@ -133,6 +140,8 @@ def load_library(path: str | None = None) -> C.CDLL:
                                                 C.c_int, vp]
     lib.tpc_mpc_solve_batch_general_backward.argtypes = [vp, C.POINTER(Params), C.POINTER(GeneralIO),
                                                          C.POINTER(GeneralGrad), u32p, C.c_int, vp]
+    lib.tpc_mpc_polish_batch_general.argtypes = [vp, C.POINTER(Params), C.POINTER(GeneralIO), C.POINTER(Polish), u32p,
+                                                 C.c_int, vp]
     lib.tpc_mpc_solve_batch_general_sharded.argtypes = [vp, C.POINTER(Params), C.POINTER(GeneralIO), u32p, vp]
     lib.tpc_mpc_rollout.argtypes = [vp, C.POINTER(Params), C.POINTER(GeneralIO), C.c_int32, vp, vp, vp,
                                     vp, u32p, C.c_int, vp]

@@ -103,15 +103,16 @@ struct Sums {
     double kkt = 0.0;
 };
 
-// The derivative of one solve from state (xs0, xs1): u(t, j), g(t, j) and tg(t, c) read the controls, dL/du and the
-// targets; dtg(t, v0, v1) receives dL/dtarget_t.  Adds the gradients to s, raises s.kkt to the step's residual, and
-// returns dL/dx0 in (dx00, dx01).  Returns false if a control, a dL/du or a target read is not finite.
-template <int I, class U, class G, class TG, class DTG>
-TPC_GRAD_HD bool qp_step(const Model& m, int H, double xs0, double xs1, U u_at, G g_at, TG tg_at, DTG dtg, double* ws,
-                         int64_t wn, Sums& s, double& dx00, double& dx01) {
+// Passes 1 and 2 of the header comment for one QP: w = H_FF^-1 g_F (w = 0 off F) by the masked Riccati sweep, F given
+// by free_at(j, u, g) on the values u(t, j), g(t, j) that u_at and g_at read.  Pass 1 reads step t's u and g before it
+// writes step t's slots, so g may live in the feed-forward's slot (2 I + j, t).  Leaves x_t, dx_t, w_t in the step's slots
+// and x_H, dx_H in (x0, x1, d0, d1); clears fin if a u or g read is not finite.  Shared by qp_step() and by
+// polish_instance() (mpc_polish_model.h).
+template <int I, class U, class G, class FR>
+TPC_GRAD_HD void riccati_passes(const Model& m, int H, double xs0, double xs1, U u_at, G g_at, FR free_at, double* ws,
+                                int64_t wn, bool& fin, double& x0, double& x1, double& d0, double& d1) {
     auto slot = [&](int q, int t) -> double& { return ws[((int64_t)q * H + t) * wn]; };
     const double a00 = m.a00, a01 = m.a01, a10 = m.a10, a11 = m.a11, c0 = m.c0, c1 = m.c1, q0 = m.q0, q1 = m.q1;
-    bool fin = true;
 
     // ---- 1. masked Riccati sweep, t = H-1 .. 0.  V_{t+1}(dx) = 1/2 dx' P dx + s' dx, P = s = 0 at t + 1 = H.
     double p00 = 0.0, p01 = 0.0, p11 = 0.0, s0 = 0.0, s1 = 0.0;
@@ -123,7 +124,7 @@ TPC_GRAD_HD bool qp_step(const Model& m, int H, double xs0, double xs1, U u_at, 
             u[j] = u_at(t, j);
             g[j] = g_at(t, j);
             fin = fin && gfinite(u[j]) && gfinite(g[j]);
-            fr[j] = !(u[j] <= m.lo[j] || u[j] >= m.hi[j]);
+            fr[j] = free_at(j, u[j], g[j]);
         }
         // S = Q + P (symmetric), SA = S A, SB = S B
         const double S00 = q0 + p00, S01 = p01, S11 = q1 + p11;
@@ -180,7 +181,7 @@ TPC_GRAD_HD bool qp_step(const Model& m, int H, double xs0, double xs1, U u_at, 
     }
 
     // ---- 2. forward: x_t, dx_t, w_t -> the step's slots (0, 1: x; 2, 3: dx; 4..: w)
-    double x0 = xs0, x1 = xs1, d0 = 0.0, d1 = 0.0;
+    x0 = xs0; x1 = xs1; d0 = 0.0; d1 = 0.0;
     for (int t = 0; t < H; ++t) {
         double w[2], u[2];
 #pragma unroll
@@ -202,6 +203,23 @@ TPC_GRAD_HD bool qp_step(const Model& m, int H, double xs0, double xs1, U u_at, 
         }
         x0 = y0; x1 = y1; d0 = e0; d1 = e1;
     }
+}
+
+// The derivative of one solve from state (xs0, xs1): u(t, j), g(t, j) and tg(t, c) read the controls, dL/du and the
+// targets; dtg(t, v0, v1) receives dL/dtarget_t.  Adds the gradients to s, raises s.kkt to the step's residual, and
+// returns dL/dx0 in (dx00, dx01).  Returns false if a control, a dL/du or a target read is not finite.
+template <int I, class U, class G, class TG, class DTG>
+TPC_GRAD_HD bool qp_step(const Model& m, int H, double xs0, double xs1, U u_at, G g_at, TG tg_at, DTG dtg, double* ws,
+                         int64_t wn, Sums& s, double& dx00, double& dx01) {
+    auto slot = [&](int q, int t) -> double& { return ws[((int64_t)q * H + t) * wn]; };
+    const double a00 = m.a00, a01 = m.a01, a10 = m.a10, a11 = m.a11, q0 = m.q0, q1 = m.q1;
+    bool fin = true;
+
+    // ---- 1, 2. the Riccati sweep and the forward pass, F = the components strictly inside the box
+    double x0, x1, d0, d1;
+    riccati_passes<I>(
+        m, H, xs0, xs1, u_at, g_at, [&](int j, double u, double) { return !(u <= m.lo[j] || u >= m.hi[j]); }, ws, wn,
+        fin, x0, x1, d0, d1);
 
     // ---- 3. backward: costates and gradients.  (x0, x1, d0, d1) hold x_{t+1}, dx_{t+1} on entry to step t.
     double P0 = 0.0, P1 = 0.0, D0 = 0.0, D1 = 0.0;   // p_{t+1}, dp_{t+1}

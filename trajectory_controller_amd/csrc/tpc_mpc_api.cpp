@@ -7,6 +7,7 @@
 #include "tpc_mpc_experimental.h"
 #include "auto_table.h"
 #include "mpc_grad_model.h"
+#include "mpc_polish_model.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -48,6 +49,10 @@ uint32_t grad_general_host(int I, int H, const grad::Args& a);
 // ... and of the closed loop (mpc_rollout_grad.hip), on the same per-step workspace
 hipError_t rollout_grad(int I, int H, const grad::RollArgs& a, void* ws, uint32_t* flags, hipStream_t s);
 uint32_t rollout_grad_host(int I, int H, const grad::RollArgs& a);
+// the polish of the general form (mpc_polish.hip), on the gradient workspace grown by the working copy of u
+int64_t polish_scratch_bytes(int I, int H, int64_t n);
+hipError_t polish_general(int I, int H, const polish::Args& a, void* ws, uint32_t* flags, hipStream_t s);
+uint32_t polish_general_host(int I, int H, const polish::Args& a);
 
 thread_local char g_create_error[kTpcErrLen] = "";
 }  // namespace tpc
@@ -1172,6 +1177,100 @@ int tpc_mpc_solve_batch_general_backward(tpc_mpc_handle h, const tpc_mpc_params*
                 if (dst[c])
                     HIP_TRY(h, copy_rows(dst[c], io->ld * 8, b + off[11 + c], lds * 8, n * 8, comps[11 + c],
                                          hipMemcpyDeviceToHost, s));
+            HIP_TRY(h, hipStreamSynchronize(s));
+        }
+        rc = order.end();
+        if (rc) return rc;
+        return finish_flags(h, flags_out, s);
+    });
+}
+
+int tpc_mpc_polish_batch_general(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io,
+                                 const tpc_mpc_polish* q, uint32_t* flags_out, int mem, void* stream) {
+    return guarded(h, [&]() -> int {
+        int rc = check_common(h, p, true);
+        if (rc) return rc;
+        if (p->dtype != TPC_MPC_F64)
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "tpc_mpc_polish_batch_general is fp64 only: p->dtype must be TPC_MPC_F64");
+        rc = check_general_io(h, io, mem);
+        if (rc) return rc;
+        if (!q) return fail(h, TPC_MPC_ERR_BAD_ARG, "null polish struct");
+        if (!(q->tol > 0.0) || q->max_rounds < 0)
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "polish needs tol > 0 and max_rounds >= 0");
+        if (h->host_only && mem == TPC_MPC_DEVICE)
+            return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): the polish takes HOST memory only");
+        if (io->n == 0) { if (flags_out) *flags_out = 0; return TPC_MPC_OK; }
+        if (!io->A || !io->B || !io->C || !io->Q || !io->R || !io->lower || !io->upper || !io->x0 || !io->targets)
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "null batch pointer");
+        if (!io->controls_inout) return fail(h, TPC_MPC_ERR_BAD_ARG, "null controls_inout: the sequence to polish");
+        const int I = io->inputs, H = p->horizon;
+        const int64_t n = io->n;
+        // the arrays in order: 10 inputs (controls_inout is also the first output), then u0, the residuals (fp64) and
+        // the status (int32), with their component counts
+        const void* src[10] = {io->A, io->B, io->C, io->Q, io->R, io->lower, io->upper, io->x0, io->targets,
+                               io->controls_inout};
+        void* dst[4] = {io->u0, q->residual_in, q->residual_out, q->status};
+        const int comps[14] = {4, 2 * I, 2, 2, I, I, I, 2, 2 * H, H * I, I, 1, 1, 1};
+        auto bind = [](polish::Args* a, const void* const* in, void* const* out) {
+            a->A = (const double*)in[0]; a->B = (const double*)in[1]; a->C = (const double*)in[2];
+            a->Q = (const double*)in[3]; a->R = (const double*)in[4]; a->lo = (const double*)in[5];
+            a->hi = (const double*)in[6]; a->x0 = (const double*)in[7]; a->targets = (const double*)in[8];
+            a->u = (double*)in[9];
+            a->u0 = (double*)out[0]; a->res_in = (double*)out[1]; a->res_out = (double*)out[2];
+            a->status = (int32_t*)out[3];
+        };
+        polish::Args a;
+        std::memset(&a, 0, sizeof(a));
+        a.n = n;
+        a.tol = q->tol;
+        a.max_rounds = q->max_rounds;
+        if (h->host_only) {   // on the calling thread, straight from and into the caller's arrays
+            a.ld = io->ld;
+            bind(&a, src, dst);
+            const uint32_t f = polish_general_host(I, H, a);
+            if (flags_out) *flags_out = f;
+            return TPC_MPC_OK;
+        }
+        HIP_TRY(h, hipSetDevice(h->device));
+        hipStream_t s = (hipStream_t)stream;
+        StreamOrderScope order(h, s);
+        rc = order.begin();
+        if (rc) return rc;
+        rc = ensure(h, &h->grad_ws, &h->grad_ws_bytes, pad256(polish_scratch_bytes(I, H, n)));
+        if (rc) return rc;
+        const int64_t lds = (n + 63) / 64 * 64;
+        int64_t off[14] = {0};
+        if (mem == TPC_MPC_DEVICE) {
+            a.ld = io->ld;
+            bind(&a, src, dst);
+        } else {
+            // HOST arrays: every component row copied on its own (n elements, never ld), as the backward entry
+            int64_t total = 0;
+            for (int c = 0; c < 14; ++c) { off[c] = total; total += pad256((int64_t)comps[c] * lds * 8); }
+            rc = ensure(h, &h->stage, &h->stage_bytes, total);
+            if (rc) return rc;
+            char* b = (char*)h->stage;
+            const void* sin[10];
+            void* sout[4];
+            for (int c = 0; c < 10; ++c) {
+                HIP_TRY(h, copy_rows(b + off[c], lds * 8, src[c], io->ld * 8, n * 8, comps[c], hipMemcpyHostToDevice, s));
+                sin[c] = b + off[c];
+            }
+            for (int c = 0; c < 4; ++c) sout[c] = dst[c] ? b + off[10 + c] : nullptr;
+            a.ld = lds;
+            bind(&a, sin, sout);
+        }
+        HIP_TRY(h, hipMemsetAsync(h->ws_words + 1, 0, sizeof(uint32_t), s));
+        hipError_t e = polish_general(I, H, a, h->grad_ws, h->ws_words + 1, s);
+        if (e != hipSuccess) return hip_fail(h, e, "kernel launch");
+        if (mem == TPC_MPC_HOST) {
+            const char* b = (const char*)h->stage;
+            HIP_TRY(h, copy_rows(io->controls_inout, io->ld * 8, b + off[9], lds * 8, n * 8, H * I, hipMemcpyDeviceToHost, s));
+            for (int c = 0; c < 3; ++c)
+                if (dst[c])
+                    HIP_TRY(h, copy_rows(dst[c], io->ld * 8, b + off[10 + c], lds * 8, n * 8, comps[10 + c],
+                                         hipMemcpyDeviceToHost, s));
+            if (q->status) HIP_TRY(h, hipMemcpyAsync(q->status, b + off[13], n * 4, hipMemcpyDeviceToHost, s));
             HIP_TRY(h, hipStreamSynchronize(s));
         }
         rc = order.end();

@@ -407,6 +407,67 @@ class MpcSolver:
         self.last_flags = flags.value
         return (u0, iters) if want_iters else u0
 
+    def polish_batch_general(self, A, B, Cc, Q, R, lower, upper, x0, targets, controls, tol: float = 1e-9,
+                             max_rounds: int = 8, want_status: bool = True, inputs: Optional[int] = None, **over):
+        """Polish solved sequences to the exact optimum (tpc_mpc_polish_batch_general), fp64 only.
+
+        Arrays as in solve_batch_general (numpy: HOST memory, CUDA torch tensors: DEVICE memory on the current stream);
+        `controls` [H*I, n] -- what solve_batch_general left there -- is updated in place: an instance that reaches
+        residual <= tol (dlib's eps) within max_rounds safeguarded Newton rounds gets the verified optimum, every other
+        one keeps its bits.  Returns (controls, status, residual_in, residual_out) with status int32 [n] = rounds
+        used or -1, and sets last_flags (FLAG_NOT_POLISHED if any instance was left); want_status=False returns
+        controls alone, leaves last_flags at 0 and keeps a DEVICE call asynchronous."""
+        p = self._params(**over)
+        H = p.horizon
+        if _is_torch(A):
+            import torch
+            n = A.shape[-1]
+            I = inputs or R.shape[0]
+
+            def ptr(t, rows):
+                if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == (rows, n)):
+                    raise ValueError(f"expected contiguous fp64 CUDA tensor [{rows},{n}]")
+                return t.data_ptr()
+
+            def new(dtype):
+                t = torch.empty(n, dtype=torch.float64 if dtype is np.float64 else torch.int32, device=A.device)
+                return t, t.data_ptr()
+            stream = C.c_void_p(torch.cuda.current_stream(A.device).cuda_stream)
+            mem = capi.DEVICE
+        else:
+            n = np.asarray(A).shape[-1]
+            I = inputs or np.asarray(R).shape[0]
+            keep = []
+
+            def ptr(a, rows):
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.shape != (rows, n):
+                    raise ValueError(f"expected an array [{rows},{n}]")
+                keep.append(a)
+                return a.ctypes.data
+
+            def new(dtype):
+                a = np.empty(n, dtype=dtype)
+                return a, a.ctypes.data
+            if not (isinstance(controls, np.ndarray) and controls.dtype == np.float64 and controls.flags.c_contiguous):
+                raise ValueError("controls must be a C-contiguous fp64 ndarray (it is updated in place)")
+            stream = None
+            mem = capi.HOST
+        status, sp = new(np.int32) if want_status else (None, None)
+        rin, rip = new(np.float64) if want_status else (None, None)
+        rout, rop = new(np.float64) if want_status else (None, None)
+        io = capi.GeneralIO(inputs=I, n=n, ld=n, A=ptr(A, 4), B=ptr(B, 2 * I), C=ptr(Cc, 2), Q=ptr(Q, 2),
+                            R=ptr(R, I), lower=ptr(lower, I), upper=ptr(upper, I), x0=ptr(x0, 2),
+                            targets=ptr(targets, 2 * H), controls_inout=ptr(controls, H * I), v_inout=None, u0=None,
+                            iters=None)
+        q = capi.Polish(tol=float(tol), max_rounds=int(max_rounds), reserved=0, status=sp, residual_in=rip,
+                        residual_out=rop)
+        flags = C.c_uint32(0)
+        self._check(self._lib.tpc_mpc_polish_batch_general(self._h, C.byref(p), C.byref(io), C.byref(q),
+                                                           C.byref(flags) if want_status else None, mem, stream))
+        self.last_flags = flags.value
+        return (controls, status, rin, rout) if want_status else controls
+
     GRAD_NAMES = ("A", "B", "C", "Q", "R", "lower", "upper", "x0", "targets", "kkt_residual")
 
     def solve_batch_general_backward(self, A, B, Cc, Q, R, lower, upper, x0, targets, controls, grad_controls,
