@@ -33,7 +33,7 @@ extern "C" {
 #endif
 
 #define TPC_MPC_ABI_VERSION 5   /* 5 = 4 + new symbols only (the split-named sharded entries; later additions, such as
-                                   tpc_mpc_solve_batch_general_backward, tpc_mpc_rollout_record / _backward and tpc_mpc_polish_batch_general,
+                                   tpc_mpc_solve_batch_general_backward, tpc_mpc_rollout_record / _backward / _polished and tpc_mpc_polish_batch_general,
                                    are new symbols and structs only and keep 5);
                                    4 broke 3: tpc_mpc_params.reserved became .options and must be zero-initialised */
 
@@ -392,6 +392,44 @@ int tpc_mpc_rollout_record(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_
                            int32_t steps, const void* new_last_targets, void* controls_out,
                            void* states_out, int32_t* iters_out, void* sequences_out, uint32_t* flags_out,
                            int mem, void* stream);
+
+/* No reference counterpart.  The closed loop of tpc_mpc_rollout with the polish of tpc_mpc_polish_batch_general between
+ * every solve and the plant update, so that every step returns the verified minimiser of its box QP (unique: R > 0)
+ * and the loop is a function of its inputs that does not depend on eps, the warm start or the kernel family beyond tol.
+ *   Definition.  Step k, per instance:
+ *     U_k <- the solve of tpc_mpc_rollout's step k (shift of the controls, warm start, p's eps / max_iter / algo)
+ *     U_k <- polish(U_k) with x_k, the shifted targets T_k, q->tol, q->max_rounds: the rule of
+ *            tpc_mpc_polish_batch_general, unchanged -- an instance whose residual passes tol is written, any other
+ *            keeps the solver's sequence
+ *     u0_k = row 0 of U_k;  x_{k+1} = A x_k + B u0_k + C  (tpc_mpc_rollout's plant arithmetic, operation for operation)
+ *     record u0_k, x_{k+1}, U_k, iters, status;  target shift and set_last_target as tpc_mpc_rollout
+ *   The result equals, bit for bit, the loop a caller could write from tpc_mpc_solve_batch_general (controls_inout and
+ *   v_inout carried), tpc_mpc_polish_batch_general and the plant update.
+ *   v (dlib's accelerated-gradient memory, v_inout) is left as the solve wrote it: the polish moves the sequence only.
+ *   The next solve reads v again only after dlib has reset it to the sequence at iteration 49 (mpc.h:328-334) -- except
+ *   when dlib's Q_diag == 0 `continue` (mpc.h:322) skips that reset at iteration 49: the projected-gradient steps then
+ *   start from the v of the previous call, which belongs to the unpolished sequence.  The polished loop is still the
+ *   composition above, since the composition carries the same v.
+ *   Method.  Per step the solve dispatch, then ONE kernel (csrc/mpc_rollout_polish.hip), one lane per instance: every
+ *   polish round in the lane, then the step tail of tpc_mpc_rollout without leaving it.
+ * q: tol > 0 and max_rounds >= 0 as in tpc_mpc_polish_batch_general (TPC_MPC_ERR_BAD_ARG otherwise, also for a null q).
+ *   q->status (int32), q->residual_in, q->residual_out (fp64) are optional and hold one row per step here: SoA [steps]
+ *   with the io's ld, like iters_out.  An (instance, step) pair the polish cannot verify keeps the solver's sequence for
+ *   that step, gets status -1 in that step's row and raises TPC_MPC_FLAG_NOT_POLISHED; the loop goes on from it.  An
+ *   instance with non-finite data or a model that breaks dlib's requires clause behaves as in tpc_mpc_rollout (its
+ *   rows, TPC_MPC_FLAG_NONFINITE / _BAD_MODEL), gets status -1 and residuals 0 in every step and does not raise
+ *   TPC_MPC_FLAG_NOT_POLISHED by itself.
+ * sequences_out is optional (NULL: not recorded); when given it holds the polished sequences in
+ * tpc_mpc_rollout_record's layout, i.e. exactly what tpc_mpc_rollout_backward is to be given together with states_out.
+ * io->controls_inout / v_inout (optional) carry the controller state in and out as in tpc_mpc_rollout (controls out =
+ * the last step's polished sequence).  Everything else as tpc_mpc_rollout.  fp64 only (p->dtype other than TPC_MPC_F64:
+ * TPC_MPC_ERR_BAD_ARG), horizons 1..64, one or two inputs.  n == 0 or steps == 0 returns TPC_MPC_OK with flags 0.
+ * Like the other closed loops it needs the device: a host-only handle (TPC_MPC_DEVICE_NONE) returns
+ * TPC_MPC_ERR_NO_DEVICE, after the argument checks above. */
+int tpc_mpc_rollout_polished(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io,
+                             int32_t steps, const void* new_last_targets, const tpc_mpc_polish* q,
+                             void* controls_out, void* states_out, int32_t* iters_out, void* sequences_out,
+                             uint32_t* flags_out, int mem, void* stream);
 
 /* Inputs and outputs of tpc_mpc_rollout_backward, SoA with the io's leading dimension ld:
  *   sequences[steps*H*I]  the recorded sequences, as tpc_mpc_rollout_record returns them (required)

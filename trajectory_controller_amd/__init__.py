@@ -5,7 +5,7 @@ Only the hot path lives here: csrc/ holds the gfx950 HIP kernels and
 (include/tpc_mpc.h -> lib/libtpc_mpc.so); capi.py / solver.py are the host-side binding;
 host/ is the C++ module shim that keeps the LMS surface; autograd.py makes the general-form solve and the closed loop torch
 autograd functions (their backward passes are the library's gradient kernels; MpcSolver.polish_batch_general moves a
-solved sequence onto the verified optimum).  Nothing in this package imports
+solved sequence onto the verified optimum, MpcSolver.rollout_polished does so inside every step of the closed loop).  Nothing in this package imports
 oracle/ -- that directory is the checker used by tests/ and bench.py only.
 """
 from .capi import (ALGO_AUTO, ALGO_GROUP, ALGO_LANE, ALGO_LANE_FMA, ALGO_WAVE, F32, F64, FLAG_BAD_MODEL, FLAG_MAX_ITER, FLAG_NONFINITE,

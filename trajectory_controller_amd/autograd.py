@@ -1,5 +1,6 @@
 """torch autograd over the batched general-form solve: `mpc_general` and the reference controller's `mpc_compact`,
-and over the closed loop: `mpc_rollout` (forward MpcSolver.rollout_record, backward tpc_mpc_rollout_backward).
+and over the closed loop: `mpc_rollout` (forward MpcSolver.rollout_record, or rollout_polished with polish=True;
+backward tpc_mpc_rollout_backward).
 
 Forward is MpcSolver.solve_batch_general from a fresh controller (zero controls); backward is
 tpc_mpc_solve_batch_general_backward on torch's current stream (include/tpc_mpc.h gives the definition of the
@@ -64,11 +65,16 @@ def mpc_general(solver, A, B, Cc, Q, R, lower, upper, x0, targets, polish=False,
 
 class _MpcRollout(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, solver, steps, over, A, B, Cc, Q, R, lower, upper, x0, targets, new_last_targets):
+    def forward(ctx, solver, steps, over, polish, A, B, Cc, Q, R, lower, upper, x0, targets, new_last_targets):
         I = R.shape[0]
         ins = [t.detach().contiguous() for t in (A, B, Cc, Q, R, lower, upper, x0, targets)]
         nlt = None if new_last_targets is None else new_last_targets.detach().contiguous()
-        controls, states, sequences, _ = solver.rollout_record(steps, *ins, nlt, inputs=I, **over)
+        if polish:   # every step onto the verified optimum before the plant moves; the backward is the same
+            tol, rounds = (1e-9, 8) if polish is True else polish
+            controls, states, sequences, _, _ = solver.rollout_polished(steps, *ins, nlt, inputs=I, tol=tol,
+                                                                        max_rounds=rounds, want_status=False, **over)
+        else:
+            controls, states, sequences, _ = solver.rollout_record(steps, *ins, nlt, inputs=I, **over)
         ctx.solver, ctx.steps, ctx.over, ctx.I = solver, steps, over, I
         ctx.has_nlt = nlt is not None
         ctx.save_for_backward(*ins, *(() if nlt is None else (nlt,)), states, sequences)
@@ -82,27 +88,34 @@ class _MpcRollout(torch.autograd.Function):
         nlt = rest.pop(0) if ctx.has_nlt else None
         states, sequences = rest
         names = ("A", "B", "C", "Q", "R", "lower", "upper", "x0", "targets", "new_last_targets")
-        want = tuple(k for k, need in zip(names, ctx.needs_input_grad[3:]) if need)
+        want = tuple(k for k, need in zip(names, ctx.needs_input_grad[4:]) if need)
         if not want:
-            return (None,) * 13
+            return (None,) * 14
         g = ctx.solver.rollout_backward(ctx.steps, *ins, nlt, sequences=sequences, states=states,
                                         grad_controls=None if grad_controls is None else grad_controls.contiguous(),
                                         grad_states=None if grad_states is None else grad_states.contiguous(),
                                         inputs=ctx.I, want=want, want_flags=False, **ctx.over)
-        return (None, None, None) + tuple(g.get(k) for k in names)
+        return (None, None, None, None) + tuple(g.get(k) for k in names)
 
 
-def mpc_rollout(solver, steps, A, B, Cc, Q, R, lower, upper, x0, targets, new_last_targets=None, **over):
+def mpc_rollout(solver, steps, A, B, Cc, Q, R, lower, upper, x0, targets, new_last_targets=None, polish=False, **over):
     """The closed loop of n fresh dlib::mpc<2,I,H> controllers (MpcSolver.rollout: `steps` warm-started operator()
     calls with the target shift and the plant update x <- A x + B u + C between them) as a differentiable function.
     Returns (controls [steps*I, n], states [steps*2, n]); gradients reach A, B, C, Q, R, lower, upper, x0, targets and
     new_last_targets [steps*2, n] (component-major CUDA fp64 tensors, solve_batch_general's layout).  Each step is
     differentiated on the active set of its solved sequence (tpc_mpc_rollout_backward, include/tpc_mpc.h); the warm
-    start gets no gradient.  Pass a small eps for accurate gradients.  `over` overrides the solver's parameters."""
+    start gets no gradient.  That is the derivative of the closed loop when every step's sequence is the optimum, which
+    dlib's default eps 0.01 does not give: pass polish=True (or a (tol, max_rounds) pair; True is (1e-9, 8), the
+    convention of mpc_general).  The forward is then MpcSolver.rollout_polished -- every step's sequence is moved onto
+    the verified optimum before the plant moves, so the loop no longer depends on eps or the warm start beyond tol and
+    "no gradient to the warm start" is exact -- and the backward runs on the polished sequences; a step the polish
+    cannot verify keeps the solver's sequence.  (A small eps, e.g. eps=1e-10, is the expensive alternative.)
+    polish=False is the unpolished loop, bit for bit.  `over` overrides the solver's parameters."""
     for t in (A, B, Cc, Q, R, lower, upper, x0, targets) + (() if new_last_targets is None else (new_last_targets,)):
         if not (t.is_cuda and t.dtype == torch.float64):
             raise ValueError("mpc_rollout takes CUDA fp64 tensors")
-    return _MpcRollout.apply(solver, int(steps), over, A, B, Cc, Q, R, lower, upper, x0, targets, new_last_targets)
+    return _MpcRollout.apply(solver, int(steps), over, polish, A, B, Cc, Q, R, lower, upper, x0, targets,
+                             new_last_targets)
 
 
 def mpc_compact(solver, v, delta_y, delta_phi, weights, step_size=0.1, wheelbase=0.21,

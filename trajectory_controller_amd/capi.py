@@ -40,7 +40,7 @@ EXPORTS = ("tpc_mpc_default_params", "tpc_mpc_create", "tpc_mpc_destroy", "tpc_m
            "tpc_mpc_solve_batch_general_sharded", "tpc_mpc_last_flags", "tpc_mpc_gather_shards",
            "tpc_mpc_shard_map", "tpc_mpc_solve_batch_compact_sharded_split", "tpc_mpc_gather_shards_split",
            "tpc_mpc_solve_batch_general_backward", "tpc_mpc_rollout_record", "tpc_mpc_rollout_backward",
-           "tpc_mpc_polish_batch_general")
+           "tpc_mpc_polish_batch_general", "tpc_mpc_rollout_polished")
 SPLIT_BLOCK, SPLIT_INTERLEAVED = 0, 1
 SPLITS = {"block": SPLIT_BLOCK, "interleaved": SPLIT_INTERLEAVED}
 
@@ -147,6 +147,8 @@ def load_library(path: str | None = None) -> C.CDLL:
                                     vp, u32p, C.c_int, vp]
     lib.tpc_mpc_rollout_record.argtypes = [vp, C.POINTER(Params), C.POINTER(GeneralIO), C.c_int32, vp, vp, vp,
                                            vp, vp, u32p, C.c_int, vp]
+    lib.tpc_mpc_rollout_polished.argtypes = [vp, C.POINTER(Params), C.POINTER(GeneralIO), C.c_int32, vp,
+                                             C.POINTER(Polish), vp, vp, vp, vp, u32p, C.c_int, vp]
     lib.tpc_mpc_rollout_backward.argtypes = [vp, C.POINTER(Params), C.POINTER(GeneralIO), C.c_int32, vp,
                                              C.POINTER(RolloutGrad), u32p, C.c_int, vp]
     lib.tpc_mpc_set_profiling.argtypes = [vp, C.c_int]

@@ -53,6 +53,9 @@ uint32_t rollout_grad_host(int I, int H, const grad::RollArgs& a);
 int64_t polish_scratch_bytes(int I, int H, int64_t n);
 hipError_t polish_general(int I, int H, const polish::Args& a, void* ws, uint32_t* flags, hipStream_t s);
 uint32_t polish_general_host(int I, int H, const polish::Args& a);
+// ... and fused with the rollout's step tail (mpc_rollout_polish.hip): one step of tpc_mpc_rollout_polished
+hipError_t launch_rollout_polish_step(int I, const polish::Args& p, const RolloutStepArgs& r, void* ws, uint32_t* flags,
+                                      hipStream_t s);
 
 thread_local char g_create_error[kTpcErrLen] = "";
 }  // namespace tpc
@@ -1281,16 +1284,26 @@ int tpc_mpc_polish_batch_general(tpc_mpc_handle h, const tpc_mpc_params* p, cons
 
 namespace {
 
-// tpc_mpc_rollout, and tpc_mpc_rollout_record when sequences_out != NULL
+// tpc_mpc_rollout, tpc_mpc_rollout_record (record: sequences_out is required) and tpc_mpc_rollout_polished (polished:
+// q is required, every step's solve is followed by the fused polish + step kernel instead of the step kernel)
 int rollout_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io, int32_t steps,
                  const void* new_last_targets, void* controls_out, void* states_out, int32_t* iters_out,
-                 void* sequences_out, bool record, uint32_t* flags_out, int mem, void* stream) {
+                 void* sequences_out, bool record, bool polished, const tpc_mpc_polish* q, uint32_t* flags_out, int mem,
+                 void* stream) {
     return guarded(h, [&]() -> int {
-        int rc = check_common(h, p);
+        // the polished loop checks its arguments before it asks for the device, so that a host-only handle reports them
+        int rc = check_common(h, p, polished);
         if (rc) return rc;
+        if (polished && p->dtype != TPC_MPC_F64)
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "tpc_mpc_rollout_polished is fp64 only: p->dtype must be TPC_MPC_F64");
         rc = check_general_io(h, io, mem);
         if (rc) return rc;
+        if (polished && !q) return fail(h, TPC_MPC_ERR_BAD_ARG, "null polish struct");
+        if (polished && (!(q->tol > 0.0) || q->max_rounds < 0))
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "polish needs tol > 0 and max_rounds >= 0");
         if (steps < 0 || steps > (1 << 24)) return fail(h, TPC_MPC_ERR_BAD_ARG, "need 0 <= steps <= 2^24");
+        if (h->host_only)
+            return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): the closed loops run on the device only");
         if (io->n == 0 || steps == 0) { if (flags_out) *flags_out = 0; return TPC_MPC_OK; }
         if (!io->A || !io->B || !io->C || !io->Q || !io->R || !io->lower || !io->upper || !io->x0 ||
             !io->targets || !controls_out)
@@ -1324,6 +1337,10 @@ int rollout_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_genera
         const int64_t o_iters = total; total += pad256(ldw * 4);
         rc = ensure(h, &h->roll, &h->roll_bytes, total);
         if (rc) return rc;
+        if (polished) {
+            rc = ensure(h, &h->grad_ws, &h->grad_ws_bytes, pad256(polish_scratch_bytes(I, H, n)));
+            if (rc) return rc;
+        }
         char* w = (char*)h->roll;
         for (int c = 0; c < 11; ++c) {
             if (src[c]) HIP_TRY(h, copy_rows(w + off[c], ldw * es, src[c], ld * es, n * es, comps[c], in_kind, s));
@@ -1334,12 +1351,18 @@ int rollout_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_genera
         int64_t ld_nlt = ld, ld_out = ld;
         char *d_ctrl = (char*)controls_out, *d_states = (char*)states_out, *d_seq = (char*)sequences_out;
         int32_t* d_iters = iters_out;
+        // ... and the polish's three per-step rows ([steps] rows like iters_out)
+        int32_t* d_status = polished ? q->status : nullptr;
+        char *d_rin = polished ? (char*)q->residual_in : nullptr, *d_rout = polished ? (char*)q->residual_out : nullptr;
         if (host) {
             const int64_t s_nlt = 0, s_ctrl = s_nlt + pad256((int64_t)steps * 2 * ldw * es);
             const int64_t s_states = s_ctrl + pad256((int64_t)steps * I * ldw * es);
             const int64_t s_iters = s_states + pad256((int64_t)steps * 2 * ldw * es);
             const int64_t s_seq = s_iters + pad256((int64_t)steps * ldw * 4);
-            const int64_t s_end = s_seq + (sequences_out ? pad256((int64_t)steps * H * I * ldw * es) : 0);
+            const int64_t s_status = s_seq + (sequences_out ? pad256((int64_t)steps * H * I * ldw * es) : 0);
+            const int64_t s_rin = s_status + (d_status ? pad256((int64_t)steps * ldw * 4) : 0);
+            const int64_t s_rout = s_rin + (d_rin ? pad256((int64_t)steps * ldw * 8) : 0);
+            const int64_t s_end = s_rout + (d_rout ? pad256((int64_t)steps * ldw * 8) : 0);
             rc = ensure(h, &h->stage, &h->stage_bytes, s_end);
             if (rc) return rc;
             char* b = (char*)h->stage;
@@ -1353,6 +1376,9 @@ int rollout_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_genera
             d_states = states_out ? b + s_states : nullptr;
             d_iters = iters_out ? (int32_t*)(b + s_iters) : nullptr;
             d_seq = sequences_out ? b + s_seq : nullptr;
+            if (d_status) d_status = (int32_t*)(b + s_status);
+            if (d_rin) d_rin = b + s_rin;
+            if (d_rout) d_rout = b + s_rout;
         }
 
         GeneralArgs a;
@@ -1372,6 +1398,15 @@ int rollout_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_genera
         r.controls_out = d_ctrl; r.states_out = d_states;
         r.iters_step = a.iters; r.iters_out = d_iters; r.sequences_out = d_seq;
 
+        polish::Args pa;
+        std::memset(&pa, 0, sizeof(pa));
+        if (polished) {
+            pa.n = n; pa.ld = ldw; pa.tol = q->tol; pa.max_rounds = q->max_rounds;
+            pa.A = (const double*)a.A; pa.B = (const double*)a.B; pa.C = (const double*)a.C; pa.Q = (const double*)a.Q;
+            pa.R = (const double*)a.R; pa.lo = (const double*)a.lo; pa.hi = (const double*)a.hi;
+            pa.x0 = (const double*)r.x; pa.targets = (const double*)r.targets; pa.u = (double*)(w + off[9]);
+        }
+
         Workspace ws;
         rc = prepare_workspace(h, algo, H, p->dtype, n, &ws, 1);
         if (rc) return rc;
@@ -1381,7 +1416,14 @@ int rollout_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_genera
             hipError_t e = dispatch_general(algo, I, H, p->dtype, a, kn, ws, s);
             if (e != hipSuccess) return hip_fail(h, e, "kernel launch");
             r.step = st;
-            e = launch_rollout_step(p->dtype, r, s);
+            if (polished) {   // the step's rows of the polish outputs; the sequence is polished where the loop keeps it
+                pa.status = d_status ? d_status + (int64_t)st * ld_out : nullptr;
+                pa.res_in = d_rin ? (double*)d_rin + (int64_t)st * ld_out : nullptr;
+                pa.res_out = d_rout ? (double*)d_rout + (int64_t)st * ld_out : nullptr;
+                e = launch_rollout_polish_step(I, pa, r, h->grad_ws, h->ws_words + 1, s);
+            } else {
+                e = launch_rollout_step(p->dtype, r, s);
+            }
             if (e != hipSuccess) return hip_fail(h, e, "rollout step launch");
         }
         // controller state back to the caller
@@ -1397,6 +1439,12 @@ int rollout_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_genera
             if (sequences_out)
                 HIP_TRY(h, copy_rows(sequences_out, ld * es, d_seq, ldw * es, n * es, (int64_t)steps * H * I,
                                      hipMemcpyDeviceToHost, s));
+            if (d_status)
+                HIP_TRY(h, copy_rows(q->status, ld * 4, d_status, ldw * 4, n * 4, steps, hipMemcpyDeviceToHost, s));
+            if (d_rin)
+                HIP_TRY(h, copy_rows(q->residual_in, ld * 8, d_rin, ldw * 8, n * 8, steps, hipMemcpyDeviceToHost, s));
+            if (d_rout)
+                HIP_TRY(h, copy_rows(q->residual_out, ld * 8, d_rout, ldw * 8, n * 8, steps, hipMemcpyDeviceToHost, s));
             HIP_TRY(h, hipStreamSynchronize(s));
         }
         rc = order.end();
@@ -1407,12 +1455,20 @@ int rollout_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_genera
 
 }  // namespace
 
+int tpc_mpc_rollout_polished(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io,
+                             int32_t steps, const void* new_last_targets, const tpc_mpc_polish* q,
+                             void* controls_out, void* states_out, int32_t* iters_out, void* sequences_out,
+                             uint32_t* flags_out, int mem, void* stream) {
+    return rollout_impl(h, p, io, steps, new_last_targets, controls_out, states_out, iters_out, sequences_out, false,
+                        true, q, flags_out, mem, stream);
+}
+
 int tpc_mpc_rollout(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io,
                     int32_t steps, const void* new_last_targets, void* controls_out,
                     void* states_out, int32_t* iters_out, uint32_t* flags_out, int mem,
                     void* stream) {
     return rollout_impl(h, p, io, steps, new_last_targets, controls_out, states_out, iters_out, nullptr, false,
-                        flags_out, mem, stream);
+                        false, nullptr, flags_out, mem, stream);
 }
 
 int tpc_mpc_rollout_record(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io,
@@ -1420,7 +1476,7 @@ int tpc_mpc_rollout_record(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_
                            void* states_out, int32_t* iters_out, void* sequences_out, uint32_t* flags_out,
                            int mem, void* stream) {
     return rollout_impl(h, p, io, steps, new_last_targets, controls_out, states_out, iters_out, sequences_out, true,
-                        flags_out, mem, stream);
+                        false, nullptr, flags_out, mem, stream);
 }
 
 int tpc_mpc_rollout_backward(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io, int32_t steps,
