@@ -33,7 +33,7 @@ extern "C" {
 #endif
 
 #define TPC_MPC_ABI_VERSION 5   /* 5 = 4 + new symbols only (the split-named sharded entries; later additions, such as
-                                   tpc_mpc_solve_batch_general_backward, tpc_mpc_rollout_record / _backward / _polished and tpc_mpc_polish_batch_general,
+                                   tpc_mpc_solve_batch_general_backward, tpc_mpc_rollout_record / _backward / _polished / _newton and tpc_mpc_polish_batch_general,
                                    are new symbols and structs only and keep 5);
                                    4 broke 3: tpc_mpc_params.reserved became .options and must be zero-initialised */
 
@@ -430,6 +430,54 @@ int tpc_mpc_rollout_polished(tpc_mpc_handle h, const tpc_mpc_params* p, const tp
                              int32_t steps, const void* new_last_targets, const tpc_mpc_polish* q,
                              void* controls_out, void* states_out, int32_t* iters_out, void* sequences_out,
                              uint32_t* flags_out, int mem, void* stream);
+
+/* No reference counterpart.  The polished closed loop with the Newton rounds FIRST: the polish is an active-set Newton
+ * method that carries its own proof (a sequence whose residual passes tol under dlib's mask is the unique minimiser,
+ * whatever produced it), so the first-order solve is needed only where the polish does not verify from the shifted
+ * warm start.  An instance the polish verifies at every step costs no solve at all, and the whole loop of such
+ * instances is ONE kernel launch (csrc/mpc_rollout_newton.hip, one lane per instance, all steps).
+ *   Phase 1, the Newton pass.  Per instance, for k = 0 .. steps-1:
+ *     U   <- dlib's shift of the carried controls (mpc.h:231-232), at step 0 too, exactly as tpc_mpc_rollout does it;
+ *            the start is io->controls_inout, zeros when that is NULL
+ *     U   <- polish(U) at x_k with the shifted targets T_k, q->tol, q->max_rounds: the rule of
+ *            tpc_mpc_polish_batch_general, unchanged
+ *     not verified (the polish's status -1): the instance stops here, first_unverified = k, and this phase writes none
+ *            of its rows of step k and later
+ *     verified: u0_k = row 0 of U;  x_{k+1} = A x_k + B u0_k + C in tpc_mpc_rollout's plant arithmetic;  record u0_k,
+ *            x_{k+1}, U_k, status = the rounds used, the residual rows, iters_out 0;  target shift and set_last_target
+ *            as tpc_mpc_rollout
+ *   An instance verified at every step gets first_unverified = steps.  A verified step equals, bit for bit,
+ *   tpc_mpc_polish_batch_general on the shifted sequence followed by tpc_mpc_rollout's step.
+ *   Phase 2, fallback TPC_MPC_NEWTON_FALLBACK_SOLVE.  The instances with first_unverified < steps are gathered into a
+ *   compact batch, run from step 0 through tpc_mpc_rollout_polished's loop (p's eps / max_iter / algo, the same q), and
+ *   every output row of theirs -- v included -- is scattered back: their outputs are exactly what
+ *   tpc_mpc_rollout_polished returns for the gathered batch.  They raise TPC_MPC_FLAG_NOT_POLISHED only for
+ *   (instance, step) pairs that loop itself leaves at -1.  first_unverified keeps phase 1's value, so the caller sees
+ *   who fell back.  The order of the instances inside the compact batch is not defined.  One 4-byte read-back (the
+ *   number of such instances) sits between the phases; there is no other host synchronisation inside the loop.
+ *   Fallback TPC_MPC_NEWTON_FALLBACK_NONE.  Phase 1 only: the rows of an unverified instance from first_unverified on
+ *   get status -1, residuals 0 and zero controls / states / sequences / iters, the instance raises
+ *   TPC_MPC_FLAG_NOT_POLISHED, and its controls_inout / v_inout come back zero (the last step's sequence row).
+ *   Controller state out.  controls_inout is the last step's sequence.  v_inout of an instance phase 1 carried through
+ *   is set equal to that sequence -- the value dlib itself resets v to (mpc.h:328-334); a fallback instance's v is
+ *   whatever the polished loop left.
+ *   Invalid instances (non-finite data, or a model that breaks dlib's requires clause; also a state that stops being
+ *   finite at a later step) keep their TPC_MPC_FLAG_NONFINITE / _BAD_MODEL, stop at that step like an unverified one
+ *   (first_unverified = the step, rows as under FALLBACK_NONE), are NOT sent to the fallback under either mode and do
+ *   not raise TPC_MPC_FLAG_NOT_POLISHED by themselves.
+ * Arguments as tpc_mpc_rollout_polished, plus `fallback` and the optional first_unverified (int32 [n], NULL: not
+ * returned).  q->status / residual_in / residual_out hold one row per step.  A null q, tol <= 0, max_rounds < 0, an
+ * unknown fallback or a dtype other than TPC_MPC_F64 return TPC_MPC_ERR_BAD_ARG.  fp64 only, horizons 1..64, one or
+ * two inputs.  n == 0 or steps == 0 returns TPC_MPC_OK with flags 0.
+ * A host-only handle (TPC_MPC_DEVICE_NONE) runs FALLBACK_NONE on the calling thread with the kernel's bits (HOST memory
+ * only), as tpc_mpc_polish_batch_general does; with FALLBACK_SOLVE it returns TPC_MPC_ERR_NO_DEVICE, after the argument
+ * checks above. */
+#define TPC_MPC_NEWTON_FALLBACK_SOLVE 0
+#define TPC_MPC_NEWTON_FALLBACK_NONE 1
+int tpc_mpc_rollout_newton(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io,
+                           int32_t steps, const void* new_last_targets, const tpc_mpc_polish* q, int32_t fallback,
+                           void* controls_out, void* states_out, int32_t* iters_out, void* sequences_out,
+                           int32_t* first_unverified, uint32_t* flags_out, int mem, void* stream);
 
 /* Inputs and outputs of tpc_mpc_rollout_backward, SoA with the io's leading dimension ld:
  *   sequences[steps*H*I]  the recorded sequences, as tpc_mpc_rollout_record returns them (required)

@@ -70,9 +70,10 @@ class _MpcRollout(torch.autograd.Function):
         ins = [t.detach().contiguous() for t in (A, B, Cc, Q, R, lower, upper, x0, targets)]
         nlt = None if new_last_targets is None else new_last_targets.detach().contiguous()
         if polish:   # every step onto the verified optimum before the plant moves; the backward is the same
-            tol, rounds = (1e-9, 8) if polish is True else polish
-            controls, states, sequences, _, _ = solver.rollout_polished(steps, *ins, nlt, inputs=I, tol=tol,
-                                                                        max_rounds=rounds, want_status=False, **over)
+            tol, rounds, newton_first = polish
+            forward = solver.rollout_newton if newton_first else solver.rollout_polished
+            controls, states, sequences, *_ = forward(steps, *ins, nlt, inputs=I, tol=tol, max_rounds=rounds,
+                                                      want_status=False, **over)
         else:
             controls, states, sequences, _ = solver.rollout_record(steps, *ins, nlt, inputs=I, **over)
         ctx.solver, ctx.steps, ctx.over, ctx.I = solver, steps, over, I
@@ -98,7 +99,8 @@ class _MpcRollout(torch.autograd.Function):
         return (None, None, None, None) + tuple(g.get(k) for k in names)
 
 
-def mpc_rollout(solver, steps, A, B, Cc, Q, R, lower, upper, x0, targets, new_last_targets=None, polish=False, **over):
+def mpc_rollout(solver, steps, A, B, Cc, Q, R, lower, upper, x0, targets, new_last_targets=None, polish=False,
+                newton_first=False, **over):
     """The closed loop of n fresh dlib::mpc<2,I,H> controllers (MpcSolver.rollout: `steps` warm-started operator()
     calls with the target shift and the plant update x <- A x + B u + C between them) as a differentiable function.
     Returns (controls [steps*I, n], states [steps*2, n]); gradients reach A, B, C, Q, R, lower, upper, x0, targets and
@@ -110,7 +112,14 @@ def mpc_rollout(solver, steps, A, B, Cc, Q, R, lower, upper, x0, targets, new_la
     the verified optimum before the plant moves, so the loop no longer depends on eps or the warm start beyond tol and
     "no gradient to the warm start" is exact -- and the backward runs on the polished sequences; a step the polish
     cannot verify keeps the solver's sequence.  (A small eps, e.g. eps=1e-10, is the expensive alternative.)
-    polish=False is the unpolished loop, bit for bit.  `over` overrides the solver's parameters."""
+    polish=False is the unpolished loop, bit for bit.  newton_first=True (with polish) makes the forward
+    MpcSolver.rollout_newton: every step is polished from the shifted warm start first, all steps in one launch, and
+    only the instances it does not verify run rollout_polished's loop; both forwards return the verified optimum of
+    every step, so they agree to rounding, and the backward is the same.  `over` overrides the solver's parameters."""
+    if newton_first and not polish:
+        raise ValueError("newton_first needs polish")
+    if polish:
+        polish = ((1e-9, 8) if polish is True else tuple(polish)) + (bool(newton_first),)
     for t in (A, B, Cc, Q, R, lower, upper, x0, targets) + (() if new_last_targets is None else (new_last_targets,)):
         if not (t.is_cuda and t.dtype == torch.float64):
             raise ValueError("mpc_rollout takes CUDA fp64 tensors")

@@ -1,8 +1,9 @@
 // The step tail of the closed loops (tpc_mpc_rollout, tpc_mpc_rollout_record, tpc_mpc_rollout_polished): what the
 // caller of dlib::mpc does between two operator() calls (reference: dlib_files/dlib/test/mpc.cpp:301-316) plus the
 // target shift operator() performs itself (mpc.h:236-237), for instance k.  Shared by rollout_step_kernel
-// (mpc_rollout.hip) and the fused polish + step kernel (mpc_rollout_polish.hip); no fused multiply-add in it, and the
-// units that include it are built with -ffp-contract=off, so both give the same bits.
+// (mpc_rollout.hip), the fused polish + step kernel (mpc_rollout_polish.hip) and the Newton-first loop
+// (mpc_rollout_newton.hip, kernel and host path); no fused multiply-add in it, and the units that include it are built
+// with -ffp-contract=off, so all give the same bits.
 #pragma once
 
 #include "mpc_internal.h"
@@ -10,7 +11,7 @@
 namespace tpc {
 
 template <typename T>
-__device__ __forceinline__ void rollout_step_tail(const RolloutStepArgs& a, int64_t k) {
+__host__ __device__ __forceinline__ void rollout_step_tail(const RolloutStepArgs& a, int64_t k) {
     const int64_t ld = a.ld;
     const T* A = (const T*)a.A + k;
     const T* B = (const T*)a.B + k;

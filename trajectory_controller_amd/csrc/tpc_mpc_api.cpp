@@ -8,10 +8,12 @@
 #include "auto_table.h"
 #include "mpc_grad_model.h"
 #include "mpc_polish_model.h"
+#include "mpc_rollout_newton.h"
 
 #include <cmath>
 #include <cstdlib>
 #include <mutex>
+#include <vector>
 
 namespace tpc {
 // per-horizon launchers, one translation unit each (mpc_lane_inst.hip / mpc_wave_inst.hip)
@@ -884,6 +886,8 @@ int tpc_mpc_destroy(tpc_mpc_handle h) {
         if (h->roll) (void)hipFree(h->roll);
         if (h->cap_iters) (void)hipFree(h->cap_iters);
         if (h->grad_ws) (void)hipFree(h->grad_ws);
+        if (h->newton) (void)hipFree(h->newton);
+        if (h->newton_fb) (void)hipFree(h->newton_fb);
         if (h->mix) (void)hipFree(h->mix);
         if (h->gather) (void)hipFree(h->gather);
         if (h->pre_stream) { (void)hipStreamSynchronize(h->pre_stream); (void)hipStreamDestroy(h->pre_stream); }
@@ -1477,6 +1481,254 @@ int tpc_mpc_rollout_record(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_
                            int mem, void* stream) {
     return rollout_impl(h, p, io, steps, new_last_targets, controls_out, states_out, iters_out, sequences_out, true,
                         false, nullptr, flags_out, mem, stream);
+}
+
+// The Newton-first closed loop (include/tpc_mpc.h): phase 1 is ONE launch for the whole loop (mpc_rollout_newton.hip);
+// with TPC_MPC_NEWTON_FALLBACK_SOLVE the instances it could not verify are gathered into a compact batch, run through
+// rollout_impl's polished mode from step 0 and scattered back.  One 4-byte read-back (the fallback's count) sits between
+// the phases; a host-only handle runs phase 1 on the calling thread.
+int tpc_mpc_rollout_newton(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io, int32_t steps,
+                           const void* new_last_targets, const tpc_mpc_polish* q, int32_t fallback, void* controls_out,
+                           void* states_out, int32_t* iters_out, void* sequences_out, int32_t* first_unverified,
+                           uint32_t* flags_out, int mem, void* stream) {
+    return guarded(h, [&]() -> int {
+        int rc = check_common(h, p, true);
+        if (rc) return rc;
+        if (p->dtype != TPC_MPC_F64)
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "tpc_mpc_rollout_newton is fp64 only: p->dtype must be TPC_MPC_F64");
+        rc = check_general_io(h, io, mem);
+        if (rc) return rc;
+        if (!q) return fail(h, TPC_MPC_ERR_BAD_ARG, "null polish struct");
+        if (!(q->tol > 0.0) || q->max_rounds < 0)
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "polish needs tol > 0 and max_rounds >= 0");
+        if (fallback != TPC_MPC_NEWTON_FALLBACK_SOLVE && fallback != TPC_MPC_NEWTON_FALLBACK_NONE)
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "unknown fallback %d", (int)fallback);
+        if (steps < 0 || steps > (1 << 24)) return fail(h, TPC_MPC_ERR_BAD_ARG, "need 0 <= steps <= 2^24");
+        const bool solve = fallback == TPC_MPC_NEWTON_FALLBACK_SOLVE;
+        if (h->host_only && solve)
+            return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): the fallback solve runs on the device only; use TPC_MPC_NEWTON_FALLBACK_NONE");
+        if (h->host_only && mem == TPC_MPC_DEVICE)
+            return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): HOST memory only");
+        if (io->n == 0 || steps == 0) { if (flags_out) *flags_out = 0; return TPC_MPC_OK; }
+        if (!io->A || !io->B || !io->C || !io->Q || !io->R || !io->lower || !io->upper || !io->x0 ||
+            !io->targets || !controls_out)
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "null batch pointer");
+        const int I = io->inputs, H = p->horizon;
+        const int64_t n = io->n, ld = io->ld;
+        // the working set: a copy of the model, then x0, targets, controls and v AS GIVEN (what the fallback restarts
+        // from), row after row with one leading dimension
+        //   0 A[4] 1 B[2I] 2 C[2] 3 Q[2] 4 R[I] 5 lo[I] 6 hi[I] 7 x[2] 8 targets[2H] 9 controls[HI] 10 v[HI]
+        const int comps[11] = {4, 2 * I, 2, 2, I, I, I, 2, 2 * H, H * I, H * I};
+        const void* src[11] = {io->A, io->B, io->C, io->Q, io->R, io->lower, io->upper, io->x0, io->targets,
+                               io->controls_inout, io->v_inout};
+        int64_t row[12];
+        row[0] = 0;
+        for (int c = 0; c < 11; ++c) row[c + 1] = row[c] + comps[c];
+        const int64_t rows_in = row[11], rows_work = 2 + 2 * H + H * I;   // ... and the state the loop carries: x, targets, controls
+
+        NewtonArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.p.n = n; a.p.tol = q->tol; a.p.max_rounds = q->max_rounds;
+        a.r.n = n; a.r.I = I; a.r.H = H; a.r.steps = steps;
+        a.raise_not_polished = solve ? 0 : 1;
+        auto bind = [&](char* w, int64_t ldw) {   // w: rows_in rows as given, then rows_work rows of carried state
+            auto at = [&](int64_t r) { return (double*)(w + r * ldw * 8); };
+            a.p.ld = a.r.ld = ldw;
+            a.p.A = at(row[0]); a.p.B = at(row[1]); a.p.C = at(row[2]); a.p.Q = at(row[3]); a.p.R = at(row[4]);
+            a.p.lo = at(row[5]); a.p.hi = at(row[6]);
+            a.p.x0 = at(rows_in); a.p.targets = at(rows_in + 2); a.p.u = at(rows_in + 2 + 2 * H);
+            a.r.A = a.p.A; a.r.B = a.p.B; a.r.C = a.p.C;
+            a.r.x = at(rows_in); a.r.targets = at(rows_in + 2); a.r.controls = a.p.u;
+        };
+
+        if (h->host_only) {   // on the calling thread, outputs straight into the caller's arrays
+            std::vector<double> w((size_t)((rows_in + rows_work) * n), 0.0);
+            std::vector<int32_t> fu(first_unverified ? 0 : (size_t)n);
+            for (int c = 0; c < 10; ++c)
+                if (src[c])
+                    for (int64_t r = 0; r < comps[c]; ++r)
+                        std::memcpy(&w[(size_t)((row[c] + r) * n)], (const double*)src[c] + r * ld, (size_t)n * 8);
+            std::memcpy(&w[(size_t)(rows_in * n)], &w[(size_t)(row[7] * n)], (size_t)(rows_work * n) * 8);
+            bind((char*)w.data(), n);
+            a.r.ld_out = a.r.ld_nlt = ld;
+            a.r.new_last_targets = new_last_targets;
+            a.r.controls_out = controls_out; a.r.states_out = states_out; a.r.iters_out = iters_out;
+            a.r.sequences_out = sequences_out;
+            a.p.status = q->status; a.p.res_in = (double*)q->residual_in; a.p.res_out = (double*)q->residual_out;
+            a.first_unverified = first_unverified ? first_unverified : fu.data();
+            const uint32_t f = rollout_newton_host(I, a);
+            for (int64_t r = 0; r < H * I; ++r) {
+                if (io->controls_inout) std::memcpy((double*)io->controls_inout + r * ld, a.p.u + r * n, (size_t)n * 8);
+                if (io->v_inout) std::memcpy((double*)io->v_inout + r * ld, a.p.u + r * n, (size_t)n * 8);
+            }
+            if (flags_out) *flags_out = f;
+            return TPC_MPC_OK;
+        }
+
+        HIP_TRY(h, hipSetDevice(h->device));
+        hipStream_t s = (hipStream_t)stream;
+        StreamOrderScope order(h, s);
+        rc = order.begin();
+        if (rc) return rc;
+        const bool host = mem == TPC_MPC_HOST;
+        const hipMemcpyKind in_kind = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+        const hipMemcpyKind out_kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+        const int64_t ldw = (n + 63) / 64 * 64;
+        const int64_t o_fu = (rows_in + rows_work) * ldw * 8, o_idx = o_fu + ldw * 4, o_words = o_idx + ldw * 4;
+        rc = ensure(h, &h->newton, &h->newton_bytes, o_words + 256);
+        if (rc) return rc;
+        rc = ensure(h, &h->grad_ws, &h->grad_ws_bytes, pad256(polish_scratch_bytes(I, H, n)));
+        if (rc) return rc;
+        char* w = (char*)h->newton;
+        for (int c = 0; c < 11; ++c) {
+            if (src[c]) HIP_TRY(h, copy_rows(w + row[c] * ldw * 8, ldw * 8, src[c], ld * 8, n * 8, comps[c], in_kind, s));
+            else HIP_TRY(h, hipMemsetAsync(w + row[c] * ldw * 8, 0, (size_t)(comps[c] * ldw * 8), s));
+        }
+        HIP_TRY(h, hipMemcpyAsync(w + rows_in * ldw * 8, w + row[7] * ldw * 8, (size_t)(rows_work * ldw * 8),
+                                  hipMemcpyDeviceToDevice, s));
+        int32_t* d_fu = (int32_t*)(w + o_fu);
+        int32_t* d_idx = (int32_t*)(w + o_idx);
+        uint32_t* d_words = (uint32_t*)(w + o_words);   // [0] the fallback's count, [1] phase 1's flags
+        HIP_TRY(h, hipMemsetAsync(d_words, 0, 8, s));
+
+        // HOST mode: new_last_targets in, and the per-step outputs, go through the staging buffer (as rollout_impl)
+        const void* d_nlt = new_last_targets;
+        int64_t ld_nlt = ld, ld_out = ld;
+        char *d_ctrl = (char*)controls_out, *d_states = (char*)states_out, *d_seq = (char*)sequences_out;
+        int32_t *d_iters = iters_out, *d_status = q->status;
+        char *d_rin = (char*)q->residual_in, *d_rout = (char*)q->residual_out;
+        if (host) {
+            const int64_t s_nlt = 0, s_ctrl = s_nlt + pad256((int64_t)steps * 2 * ldw * 8);
+            const int64_t s_states = s_ctrl + pad256((int64_t)steps * I * ldw * 8);
+            const int64_t s_iters = s_states + pad256((int64_t)steps * 2 * ldw * 8);
+            const int64_t s_seq = s_iters + pad256((int64_t)steps * ldw * 4);
+            const int64_t s_status = s_seq + (sequences_out ? pad256((int64_t)steps * H * I * ldw * 8) : 0);
+            const int64_t s_rin = s_status + (d_status ? pad256((int64_t)steps * ldw * 4) : 0);
+            const int64_t s_rout = s_rin + (d_rin ? pad256((int64_t)steps * ldw * 8) : 0);
+            const int64_t s_end = s_rout + (d_rout ? pad256((int64_t)steps * ldw * 8) : 0);
+            rc = ensure(h, &h->stage, &h->stage_bytes, s_end);
+            if (rc) return rc;
+            char* b = (char*)h->stage;
+            if (new_last_targets) {
+                HIP_TRY(h, copy_rows(b + s_nlt, ldw * 8, new_last_targets, ld * 8, n * 8, (int64_t)steps * 2,
+                                     hipMemcpyHostToDevice, s));
+                d_nlt = b + s_nlt;
+            }
+            ld_nlt = ld_out = ldw;
+            d_ctrl = b + s_ctrl;
+            d_states = states_out ? b + s_states : nullptr;
+            d_iters = iters_out ? (int32_t*)(b + s_iters) : nullptr;
+            d_seq = sequences_out ? b + s_seq : nullptr;
+            if (d_status) d_status = (int32_t*)(b + s_status);
+            if (d_rin) d_rin = b + s_rin;
+            if (d_rout) d_rout = b + s_rout;
+        }
+
+        bind(w, ldw);
+        a.r.ld_out = ld_out; a.r.ld_nlt = ld_nlt;
+        a.r.new_last_targets = d_nlt;
+        a.r.controls_out = d_ctrl; a.r.states_out = d_states; a.r.iters_out = d_iters; a.r.sequences_out = d_seq;
+        a.p.status = d_status; a.p.res_in = (double*)d_rin; a.p.res_out = (double*)d_rout;
+        a.first_unverified = d_fu;
+        a.fb_index = solve ? d_idx : nullptr;
+        a.fb_count = d_words;
+        hipError_t e = rollout_newton(I, a, h->grad_ws, d_words + 1, s);
+        if (e != hipSuccess) return hip_fail(h, e, "kernel launch");
+
+        uint32_t count = 0;
+        if (solve) {
+            HIP_TRY(h, hipMemcpyAsync(&count, d_words, sizeof(count), hipMemcpyDeviceToHost, s));
+            HIP_TRY(h, hipStreamSynchronize(s));
+        }
+        char* d_cfinal = w + (rows_in + 2 + 2 * H) * ldw * 8;   // the last step's sequence: controls out, and v out
+        char* d_vfinal = d_cfinal;
+        if (count > 0) {
+            // the compact batch, leading dimension ldc: the rows_in rows of the working set, new_last_targets, then
+            // every output of the polished loop
+            const int64_t cnt = count, ldc = (cnt + 63) / 64 * 64, S = steps;
+            int64_t r_total = rows_in;
+            auto take = [&](bool on, int64_t r) { const int64_t at = r_total; if (on) r_total += r; return on ? at : -1; };
+            const int64_t r_nlt = take(d_nlt != nullptr, S * 2), r_ctrl = take(true, S * I);
+            const int64_t r_states = take(d_states != nullptr, S * 2), r_seq = take(d_seq != nullptr, S * H * I);
+            const int64_t r_rin = take(d_rin != nullptr, S), r_rout = take(d_rout != nullptr, S);
+            const int64_t o_i32 = r_total * ldc * 8;   // int32 rows behind the fp64 ones: iters, status
+            rc = ensure(h, &h->newton_fb, &h->newton_fb_bytes, o_i32 + 2 * S * ldc * 4);
+            if (rc) return rc;
+            char* fb = (char*)h->newton_fb;
+            auto fat = [&](int64_t r) -> char* { return r < 0 ? nullptr : fb + r * ldc * 8; };
+            int32_t* f_iters = d_iters ? (int32_t*)(fb + o_i32) : nullptr;
+            int32_t* f_status = d_status ? (int32_t*)(fb + o_i32 + S * ldc * 4) : nullptr;
+
+            NewtonMove g;
+            std::memset(&g, 0, sizeof(g));
+            g.count = cnt; g.index = d_idx;
+            g.set[g.sets++] = NewtonRows{w, fb, rows_in, ldw, ldc, 8};
+            if (d_nlt) g.set[g.sets++] = NewtonRows{d_nlt, fat(r_nlt), S * 2, ld_nlt, ldc, 8};
+            e = rollout_newton_move(g, false, s);
+            if (e != hipSuccess) return hip_fail(h, e, "gather launch");
+
+            tpc_mpc_general_io io2;
+            std::memset(&io2, 0, sizeof(io2));
+            io2.inputs = I; io2.n = cnt; io2.ld = ldc;
+            io2.A = fat(row[0]); io2.B = fat(row[1]); io2.C = fat(row[2]); io2.Q = fat(row[3]); io2.R = fat(row[4]);
+            io2.lower = fat(row[5]); io2.upper = fat(row[6]); io2.x0 = fat(row[7]); io2.targets = fat(row[8]);
+            io2.controls_inout = fat(row[9]); io2.v_inout = fat(row[10]);
+            tpc_mpc_polish q2 = *q;
+            q2.status = f_status; q2.residual_in = fat(r_rin); q2.residual_out = fat(r_rout);
+            // its flags stay in the handle's word (no flags_out: no synchronisation); phase 1's are merged in below
+            rc = rollout_impl(h, p, &io2, steps, fat(r_nlt), fat(r_ctrl), fat(r_states), f_iters, fat(r_seq), false, true,
+                              &q2, nullptr, TPC_MPC_DEVICE, stream);
+            if (rc) return rc;
+
+            if (io->v_inout) {   // v out: the sequence for a Newton-only instance, the polished loop's v for the others
+                d_vfinal = w + row[10] * ldw * 8;
+                HIP_TRY(h, hipMemcpyAsync(d_vfinal, d_cfinal, (size_t)((int64_t)H * I * ldw * 8), hipMemcpyDeviceToDevice, s));
+            }
+            NewtonMove sc;
+            std::memset(&sc, 0, sizeof(sc));
+            sc.count = cnt; sc.index = d_idx;
+            sc.set[sc.sets++] = NewtonRows{fat(r_ctrl), d_ctrl, S * I, ldc, ld_out, 8};
+            if (d_states) sc.set[sc.sets++] = NewtonRows{fat(r_states), d_states, S * 2, ldc, ld_out, 8};
+            if (d_seq) sc.set[sc.sets++] = NewtonRows{fat(r_seq), d_seq, S * H * I, ldc, ld_out, 8};
+            if (d_rin) sc.set[sc.sets++] = NewtonRows{fat(r_rin), d_rin, S, ldc, ld_out, 8};
+            if (d_rout) sc.set[sc.sets++] = NewtonRows{fat(r_rout), d_rout, S, ldc, ld_out, 8};
+            if (d_iters) sc.set[sc.sets++] = NewtonRows{f_iters, d_iters, S, ldc, ld_out, 4};
+            if (d_status) sc.set[sc.sets++] = NewtonRows{f_status, d_status, S, ldc, ld_out, 4};
+            sc.set[sc.sets++] = NewtonRows{fat(row[9]), d_cfinal, (int64_t)H * I, ldc, ldw, 8};
+            if (io->v_inout) sc.set[sc.sets++] = NewtonRows{fat(row[10]), d_vfinal, (int64_t)H * I, ldc, ldw, 8};
+            e = rollout_newton_move(sc, true, s);
+            if (e != hipSuccess) return hip_fail(h, e, "scatter launch");
+        } else {
+            HIP_TRY(h, hipMemsetAsync(h->ws_words + 1, 0, sizeof(uint32_t), s));
+        }
+        e = rollout_newton_merge_flags(h->ws_words + 1, d_words + 1, s);
+        if (e != hipSuccess) return hip_fail(h, e, "flag merge launch");
+
+        // controller state and first_unverified back to the caller
+        if (io->controls_inout) HIP_TRY(h, copy_rows(io->controls_inout, ld * 8, d_cfinal, ldw * 8, n * 8, H * I, out_kind, s));
+        if (io->v_inout) HIP_TRY(h, copy_rows(io->v_inout, ld * 8, d_vfinal, ldw * 8, n * 8, H * I, out_kind, s));
+        if (first_unverified) HIP_TRY(h, hipMemcpyAsync(first_unverified, d_fu, (size_t)n * 4, out_kind, s));
+        if (host) {
+            HIP_TRY(h, copy_rows(controls_out, ld * 8, d_ctrl, ldw * 8, n * 8, (int64_t)steps * I, hipMemcpyDeviceToHost, s));
+            if (states_out)
+                HIP_TRY(h, copy_rows(states_out, ld * 8, d_states, ldw * 8, n * 8, (int64_t)steps * 2, hipMemcpyDeviceToHost, s));
+            if (iters_out)
+                HIP_TRY(h, copy_rows(iters_out, ld * 4, d_iters, ldw * 4, n * 4, steps, hipMemcpyDeviceToHost, s));
+            if (sequences_out)
+                HIP_TRY(h, copy_rows(sequences_out, ld * 8, d_seq, ldw * 8, n * 8, (int64_t)steps * H * I,
+                                     hipMemcpyDeviceToHost, s));
+            if (d_status)
+                HIP_TRY(h, copy_rows(q->status, ld * 4, d_status, ldw * 4, n * 4, steps, hipMemcpyDeviceToHost, s));
+            if (d_rin)
+                HIP_TRY(h, copy_rows(q->residual_in, ld * 8, d_rin, ldw * 8, n * 8, steps, hipMemcpyDeviceToHost, s));
+            if (d_rout)
+                HIP_TRY(h, copy_rows(q->residual_out, ld * 8, d_rout, ldw * 8, n * 8, steps, hipMemcpyDeviceToHost, s));
+            HIP_TRY(h, hipStreamSynchronize(s));
+        }
+        rc = order.end();
+        if (rc) return rc;
+        return finish_flags(h, flags_out, s);
+    });
 }
 
 int tpc_mpc_rollout_backward(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io, int32_t steps,

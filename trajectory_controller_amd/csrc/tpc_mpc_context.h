@@ -47,6 +47,12 @@ struct tpc_mpc_context {
     // per-step factors and states of tpc_mpc_solve_batch_general_backward (mpc_grad_model.h: [quantity][step][n])
     void* grad_ws = nullptr;
     int64_t grad_ws_bytes = 0;
+    // tpc_mpc_rollout_newton: the Newton pass's working set (model copy, the inputs as given, the carried state,
+    // first_unverified, the fallback's queue) and the compact batch of the fallback with its outputs
+    void* newton = nullptr;
+    int64_t newton_bytes = 0;
+    void* newton_fb = nullptr;
+    int64_t newton_fb_bytes = 0;
     // AUTO's presolve (tpc_mpc_api.cpp, presolve_begin): the instances predicted to end on the iteration cap are solved
     // bit-exactly on a stream of the handle's own BESIDE the tolerance family's pass: LANE scratch + side outputs, stream, events
     void* pre = nullptr;

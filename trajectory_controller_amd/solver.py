@@ -700,6 +700,83 @@ class MpcSolver:
         self.last_flags = flags.value
         return c_out, s_out, q_out, status, i_out
 
+    def rollout_newton(self, steps: int, A, B, Cc, Q, R, lower, upper, x0, targets, new_last_targets=None,
+                       controls=None, v_state=None, inputs: Optional[int] = None, tol: float = 1e-9,
+                       max_rounds: int = 8, fallback: str = "solve", want_status: bool = True,
+                       want_iters: bool = False, residuals=None, **over):
+        """The polished closed loop with the Newton rounds first (tpc_mpc_rollout_newton), fp64 only: every step is
+        polished from the shifted warm start without a first-order solve, all steps in one launch; an instance is
+        carried as long as the polish verifies.  fallback="solve": the instances that stopped are run from step 0
+        through rollout_polished's loop and written back; fallback="none": their rows from the stop on are status -1
+        and zeros, and last_flags carries FLAG_NOT_POLISHED (the only mode of a host-only solver, device=None).
+        Arguments and arrays as rollout_polished.  Returns rollout_polished's tuple plus first_unverified:
+        (controls[steps*I, n], states[steps*2, n], sequences[steps*H*I, n], status[steps, n] | None,
+        iters[steps, n] | None, first_unverified[n]) -- int32, the step phase 1 stopped at, `steps` for an instance
+        it carried to the end.  iters is 0 for the steps of such an instance."""
+        p = self._params(**over)
+        H = p.horizon
+        if _is_torch(A):
+            import torch
+            n = A.shape[-1]
+            I = inputs or R.shape[0]
+
+            def ptr(t, rows):
+                if t is None:
+                    return None
+                if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == (rows, n)):
+                    raise ValueError(f"expected contiguous fp64 CUDA tensor [{rows},{n}]")
+                return t.data_ptr()
+
+            def new(rows, dtype=np.float64):
+                return torch.empty((rows, n), dtype=torch.float64 if dtype is np.float64 else torch.int32,
+                                   device=A.device)
+            stream = C.c_void_p(torch.cuda.current_stream(A.device).cuda_stream)
+            mem = capi.DEVICE
+            optr = lambda t: None if t is None else t.data_ptr()
+        else:
+            A = np.ascontiguousarray(A, dtype=np.float64)
+            n = A.shape[-1]
+            I = inputs or np.asarray(R).shape[0]
+            keep = []
+
+            def ptr(a, rows):
+                if a is None:
+                    return None
+                if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and
+                        a.shape == (rows, n)):
+                    raise ValueError(f"expected C-contiguous fp64 ndarray [{rows},{n}]")
+                keep.append(a)
+                return a.ctypes.data
+            B, Cc, Q, R, lower, upper, x0, targets = (np.ascontiguousarray(a, dtype=np.float64) for a in
+                                                      (B, Cc, Q, R, lower, upper, x0, targets))
+            if new_last_targets is not None:
+                new_last_targets = np.ascontiguousarray(new_last_targets, dtype=np.float64)
+
+            def new(rows, dtype=np.float64):
+                return np.empty((rows, n), dtype=dtype)
+            stream = None
+            mem = capi.HOST
+            optr = lambda a: None if a is None else a.ctypes.data
+        c_out, s_out, q_out = new(steps * I), new(steps * 2), new(steps * H * I)
+        i_out = new(steps, np.int32) if want_iters else None
+        status = new(steps, np.int32) if want_status else None
+        first = new(1, np.int32)
+        io = capi.GeneralIO(inputs=I, n=n, ld=n, A=ptr(A, 4), B=ptr(B, 2 * I), C=ptr(Cc, 2), Q=ptr(Q, 2),
+                            R=ptr(R, I), lower=ptr(lower, I), upper=ptr(upper, I), x0=ptr(x0, 2),
+                            targets=ptr(targets, 2 * H), controls_inout=ptr(controls, H * I),
+                            v_inout=ptr(v_state, H * I), u0=None, iters=None)
+        rin, rout = residuals if residuals is not None else (None, None)
+        q = capi.Polish(tol=float(tol), max_rounds=int(max_rounds), reserved=0, status=optr(status),
+                        residual_in=ptr(rin, steps), residual_out=ptr(rout, steps))
+        flags = C.c_uint32(0)
+        self._check(self._lib.tpc_mpc_rollout_newton(self._h, C.byref(p), C.byref(io), int(steps),
+                                                     ptr(new_last_targets, 2 * steps), C.byref(q),
+                                                     capi.NEWTON_FALLBACKS[fallback], optr(c_out), optr(s_out),
+                                                     optr(i_out), optr(q_out), optr(first),
+                                                     C.byref(flags) if want_status else None, mem, stream))
+        self.last_flags = flags.value
+        return c_out, s_out, q_out, status, i_out, first[0]
+
     ROLLOUT_GRAD_NAMES = GRAD_NAMES[:-1] + ("new_last_targets", "kkt_residual")
 
     def rollout_backward(self, steps: int, A, B, Cc, Q, R, lower, upper, x0, targets, new_last_targets=None, *,
