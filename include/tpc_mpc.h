@@ -523,6 +523,75 @@ int tpc_mpc_rollout_backward(tpc_mpc_handle h, const tpc_mpc_params* p, const tp
                              int32_t steps, const void* new_last_targets, const tpc_mpc_rollout_grad* g,
                              uint32_t* flags_out, int mem, void* stream);
 
+/* K directions of tpc_mpc_solve_batch_general_forward / tpc_mpc_rollout_forward.  A direction is a tangent of every
+ * input: tA[4] tB[2*I] tC[2] tQ[2] tR[I] tlower[I] tupper[I] tx0[2] ttargets[H*2] tnew_last_targets[steps*2], each the
+ * tangent of the array of the same name and shape.  Every array is optional (NULL = zero) and holds the K directions as
+ * K stacked row blocks, SoA with the io's ld: element (d, c, k) of a C-component array is base[(d*C + c)*ld + k]. */
+typedef struct tpc_mpc_tangents {
+    int32_t directions, reserved;
+    const void *tA, *tB, *tC, *tQ, *tR, *tlower, *tupper, *tx0, *ttargets, *tnew_last_targets;
+} tpc_mpc_tangents;
+
+/* No reference counterpart.  Forward mode (Jacobian-vector products) of tpc_mpc_solve_batch_general: for n instances and
+ * K directions, the directional derivative tcontrols[K*H*I] of the controls u along each direction, given u.
+ *   Definition.  Notation and active set as tpc_mpc_solve_batch_general_backward: component (t, j) is ACTIVE iff
+ *   u <= lower_j || u >= upper_j, the u <= lower_j test first; F is the rest.  x_k below is io->x0 and tx_k is tx0.
+ *     ub(t,j)  = tlower_j / tupper_j on an active component (by the bound it sits on), 0 on F
+ *     forward  t = 0..H-1 : x_{t+1}  = A x_t + B u_t + C                            (x_0 = x_k)
+ *                           tx_{t+1} = tA x_t + A tx_t + tB u_t + B ub_t + tC       (tx_0 = tx_k)
+ *     backward t = H-1..0 : e   = x_{t+1} - T[t]
+ *                           p_t  = A' p_{t+1} + Q e
+ *                           tp_t = tA' p_{t+1} + A' tp_{t+1} + tQ e + Q (tx_{t+1} - tT[t])
+ *                           r_t  = tB' p_t + B' tp_t + tR u_t + R ub_t
+ *                           masked Riccati step with g = r_t, F as above (the arithmetic of the backward pass)
+ *     tU = ub - w,  w = H_FF^-1 r_F (w = 0 off F)
+ *   r is the directional derivative of dlib's df = H u + MM along (the direction, ub), taken at u, so tU is the
+ *   derivative of the map tpc_mpc_solve_batch_general_backward differentiates, and the linear map direction -> tU is,
+ *   operation by operation, the transpose of what that entry computes:  sum G . tU = sum_theta <dL/dtheta, ttheta> for
+ *   every G = dL/du, to rounding.  When u is the optimum it is the derivative of the optimum.
+ *   Method.  One lane per (direction, instance) pair, lane L = direction L / n of instance L % n, all K directions in
+ *   one launch (csrc/mpc_tangent_model.h): a forward pass, the fused costate / Riccati pass, and the forward pass that
+ *   turns gains into w.  The per-step quantities live in device scratch of the handle.
+ * controls [H*I] (required) is u; t (required) the directions, 1 <= t->directions and directions * n < 2^31
+ * (TPC_MPC_ERR_BAD_ARG otherwise); t->tnew_last_targets is ignored.  tcontrols (required): element (d, c, k) at
+ * tcontrols[(d*H*I + c)*ld + k].  io, p: as for tpc_mpc_solve_batch_general_backward; fp64 only, horizons 1..64, one or
+ * two inputs.  An instance with non-finite data or controls, or tangents in direction d (the bounds' tangents must be
+ * finite; the bounds may be infinite), raises TPC_MPC_FLAG_NONFINITE, a model that breaks dlib's requires clause
+ * TPC_MPC_FLAG_BAD_MODEL; that (d, k) pair gets an all-zero block.  n == 0 returns TPC_MPC_OK with flags 0.  Memory,
+ * stream, flags and the host-only handle as tpc_mpc_solve_batch_general_backward. */
+int tpc_mpc_solve_batch_general_forward(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io,
+                                        const void* controls, const tpc_mpc_tangents* t, void* tcontrols,
+                                        uint32_t* flags_out, int mem, void* stream);
+
+/* No reference counterpart.  Forward mode of tpc_mpc_rollout: for n instances and K directions, the directional
+ * derivatives of (controls_out, states_out) of the closed loop, taken at the recorded sequences and states.  With few
+ * parameters and many outputs (a Jacobian for Gauss-Newton / Levenberg-Marquardt, a sensitivity study) it replaces one
+ * tpc_mpc_rollout_backward call per output by one direction per parameter, all of them in one launch.
+ *   Definition.  Notation as tpc_mpc_rollout_backward: step k solves from x_k (io->x0 for k = 0, states[k-1] after) with
+ *   the shifted targets T_k and has the recorded sequence U_k; tT_k[t] comes from ttargets / tnew_last_targets through
+ *   the same map as T_k.  The tangent of step k is the step of tpc_mpc_solve_batch_general_forward at (x_k, tx_k, T_k,
+ *   tT_k, U_k); only its row 0 feeds the plant:
+ *     tu0_k    = ub_0 - k_0          the Riccati response starts at dx_0 = 0, so w_0 is the sweep's feed-forward k_0 at
+ *                                    t = 0: one forward and one fused backward pass per step, no stored gains
+ *     tx_{k+1} = tA x_k + A tx_k + tB u0_k + B tu0_k + tC                     (tx_0 = tx0)
+ *     tcontrols[k] = tu0_k,  tstates[k] = tx_{k+1}
+ *   The map direction -> (tcontrols, tstates) is, operation by operation, the transpose of tpc_mpc_rollout_backward:
+ *   sum G_u . tcontrols + sum G_x . tstates = sum_theta <dL/dtheta, ttheta>, to rounding.  When every U_k is the optimum
+ *   (tpc_mpc_rollout_polished, tpc_mpc_rollout_newton) it is the derivative of the closed loop; the warm start gets no
+ *   tangent, as it gets no gradient.
+ *   Method.  One lane per (direction, instance) pair as in tpc_mpc_solve_batch_general_forward, every step and every
+ *   direction in one launch (csrc/mpc_rollout_tangent.hip); tx_k stays in registers from step to step.
+ * io, p, steps, new_last_targets, sequences [steps*H*I] and states [steps*2] (both required): as for
+ * tpc_mpc_rollout_backward.  t (required): 1 <= t->directions, directions * n < 2^31; tnew_last_targets without
+ * new_last_targets is TPC_MPC_ERR_BAD_ARG.  tcontrols (required): element (d, c, k) at tcontrols[(d*steps*I + c)*ld + k];
+ * tstates (optional): [(d*steps*2 + c)*ld + k].  fp64 only, horizons 1..64, one or two inputs.  n == 0 or steps == 0
+ * returns TPC_MPC_OK with flags 0.  Flags, zeroed (d, k) blocks, memory, stream and the host-only handle as
+ * tpc_mpc_solve_batch_general_forward (non-finite sequences or states count as non-finite data). */
+int tpc_mpc_rollout_forward(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io, int32_t steps,
+                            const void* new_last_targets, const void* sequences, const void* states,
+                            const tpc_mpc_tangents* t, void* tcontrols, void* tstates, uint32_t* flags_out, int mem,
+                            void* stream);
+
 /* ---- batched cycle(): raw trajectories in, CarCommand fields out -------------------------------- */
 
 /* Polylines of n instances, SoA: point i of instance k at base[i*ld + k] (float), `count[k]` points

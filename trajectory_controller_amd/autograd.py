@@ -10,6 +10,10 @@ default eps 0.01 leaves a loose solution, so either pass polish=True (solve at e
 tpc_mpc_polish_batch_general onto the verified optimum -- the cheap way) or a small eps (e.g. eps=1e-10).  Inputs are CUDA fp64
 tensors; both functions are once-differentiable.  Instances whose data are non-finite or break dlib's requires clause
 get zero gradients.
+
+Forward mode (torch.autograd.forward_ad) works on all three functions: the jvp of mpc_general / mpc_compact is
+tpc_mpc_solve_batch_general_forward, that of mpc_rollout tpc_mpc_rollout_forward, one direction per dual level, at
+the same sequences the backward is taken at.  torch.func transforms are not supported.
 """
 from __future__ import annotations
 
@@ -35,7 +39,18 @@ class _MpcGeneral(torch.autograd.Function):
             solver.polish_batch_general(*ins, controls, tol=tol, max_rounds=rounds, want_status=False, inputs=I, **keys)
         ctx.solver, ctx.over, ctx.I = solver, over, I
         ctx.save_for_backward(*ins, controls)
+        ctx.save_for_forward(*ins, controls)
         return controls
+
+    @staticmethod
+    def jvp(ctx, _solver, _over, _polish, *tangents):
+        *ins, controls = ctx.saved_tensors
+        names = ("A", "B", "C", "Q", "R", "lower", "upper", "x0", "targets")
+        tan = {k: t.contiguous() for k, t in zip(names, tangents) if t is not None}
+        if not tan:
+            return torch.zeros_like(controls)
+        return ctx.solver.solve_batch_general_forward(*ins, controls, tan, inputs=ctx.I, want_flags=False,
+                                                      **ctx.over)[0]
 
     @staticmethod
     @once_differentiable
@@ -79,7 +94,22 @@ class _MpcRollout(torch.autograd.Function):
         ctx.solver, ctx.steps, ctx.over, ctx.I = solver, steps, over, I
         ctx.has_nlt = nlt is not None
         ctx.save_for_backward(*ins, *(() if nlt is None else (nlt,)), states, sequences)
+        ctx.save_for_forward(*ins, *(() if nlt is None else (nlt,)), states, sequences, controls)
         return controls, states
+
+    @staticmethod
+    def jvp(ctx, _solver, _steps, _over, _polish, *tangents):
+        saved = list(ctx.saved_tensors)
+        ins, rest = saved[:9], saved[9:]
+        nlt = rest.pop(0) if ctx.has_nlt else None
+        states, sequences, controls = rest
+        names = ("A", "B", "C", "Q", "R", "lower", "upper", "x0", "targets", "new_last_targets")
+        tan = {k: t.contiguous() for k, t in zip(names, tangents) if t is not None}
+        if not tan:
+            return torch.zeros_like(controls), torch.zeros_like(states)
+        tu, tx = ctx.solver.rollout_forward(ctx.steps, *ins, nlt, sequences=sequences, states=states, tangents=tan,
+                                            inputs=ctx.I, want_flags=False, **ctx.over)
+        return tu[0], tx[0]
 
     @staticmethod
     @once_differentiable

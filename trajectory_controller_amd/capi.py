@@ -42,7 +42,8 @@ EXPORTS = ("tpc_mpc_default_params", "tpc_mpc_create", "tpc_mpc_destroy", "tpc_m
            "tpc_mpc_solve_batch_general_sharded", "tpc_mpc_last_flags", "tpc_mpc_gather_shards",
            "tpc_mpc_shard_map", "tpc_mpc_solve_batch_compact_sharded_split", "tpc_mpc_gather_shards_split",
            "tpc_mpc_solve_batch_general_backward", "tpc_mpc_rollout_record", "tpc_mpc_rollout_backward",
-           "tpc_mpc_polish_batch_general", "tpc_mpc_rollout_polished", "tpc_mpc_rollout_newton")
+           "tpc_mpc_polish_batch_general", "tpc_mpc_rollout_polished", "tpc_mpc_rollout_newton",
+           "tpc_mpc_solve_batch_general_forward", "tpc_mpc_rollout_forward")
 SPLIT_BLOCK, SPLIT_INTERLEAVED = 0, 1
 SPLITS = {"block": SPLIT_BLOCK, "interleaved": SPLIT_INTERLEAVED}
 
@@ -86,6 +87,14 @@ class RolloutGrad(C.Structure):
                 ("dQ", C.c_void_p), ("dR", C.c_void_p), ("dlower", C.c_void_p), ("dupper", C.c_void_p),
                 ("dx0", C.c_void_p), ("dtargets", C.c_void_p), ("dnew_last_targets", C.c_void_p),
                 ("kkt_residual", C.c_void_p)]
+
+
+class Tangents(C.Structure):
+    """struct tpc_mpc_tangents"""
+    _fields_ = [("directions", C.c_int32), ("reserved", C.c_int32), ("tA", C.c_void_p), ("tB", C.c_void_p),
+                ("tC", C.c_void_p), ("tQ", C.c_void_p), ("tR", C.c_void_p), ("tlower", C.c_void_p),
+                ("tupper", C.c_void_p), ("tx0", C.c_void_p), ("ttargets", C.c_void_p),
+                ("tnew_last_targets", C.c_void_p)]
 
 
 class Trajectories(C.Structure):
@@ -155,6 +164,10 @@ def load_library(path: str | None = None) -> C.CDLL:
                                            C.POINTER(Polish), C.c_int32, vp, vp, vp, vp, vp, u32p, C.c_int, vp]
     lib.tpc_mpc_rollout_backward.argtypes = [vp, C.POINTER(Params), C.POINTER(GeneralIO), C.c_int32, vp,
                                              C.POINTER(RolloutGrad), u32p, C.c_int, vp]
+    lib.tpc_mpc_solve_batch_general_forward.argtypes = [vp, C.POINTER(Params), C.POINTER(GeneralIO), vp,
+                                                        C.POINTER(Tangents), vp, u32p, C.c_int, vp]
+    lib.tpc_mpc_rollout_forward.argtypes = [vp, C.POINTER(Params), C.POINTER(GeneralIO), C.c_int32, vp, vp, vp,
+                                            C.POINTER(Tangents), vp, vp, u32p, C.c_int, vp]
     lib.tpc_mpc_set_profiling.argtypes = [vp, C.c_int]
     lib.tpc_mpc_last_kernel_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                               C.POINTER(C.c_int)]

@@ -9,6 +9,7 @@
 #include "mpc_grad_model.h"
 #include "mpc_polish_model.h"
 #include "mpc_rollout_newton.h"
+#include "mpc_tangent_model.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -58,6 +59,14 @@ uint32_t polish_general_host(int I, int H, const polish::Args& a);
 // ... and fused with the rollout's step tail (mpc_rollout_polish.hip): one step of tpc_mpc_rollout_polished
 hipError_t launch_rollout_polish_step(int I, const polish::Args& p, const RolloutStepArgs& r, void* ws, uint32_t* flags,
                                       hipStream_t s);
+
+// the forward-mode derivatives (mpc_tangent.hip, mpc_rollout_tangent.hip): one lane per (direction, instance), the
+// per-step workspace of K * n lanes inside the gradient workspace
+int64_t tangent_scratch_bytes(int I, int H, int64_t n, int K, bool whole);
+hipError_t tangent_general(int I, int H, const tangent::Args& a, void* ws, uint32_t* flags, hipStream_t s);
+uint32_t tangent_general_host(int I, int H, const tangent::Args& a);
+hipError_t rollout_tangent(int I, int H, const tangent::RollArgs& a, void* ws, uint32_t* flags, hipStream_t s);
+uint32_t rollout_tangent_host(int I, int H, const tangent::RollArgs& a);
 
 thread_local char g_create_error[kTpcErrLen] = "";
 }  // namespace tpc
@@ -793,6 +802,82 @@ int compact_launch(tpc_mpc_context* h, const tpc_mpc_params* p, int64_t n, const
 }
 
 }  // namespace tpc
+
+namespace {
+
+// What the two forward-mode entries share after their argument checks: nin input arrays (a null one is not staged) of
+// rows[c] component rows and nout output arrays of rows[nin + c], run by `run(ld, in, out, s, host_flags)` -- on the
+// calling thread for a host-only handle (host_flags != null), else as a launch on s after HOST arrays were staged with
+// the leading dimension lds.  Staging, stream and flag behaviour are tpc_mpc_rollout_backward's.
+template <class Run>
+int forward_run(tpc_mpc_context* h, const tpc_mpc_general_io* io, int mem, void* stream, uint32_t* flags_out,
+                int64_t ws_bytes, const void* const* src, void* const* dst, const int64_t* rows, int nin, int nout,
+                Run run) {
+    const int64_t n = io->n;
+    if (h->host_only) {   // on the calling thread, straight from and into the caller's arrays
+        uint32_t f = 0;
+        (void)run(io->ld, src, dst, (hipStream_t) nullptr, &f);
+        if (flags_out) *flags_out = f;
+        return TPC_MPC_OK;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    StreamOrderScope order(h, s);
+    int rc = order.begin();
+    if (rc) return rc;
+    rc = ensure(h, &h->grad_ws, &h->grad_ws_bytes, pad256(ws_bytes));
+    if (rc) return rc;
+    const int64_t lds = (n + 63) / 64 * 64;
+    std::vector<int64_t> off(nin + nout, 0);
+    std::vector<const void*> sin(src, src + nin);
+    std::vector<void*> sout(dst, dst + nout);
+    int64_t ld = io->ld;
+    if (mem == TPC_MPC_HOST) {
+        // HOST arrays: every component row copied on its own (n elements, never ld); only the arrays given are staged
+        int64_t total = 0;
+        for (int c = 0; c < nin + nout; ++c) {
+            const bool given = c < nin ? src[c] != nullptr : dst[c - nin] != nullptr;
+            off[c] = total;
+            if (given) total += pad256(rows[c] * lds * 8);
+        }
+        rc = ensure(h, &h->stage, &h->stage_bytes, total);
+        if (rc) return rc;
+        char* b = (char*)h->stage;
+        for (int c = 0; c < nin; ++c) {
+            sin[c] = src[c] ? b + off[c] : nullptr;
+            if (src[c])
+                HIP_TRY(h, copy_rows(b + off[c], lds * 8, src[c], io->ld * 8, n * 8, rows[c], hipMemcpyHostToDevice, s));
+        }
+        for (int c = 0; c < nout; ++c) sout[c] = dst[c] ? b + off[nin + c] : nullptr;
+        ld = lds;
+    }
+    HIP_TRY(h, hipMemsetAsync(h->ws_words + 1, 0, sizeof(uint32_t), s));
+    hipError_t e = run(ld, sin.data(), sout.data(), s, (uint32_t*)nullptr);
+    if (e != hipSuccess) return hip_fail(h, e, "kernel launch");
+    if (mem == TPC_MPC_HOST) {
+        const char* b = (const char*)h->stage;
+        for (int c = 0; c < nout; ++c)
+            if (dst[c])
+                HIP_TRY(h, copy_rows(dst[c], io->ld * 8, b + off[nin + c], lds * 8, n * 8, rows[nin + c],
+                                     hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+    }
+    rc = order.end();
+    if (rc) return rc;
+    return finish_flags(h, flags_out, s);
+}
+
+// the ten tangent arrays of a tpc_mpc_tangents in Dirs' order, from in[0..9]
+tangent::Dirs bind_dirs(const void* const* in) {
+    tangent::Dirs d;
+    d.tA = (const double*)in[0]; d.tB = (const double*)in[1]; d.tC = (const double*)in[2];
+    d.tQ = (const double*)in[3]; d.tR = (const double*)in[4]; d.tlo = (const double*)in[5];
+    d.thi = (const double*)in[6]; d.tx0 = (const double*)in[7]; d.ttargets = (const double*)in[8];
+    d.tnlt = (const double*)in[9];
+    return d;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -1831,6 +1916,103 @@ int tpc_mpc_rollout_backward(tpc_mpc_handle h, const tpc_mpc_params* p, const tp
         rc = order.end();
         if (rc) return rc;
         return finish_flags(h, flags_out, s);
+    });
+}
+
+int tpc_mpc_solve_batch_general_forward(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io,
+                                        const void* controls, const tpc_mpc_tangents* t, void* tcontrols,
+                                        uint32_t* flags_out, int mem, void* stream) {
+    return guarded(h, [&]() -> int {
+        int rc = check_common(h, p, true);
+        if (rc) return rc;
+        if (p->dtype != TPC_MPC_F64)
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "tpc_mpc_solve_batch_general_forward is fp64 only: p->dtype must be TPC_MPC_F64");
+        rc = check_general_io(h, io, mem);
+        if (rc) return rc;
+        if (!t) return fail(h, TPC_MPC_ERR_BAD_ARG, "null tangent struct");
+        if (t->directions < 1 || (int64_t)t->directions * io->n > 0x7fffffffll)
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "need directions >= 1 and directions * n < 2^31");
+        if (h->host_only && mem == TPC_MPC_DEVICE)
+            return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): the forward pass takes HOST memory only");
+        if (io->n == 0) { if (flags_out) *flags_out = 0; return TPC_MPC_OK; }
+        if (!io->A || !io->B || !io->C || !io->Q || !io->R || !io->lower || !io->upper || !io->x0 || !io->targets)
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "null batch pointer");
+        if (!controls || !tcontrols) return fail(h, TPC_MPC_ERR_BAD_ARG, "null controls / tcontrols");
+        const int I = io->inputs, H = p->horizon, K = t->directions;
+        const int64_t n = io->n;
+        // ten primal inputs, ten tangents (K stacked blocks each; tnew_last_targets is not used here), one output
+        const void* src[20] = {io->A, io->B, io->C, io->Q, io->R, io->lower, io->upper, io->x0, io->targets, controls,
+                               t->tA, t->tB, t->tC, t->tQ, t->tR, t->tlower, t->tupper, t->tx0, t->ttargets, nullptr};
+        void* dst[1] = {tcontrols};
+        const int64_t rows[21] = {4, 2 * I, 2, 2, I, I, I, 2, 2 * H, H * I,
+                                  4 * K, 2 * I * K, 2 * K, 2 * K, I * K, I * K, I * K, 2 * K, 2 * H * K, 0,
+                                  (int64_t)H * I * K};
+        return forward_run(h, io, mem, stream, flags_out, tangent_scratch_bytes(I, H, n, K, true), src, dst, rows, 20, 1,
+                           [&](int64_t ld, const void* const* in, void* const* out, hipStream_t s, uint32_t* hf) {
+                               tangent::Args a;
+                               std::memset(&a, 0, sizeof(a));
+                               a.n = n; a.ld = ld; a.K = K;
+                               a.A = (const double*)in[0]; a.B = (const double*)in[1]; a.C = (const double*)in[2];
+                               a.Q = (const double*)in[3]; a.R = (const double*)in[4]; a.lo = (const double*)in[5];
+                               a.hi = (const double*)in[6]; a.x0 = (const double*)in[7];
+                               a.targets = (const double*)in[8]; a.u = (const double*)in[9];
+                               a.t = bind_dirs(in + 10);
+                               a.tu = (double*)out[0];
+                               if (hf) { *hf = tangent_general_host(I, H, a); return hipSuccess; }
+                               return tangent_general(I, H, a, h->grad_ws, h->ws_words + 1, s);
+                           });
+    });
+}
+
+int tpc_mpc_rollout_forward(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io, int32_t steps,
+                            const void* new_last_targets, const void* sequences, const void* states,
+                            const tpc_mpc_tangents* t, void* tcontrols, void* tstates, uint32_t* flags_out, int mem,
+                            void* stream) {
+    return guarded(h, [&]() -> int {
+        int rc = check_common(h, p, true);
+        if (rc) return rc;
+        if (p->dtype != TPC_MPC_F64)
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "tpc_mpc_rollout_forward is fp64 only: p->dtype must be TPC_MPC_F64");
+        rc = check_general_io(h, io, mem);
+        if (rc) return rc;
+        if (!t) return fail(h, TPC_MPC_ERR_BAD_ARG, "null tangent struct");
+        if (steps < 0 || steps > (1 << 24)) return fail(h, TPC_MPC_ERR_BAD_ARG, "need 0 <= steps <= 2^24");
+        if (t->directions < 1 || (int64_t)t->directions * io->n > 0x7fffffffll)
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "need directions >= 1 and directions * n < 2^31");
+        if (t->tnew_last_targets && !new_last_targets)
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "tnew_last_targets given without new_last_targets");
+        if (h->host_only && mem == TPC_MPC_DEVICE)
+            return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): the forward pass takes HOST memory only");
+        if (io->n == 0 || steps == 0) { if (flags_out) *flags_out = 0; return TPC_MPC_OK; }
+        if (!io->A || !io->B || !io->C || !io->Q || !io->R || !io->lower || !io->upper || !io->x0 || !io->targets)
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "null batch pointer");
+        if (!sequences || !states || !tcontrols) return fail(h, TPC_MPC_ERR_BAD_ARG, "null sequences / states / tcontrols");
+        const int I = io->inputs, H = p->horizon, K = t->directions;
+        const int64_t n = io->n, S = steps;
+        // twelve primal inputs (new_last_targets may be null), ten tangents (K stacked blocks each), two outputs
+        const void* src[22] = {io->A, io->B, io->C, io->Q, io->R, io->lower, io->upper, io->x0, io->targets,
+                               new_last_targets, sequences, states,
+                               t->tA, t->tB, t->tC, t->tQ, t->tR, t->tlower, t->tupper, t->tx0, t->ttargets,
+                               t->tnew_last_targets};
+        void* dst[2] = {tcontrols, tstates};
+        const int64_t rows[24] = {4, 2 * I, 2, 2, I, I, I, 2, 2 * H, 2 * S, S * H * I, 2 * S,
+                                  4 * K, 2 * I * K, 2 * K, 2 * K, I * K, I * K, I * K, 2 * K, 2 * H * K, 2 * S * K,
+                                  S * I * K, 2 * S * K};
+        return forward_run(h, io, mem, stream, flags_out, tangent_scratch_bytes(I, H, n, K, false), src, dst, rows, 22, 2,
+                           [&](int64_t ld, const void* const* in, void* const* out, hipStream_t s, uint32_t* hf) {
+                               tangent::RollArgs a;
+                               std::memset(&a, 0, sizeof(a));
+                               a.n = n; a.ld = ld; a.steps = steps; a.K = K;
+                               a.A = (const double*)in[0]; a.B = (const double*)in[1]; a.C = (const double*)in[2];
+                               a.Q = (const double*)in[3]; a.R = (const double*)in[4]; a.lo = (const double*)in[5];
+                               a.hi = (const double*)in[6]; a.x0 = (const double*)in[7];
+                               a.targets = (const double*)in[8]; a.nlt = (const double*)in[9];
+                               a.seq = (const double*)in[10]; a.states = (const double*)in[11];
+                               a.t = bind_dirs(in + 12);
+                               a.tu = (double*)out[0]; a.tx = (double*)out[1];
+                               if (hf) { *hf = rollout_tangent_host(I, H, a); return hipSuccess; }
+                               return rollout_tangent(I, H, a, h->grad_ws, h->ws_words + 1, s);
+                           });
     });
 }
 

@@ -857,6 +857,119 @@ class MpcSolver:
             out["kkt_residual"] = out["kkt_residual"].reshape(n)
         return out
 
+    TANGENT_NAMES = ("A", "B", "C", "Q", "R", "lower", "upper", "x0", "targets", "new_last_targets")
+
+    def _forward_setup(self, A, R, inputs, tangents, rows):
+        """What the two forward-mode calls share: (n, I, K, ptr, new, stream, mem, Tangents factory).  `tangents` maps
+        names of TANGENT_NAMES to arrays [K, c, n] (2-D [c, n]: K = 1); rows(I) gives c per name."""
+        unknown = set(tangents) - set(self.TANGENT_NAMES)
+        if unknown:
+            raise ValueError(f"unknown tangent names {sorted(unknown)}")
+        tangents = {k: v for k, v in tangents.items() if v is not None}
+        if not tangents:
+            raise ValueError("tangents is empty: give at least one direction array")
+        K = None
+        for name, v in tangents.items():
+            k = 1 if v.ndim == 2 else v.shape[0] if v.ndim == 3 else None
+            if k is None or (K is not None and k != K):
+                raise ValueError(f"tangent {name!r}: expected [K, c, n] (or [c, n] for K = 1) with one K for all")
+            K = k
+        if _is_torch(A):
+            import torch
+            n = A.shape[-1]
+            I = inputs or R.shape[0]
+
+            def ptr(t, r):
+                if t is None:
+                    return None
+                if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == r * n
+                        and t.shape[-1] == n):
+                    raise ValueError(f"expected contiguous fp64 CUDA tensor [{r},{n}]")
+                return t.data_ptr()
+
+            def new(*shape):
+                return torch.empty(shape + (n,), dtype=torch.float64, device=A.device)
+            stream = C.c_void_p(torch.cuda.current_stream(A.device).cuda_stream)
+            mem = capi.DEVICE
+            optr = lambda t: None if t is None else t.data_ptr()
+        else:
+            n = np.asarray(A).shape[-1]
+            I = inputs or np.asarray(R).shape[0]
+            keep = []
+
+            def ptr(a, r):
+                if a is None:
+                    return None
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.size != r * n or a.shape[-1] != n:
+                    raise ValueError(f"expected an array [{r},{n}]")
+                keep.append(a)
+                return a.ctypes.data
+
+            def new(*shape):
+                return np.empty(shape + (n,), dtype=np.float64)
+            stream = None
+            mem = capi.HOST
+            optr = lambda a: None if a is None else a.ctypes.data
+        c = rows(I)
+        fields = {("t" + name): ptr(tangents.get(name), K * c[name]) for name in self.TANGENT_NAMES}
+        tan = capi.Tangents(directions=K, reserved=0, **fields)
+        return n, I, K, ptr, new, optr, stream, mem, tan
+
+    def solve_batch_general_forward(self, A, B, Cc, Q, R, lower, upper, x0, targets, controls, tangents,
+                                    inputs: Optional[int] = None, want_flags: bool = True, **over):
+        """Forward mode of solve_batch_general (tpc_mpc_solve_batch_general_forward), fp64 only: the directional
+        derivatives of the controls along K directions, taken at `controls` [H*I, n].  `tangents` maps the names "A",
+        "B", "C", "Q", "R", "lower", "upper", "x0", "targets" to arrays [K, c, n] (c the rows of that input; a 2-D
+        [c, n] array means K = 1; a missing name is a zero tangent).  Arrays as in solve_batch_general_backward (numpy:
+        HOST memory, CUDA torch tensors: DEVICE memory on the current stream).  Returns tcontrols [K, H*I, n]; a
+        flagged (direction, instance) pair gets zeros (last_flags)."""
+        p = self._params(**over)
+        H = p.horizon
+        if "new_last_targets" in tangents:
+            raise ValueError("the single solve has no new_last_targets")
+        n, I, K, ptr, new, optr, stream, mem, tan = self._forward_setup(
+            A, R, inputs, tangents, lambda I: {"A": 4, "B": 2 * I, "C": 2, "Q": 2, "R": I, "lower": I, "upper": I,
+                                               "x0": 2, "targets": 2 * H, "new_last_targets": 0})
+        io = capi.GeneralIO(inputs=I, n=n, ld=n, A=ptr(A, 4), B=ptr(B, 2 * I), C=ptr(Cc, 2), Q=ptr(Q, 2),
+                            R=ptr(R, I), lower=ptr(lower, I), upper=ptr(upper, I), x0=ptr(x0, 2),
+                            targets=ptr(targets, 2 * H), controls_inout=None, v_inout=None, u0=None, iters=None)
+        tu = new(K, H * I)
+        flags = C.c_uint32(0)
+        self._check(self._lib.tpc_mpc_solve_batch_general_forward(self._h, C.byref(p), C.byref(io),
+                                                                  ptr(controls, H * I), C.byref(tan), optr(tu),
+                                                                  C.byref(flags) if want_flags else None, mem, stream))
+        self.last_flags = flags.value
+        return tu
+
+    def rollout_forward(self, steps: int, A, B, Cc, Q, R, lower, upper, x0, targets, new_last_targets=None, *,
+                        sequences, states, tangents, inputs: Optional[int] = None, want_states: bool = True,
+                        want_flags: bool = True, **over):
+        """Forward mode of rollout (tpc_mpc_rollout_forward), fp64 only: the directional derivatives of the rollout's
+        controls and states along K directions, taken at what rollout_record / rollout_polished / rollout_newton
+        returned (`sequences` [steps*H*I, n], `states` [steps*2, n]); all K directions and all steps run in one
+        launch.  `tangents`: as in solve_batch_general_forward, plus "new_last_targets" [K, steps*2, n] (only with
+        new_last_targets).  Returns (tcontrols [K, steps*I, n], tstates [K, steps*2, n] | None); a flagged (direction,
+        instance) pair gets zeros (last_flags; want_flags=False keeps a DEVICE call asynchronous)."""
+        p = self._params(**over)
+        H = p.horizon
+        n, I, K, ptr, new, optr, stream, mem, tan = self._forward_setup(
+            A, R, inputs, tangents, lambda I: {"A": 4, "B": 2 * I, "C": 2, "Q": 2, "R": I, "lower": I, "upper": I,
+                                               "x0": 2, "targets": 2 * H, "new_last_targets": 2 * steps})
+        io = capi.GeneralIO(inputs=I, n=n, ld=n, A=ptr(A, 4), B=ptr(B, 2 * I), C=ptr(Cc, 2), Q=ptr(Q, 2),
+                            R=ptr(R, I), lower=ptr(lower, I), upper=ptr(upper, I), x0=ptr(x0, 2),
+                            targets=ptr(targets, 2 * H), controls_inout=None, v_inout=None, u0=None, iters=None)
+        tu = new(K, steps * I)
+        tx = new(K, steps * 2) if want_states else None
+        flags = C.c_uint32(0)
+        self._check(self._lib.tpc_mpc_rollout_forward(self._h, C.byref(p), C.byref(io), int(steps),
+                                                      ptr(new_last_targets, 2 * steps),
+                                                      ptr(sequences, steps * H * I), ptr(states, 2 * steps),
+                                                      C.byref(tan), optr(tu), optr(tx),
+                                                      C.byref(flags) if want_flags else None, mem, stream))
+        self.last_flags = flags.value
+        return tu, tx
+
     def follow_batch(self, pos_x, pos_y, dir_x, dir_y, velocity, count, car_velocity, look_ahead,
                      lookup=None, want_iters: bool = False, **over):
         """Batched tobiMPC branch of cycle() on raw trajectories (device tensors).
