@@ -592,6 +592,78 @@ int tpc_mpc_rollout_forward(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc
                             const tpc_mpc_tangents* t, void* tcontrols, void* tstates, uint32_t* flags_out, int mem,
                             void* stream);
 
+/* ---- closed loops against a separate plant ------------------------------------------------------ */
+
+/* The closed loops above move the state with the controller's own model.  A plant is what moves it instead: three
+ * optional arrays and an optional disturbance, nothing else.  Every pointer null is the controller's model and no
+ * disturbance: the parent loop, bit for bit, signed zeros included. */
+typedef struct tpc_mpc_plant {
+    const void *A, *B, *C;      /* [4] [2*I] [2], SoA with the io's ld; all three or none (none = the controller's) */
+    const void *disturbance;    /* optional, [steps*2], SoA with leading dimension ld_d; row k is added to x_{k+1}   */
+    int64_t ld_d;
+} tpc_mpc_plant;
+
+#define TPC_MPC_LOOP_RECORD 0     /* tpc_mpc_rollout_record   */
+#define TPC_MPC_LOOP_POLISHED 1   /* tpc_mpc_rollout_polished */
+#define TPC_MPC_LOOP_NEWTON 2     /* tpc_mpc_rollout_newton   */
+/* The closed loop `loop` against a separate plant, fp64 only.
+ *   Definition.  Step k is the named parent's step -- the solve / polish / Newton rounds at x_k with the controller's
+ *   A, B, C, Q, R, bounds and T_k -- except its last line, which becomes
+ *     x_{k+1} = ((Ap x_k + Bp u0_k) + Cp) (+ d_k)
+ *   in the step tail's arithmetic, operation for operation (no fused multiply-add, the same association); the
+ *   disturbance's row k is one more plain add at the end, and no add at all when plant->disturbance is null.
+ * plant (required; its A, B, C all given or all null, one or two of them is TPC_MPC_ERR_BAD_ARG): any finite Ap, Bp,
+ * Cp, d is allowed, there is no requires clause.  TPC_MPC_LOOP_NEWTON: an instance with a non-finite plant or
+ * disturbance value raises TPC_MPC_FLAG_NONFINITE and is left as tpc_mpc_rollout_newton leaves an instance with a
+ * non-finite model (first_unverified 0, status -1 and zeros from step 0, not handed to the fallback).  The solve-based
+ * loops carry such a value into x_{k+1}, where the next step's solve raises the flag as for a non-finite x0.
+ * Arguments the chosen loop does not have are ignored (q, fallback, first_unverified for _RECORD; fallback,
+ * first_unverified for _POLISHED); every other argument and check is the parent's, an unknown loop is
+ * TPC_MPC_ERR_BAD_ARG.  A host-only handle runs TPC_MPC_LOOP_NEWTON with TPC_MPC_NEWTON_FALLBACK_NONE on the calling
+ * thread with the kernel's bits; anything else is TPC_MPC_ERR_NO_DEVICE, reported after the argument checks. */
+int tpc_mpc_rollout_plant(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io,
+                          const tpc_mpc_plant* plant, int32_t loop, int32_t steps, const void* new_last_targets,
+                          const tpc_mpc_polish* q, int32_t fallback, void* controls_out, void* states_out,
+                          int32_t* iters_out, void* sequences_out, int32_t* first_unverified, uint32_t* flags_out,
+                          int mem, void* stream);
+
+/* Gradients of the plant's inputs: [4] [2*I] [2] with the io's ld, ddisturbance [steps*2] with the plant's ld_d (the
+ * io's ld when the plant has no disturbance).  All optional, all overwritten. */
+typedef struct tpc_mpc_plant_grad {
+    void *dA, *dB, *dC, *ddisturbance;
+} tpc_mpc_plant_grad;
+/* tpc_mpc_rollout_backward against a separate plant.  The sweep, for k = steps-1 .. 0 with lambda = 0 at the end:
+ *     mu = lambda + G_x[k]
+ *     dAp += mu x_k',  dBp += mu u0_k',  dCp += mu,  ddisturbance[k] = mu
+ *     dL/du0_k = G_u[k] + Bp' mu
+ *     lambda = Ap' mu + d          (d: the solve's dL/dx_k)
+ * and the controller's dA .. dupper receive the solves' contributions only.  With the plant's arrays null the plant
+ * terms go into dA, dB, dC as in tpc_mpc_rollout_backward (pg's dA, dB, dC must then be null: TPC_MPC_ERR_BAD_ARG);
+ * ddisturbance may be asked for without a disturbance: it is the gradient at d = 0.  The disturbance itself is not
+ * read (the states are recorded).  plant and pg are required; everything else as tpc_mpc_rollout_backward, non-finite
+ * plant values counting as non-finite data. */
+int tpc_mpc_rollout_plant_backward(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io,
+                                   const tpc_mpc_plant* plant, int32_t steps, const void* new_last_targets,
+                                   const tpc_mpc_rollout_grad* g, const tpc_mpc_plant_grad* pg, uint32_t* flags_out,
+                                   int mem, void* stream);
+
+/* Tangents of the plant's inputs, K = t->directions stacked row blocks like tpc_mpc_tangents' (element (d, c, k) of a
+ * C-component array at base[(d*C + c)*ld + k]; tdisturbance [K*steps*2] with the plant's ld_d).  Null = zero. */
+typedef struct tpc_mpc_plant_tangents {
+    const void *tA, *tB, *tC, *tdisturbance;
+} tpc_mpc_plant_tangents;
+/* tpc_mpc_rollout_forward against a separate plant:
+ *     tx_{k+1} = tAp x_k + Ap tx_k + tBp u0_k + Bp tu0_k + tCp + td_k
+ * and t's tA, tB, tC enter the step's QP only.  With the plant's arrays null the controller's model and its tangents
+ * move the state as in tpc_mpc_rollout_forward (pt's tA, tB, tC must then be null).  The transpose identity of
+ * tpc_mpc_rollout_forward holds with the plant's and the disturbance's terms on its right-hand side.  plant is
+ * required, pt may be null (all zero); everything else as tpc_mpc_rollout_forward. */
+int tpc_mpc_rollout_plant_forward(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io,
+                                  const tpc_mpc_plant* plant, int32_t steps, const void* new_last_targets,
+                                  const void* sequences, const void* states, const tpc_mpc_tangents* t,
+                                  const tpc_mpc_plant_tangents* pt, void* tcontrols, void* tstates,
+                                  uint32_t* flags_out, int mem, void* stream);
+
 /* ---- batched cycle(): raw trajectories in, CarCommand fields out -------------------------------- */
 
 /* Polylines of n instances, SoA: point i of instance k at base[i*ld + k] (float), `count[k]` points

@@ -1,0 +1,373 @@
+"""GPU tests of the closed loops against a separate plant (tpc_mpc_rollout_plant, _plant_backward, _plant_forward): the
+gfx950 kernels against the host-only handle bit for bit (HOST and DEVICE memory), the Newton loop's fallback against the
+polished plant loop (the gather carries the plant and the disturbance), the polished plant loop against the Newton
+loop where that one verifies, and the existing entries' bytes around plant calls on one handle."""
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+
+from tests.model import mpc_grad_dense as dense
+from tests.model import mpc_rollout_dense as rd
+from tests.model import mpc_rollout_tangent_dense as td
+from tests.test_rollout_plant_host import make_plant, same_bits
+from trajectory_controller_amd import MpcSolver, capi
+
+pytestmark = pytest.mark.gpu
+NAMES = rd.NAMES
+TOL, ROUNDS = 1e-9, 8
+
+
+def _case(I, H, S, n, with_nlt=True):
+    th, nlt = rd.batch(I, H, S, n, seed=H + I, with_nlt=with_nlt)
+    ins = [dense.soa(th[k], n) for k in NAMES]
+    nl = None if nlt is None else dense.soa(nlt, n)
+    return ins, nl, make_plant(ins, I, S)
+
+
+def _newton(s, I, S, ins, nl, plant, dist, to=lambda a: a, back=np.asarray, **kw):
+    out = s.rollout_newton(S, *[to(a) for a in ins], None if nl is None else to(nl), inputs=I, tol=TOL,
+                           max_rounds=kw.pop("max_rounds", ROUNDS), want_iters=True,
+                           plant=None if plant is None else tuple(to(a) for a in plant),
+                           disturbance=None if dist is None else to(dist), **kw)
+    return [back(a) for a in out], s.last_flags
+
+
+@pytest.mark.parametrize("mem", ["host", "device"])
+@pytest.mark.parametrize("with_nlt", [True, False], ids=["nlt", "nonlt"])
+@pytest.mark.parametrize("I,H,n", [(1, 4, 70), (2, 10, 333), (2, 20, 70), (1, 40, 333), (2, 40, 70)])
+def test_device_equals_host_only_handle_bit_for_bit(I, H, n, with_nlt, mem):
+    S, K = 5, 3
+    ins, nl, (plant, dist) = _case(I, H, S, n, with_nlt)
+    to = (lambda a: torch.from_numpy(a).cuda()) if mem == "device" else (lambda a: a)
+    back = (lambda a: a.cpu().numpy()) if mem == "device" else np.asarray
+    rng = np.random.default_rng(2)
+    G_u, G_x = rng.standard_normal((S * I, n)), rng.standard_normal((2 * S, n))
+    tan = td.soa_tangents(td.random_tangents(I, H, S, n, 8, with_nlt=with_nlt, K=K), n)
+    tan.update(Ap=rng.standard_normal((K, 4, n)), Bp=rng.standard_normal((K, 2 * I, n)),
+               Cp=rng.standard_normal((K, 2, n)), disturbance=rng.standard_normal((K, 2 * S, n)))
+    with MpcSolver(horizon=H, device=None) as hs:
+        want, wflags = _newton(hs, I, S, ins, nl, plant, dist, fallback="none")
+        u, x, q = want[:3]
+        wg = hs.rollout_backward(S, *ins, nl, sequences=q, states=x, grad_controls=G_u, grad_states=G_x, inputs=I,
+                                 plant=plant, disturbance=dist)
+        wt = hs.rollout_forward(S, *ins, nl, sequences=q, states=x, tangents=tan, inputs=I, plant=plant)
+    with MpcSolver(horizon=H, device=0) as s:
+        got, flags = _newton(s, I, S, ins, nl, plant, dist, to, back, fallback="none")
+        assert flags == wflags
+        for a, b in zip(got, want):
+            assert same_bits(a, b)
+        dins, dnl = [to(a) for a in ins], (None if nl is None else to(nl))
+        g = s.rollout_backward(S, *dins, dnl, sequences=to(q), states=to(x), grad_controls=to(G_u), grad_states=to(G_x),
+                               inputs=I, plant=tuple(to(a) for a in plant), disturbance=to(dist))
+        for k in wg:
+            assert same_bits(back(g[k]), wg[k]), k
+        t = s.rollout_forward(S, *dins, dnl, sequences=to(q), states=to(x), tangents={k: to(v) for k, v in tan.items()},
+                              inputs=I, plant=tuple(to(a) for a in plant))
+        assert same_bits(back(t[0]), wt[0]) and same_bits(back(t[1]), wt[1])
+
+
+@pytest.mark.parametrize("I,H", [(1, 1), (2, 64)])
+def test_derivative_entries_at_the_extreme_horizons(I, H):
+    S, K, n = 3, 1, 70
+    ins, nl, (plant, dist) = _case(I, H, S, n)
+    rng = np.random.default_rng(4)
+    q = np.clip(rng.uniform(-0.5, 0.5, (S * H * I, n)), np.tile(ins[5], (S * H, 1)), np.tile(ins[6], (S * H, 1)))
+    x, G_x = rng.standard_normal((2 * S, n)), rng.standard_normal((2 * S, n))
+    tan = {"Ap": rng.standard_normal((K, 4, n)), "disturbance": rng.standard_normal((K, 2 * S, n))}
+    with MpcSolver(horizon=H, device=None) as hs:
+        wg = hs.rollout_backward(S, *ins, nl, sequences=q, states=x, grad_states=G_x, inputs=I, plant=plant)
+        wt = hs.rollout_forward(S, *ins, nl, sequences=q, states=x, tangents=tan, inputs=I, plant=plant)
+    with MpcSolver(horizon=H, device=0) as s:
+        g = s.rollout_backward(S, *ins, nl, sequences=q, states=x, grad_states=G_x, inputs=I, plant=plant)
+        t = s.rollout_forward(S, *ins, nl, sequences=q, states=x, tangents=tan, inputs=I, plant=plant)
+    for k in wg:
+        assert same_bits(g[k], wg[k]), k
+    assert same_bits(t[0], wt[0]) and same_bits(t[1], wt[1])
+
+
+@pytest.mark.parametrize("algo", ["lane", "group"])
+@pytest.mark.parametrize("I,H", [(2, 10), (1, 20)])
+def test_fallback_equals_the_polished_plant_loop(I, H, algo):
+    """max_rounds = 0 verifies nothing in phase 1, so every instance falls back: the gather has to carry the plant's
+    arrays and the disturbance's rows.  With 8 rounds the fallen-back instances equal the polished loop's, the others keep
+    their FALLBACK_NONE bits."""
+    S, n = 4, 333
+    ins, nl, (plant, dist) = _case(I, H, S, n)
+    with MpcSolver(horizon=H, device=0, algo=algo) as s:
+        pol = s.rollout_polished(S, *ins, nl, inputs=I, tol=TOL, max_rounds=ROUNDS, want_iters=True, plant=plant,
+                                 disturbance=dist)
+        parent = s.rollout_polished(S, *ins, nl, inputs=I, tol=TOL, max_rounds=ROUNDS, want_iters=True)
+        assert not same_bits(pol[1], parent[1])
+        none, _ = _newton(s, I, S, ins, nl, plant, dist, fallback="none")
+        full, _ = _newton(s, I, S, ins, nl, plant, dist, fallback="solve")
+        fb = none[5] < S
+        assert fb.any() and not fb.all()
+        for i, name in enumerate(("controls", "states", "sequences", "status", "iters")):
+            assert same_bits(np.ascontiguousarray(full[i][:, fb]), np.ascontiguousarray(pol[i][:, fb])), name
+            assert same_bits(np.ascontiguousarray(full[i][:, ~fb]), np.ascontiguousarray(none[i][:, ~fb])), name
+    with MpcSolver(horizon=H, device=0, algo=algo) as s:
+        pol0 = s.rollout_polished(S, *ins, nl, inputs=I, tol=TOL, max_rounds=0, want_iters=True, plant=plant,
+                                  disturbance=dist)
+        all_fb, _ = _newton(s, I, S, ins, nl, plant, dist, fallback="solve", max_rounds=0)
+        assert (all_fb[5] == 0).all()
+        for i in range(5):
+            assert same_bits(all_fb[i], pol0[i])
+
+
+def _composed(s, I, H, S, ins, nlt, plant, dist, polished, **over):
+    """tests/test_rollout_polish_gpu.py::_composed with one line changed: solve_batch_general carrying controls and v,
+    polish_batch_general (the polished loop only), then the PLANT's line and the target shift in numpy in the step
+    kernel's operation order.  (controls, states, sequences, iters, status | None, c, v)"""
+    n = ins[0].shape[1]
+    model = ins[:7]
+    A, B, Cc = plant
+    x, T = ins[7].copy(), ins[8].copy()
+    c, v = np.zeros((H * I, n)), np.zeros((H * I, n))
+    out = [[] for _ in range(5)]
+    for k in range(S):
+        _, it = s.solve_batch_general(*model, x, T, controls=c, v_state=v, inputs=I, want_iters=True, **over)
+        st = None
+        if polished:
+            _, st, _, _ = s.polish_batch_general(*model, x, T, c, tol=TOL, max_rounds=ROUNDS, inputs=I)
+        u = c.copy()
+        bu0, bu1 = B[0] * u[0], B[I] * u[0]
+        if I == 2:
+            bu0, bu1 = bu0 + B[1] * u[1], bu1 + B[3] * u[1]
+        n0 = (((A[0] * x[0] + A[1] * x[1]) + bu0) + Cc[0]) + dist[2 * k]
+        n1 = (((A[2] * x[0] + A[3] * x[1]) + bu1) + Cc[1]) + dist[2 * k + 1]
+        x = np.stack([n0, n1])
+        T[:-2] = T[2:].copy()
+        if nlt is not None and k + 1 < S:
+            T[-2:] = nlt[2 * (k + 1):2 * (k + 1) + 2]
+        for lst, val in zip(out, (u[:I], x, u, it, st)):
+            lst.append(None if val is None else np.array(val))
+    cat = lambda l: None if l[0] is None else np.ascontiguousarray(np.concatenate([a.reshape(-1, n) for a in l]))
+    return [cat(l) for l in out] + [c.copy(), v.copy()]
+
+
+@pytest.mark.parametrize("algo", ["lane", "group"])
+@pytest.mark.parametrize("polished", [False, True], ids=["record", "polished"])
+@pytest.mark.parametrize("I,H,with_nlt", [(2, 10, True), (1, 20, False), (2, 40, True)])
+def test_solve_based_loops_equal_the_composed_loop_bits(I, H, with_nlt, polished, algo):
+    """TPC_MPC_LOOP_RECORD and _POLISHED with plant and disturbance against the loop written from the public entries;
+    every output, nothing left out."""
+    S, n = 4, 130
+    ins, nl, (plant, dist) = _case(I, H, S, n, with_nlt)
+    with MpcSolver(horizon=H, device=0, algo=algo) as s:
+        want = _composed(s, I, H, S, ins, nl, plant, dist, polished)
+        c, v = np.zeros((H * I, n)), np.zeros((H * I, n))
+        if polished:
+            u, x, q, st, it = s.rollout_polished(S, *ins, nl, controls=c, v_state=v, inputs=I, tol=TOL,
+                                                 max_rounds=ROUNDS, want_iters=True, plant=plant, disturbance=dist)
+        else:
+            u, x, q, it = s.rollout_record(S, *ins, nl, controls=c, v_state=v, inputs=I, want_iters=True, plant=plant,
+                                           disturbance=dist)
+            st = None
+    for name, a, b in zip(("controls", "states", "sequences", "iters", "status", "controls_inout", "v_inout"),
+                          (u, x, q, it, st, c, v), want):
+        assert (a is None and b is None) or same_bits(a, b), name
+    # the plant matters: a loop that moved with the controller's model gives other states
+    with MpcSolver(horizon=H, device=0, algo=algo) as s:
+        parent = s.rollout_record(S, *ins, nl, inputs=I)
+    assert not same_bits(parent[1], x)
+
+
+@pytest.mark.parametrize("mem", ["host", "device"])
+@pytest.mark.parametrize("K", [1, 3])
+def test_a_shard_of_a_wider_batch(mem, K):
+    """ld > n and ld_d != ld through the C entries on the device: columns [5, 5 + n) of wider arrays equal the packed
+    host-only call, and the padding of every output is untouched."""
+    import ctypes as C
+    I, H, S, n, off = 2, 10, 4, 70, 5
+    ld, ld_d = n + 13, n + 29
+    ins, nl, (plant, dist) = _case(I, H, S, n)
+    rng = np.random.default_rng(3)
+    G_x = rng.standard_normal((2 * S, n))
+    tAp, td = rng.standard_normal((K, 4, n)), rng.standard_normal((K, 2 * S, n))
+    with MpcSolver(horizon=H, device=None) as hs:
+        want, wflags = _newton(hs, I, S, ins, nl, plant, dist, fallback="none")
+        wg = hs.rollout_backward(S, *ins, nl, sequences=want[2], states=want[1], grad_states=G_x, inputs=I, plant=plant,
+                                 want=("A", "Ap", "disturbance"))
+        wt = hs.rollout_forward(S, *ins, nl, sequences=want[2], states=want[1], inputs=I, plant=plant,
+                                tangents={"Ap": tAp, "disturbance": td})
+
+    def wide(a, ld, fill=np.nan):
+        w = np.full(a.shape[:-1] + (ld,), fill, dtype=a.dtype)
+        w[..., off:off + n] = a
+        return w.reshape(-1, ld)
+    hold = lambda a: torch.from_numpy(a).cuda() if mem == "device" else a
+    size = lambda a: a.element_size() if torch.is_tensor(a) else a.itemsize
+    ptr = lambda a: (a.data_ptr() if torch.is_tensor(a) else a.ctypes.data) + off * size(a)
+    back = lambda a: a.cpu().numpy() if torch.is_tensor(a) else a
+    arrs = [hold(wide(a, ld)) for a in list(ins) + [nl] + list(plant)]
+    wd = hold(wide(dist, ld_d))
+    u, x, q = (hold(np.full((r, ld), 3.0)) for r in (S * I, 2 * S, S * H * I))
+    st, first = hold(np.full((S, ld), 9, np.int32)), hold(np.full((1, ld), 9, np.int32))
+    lib = capi.load_library()
+    with MpcSolver(horizon=H, device=0) as s:
+        p, m = s._params(), (capi.DEVICE if mem == "device" else capi.HOST)
+        io = capi.GeneralIO(inputs=I, n=n, ld=ld, **{k: ptr(a) for k, a in zip(
+            ("A", "B", "C", "Q", "R", "lower", "upper", "x0", "targets"), arrs)})
+        pl = capi.Plant(A=ptr(arrs[10]), B=ptr(arrs[11]), C=ptr(arrs[12]), disturbance=ptr(wd), ld_d=ld_d)
+        pol = capi.Polish(tol=TOL, max_rounds=ROUNDS, reserved=0, status=ptr(st))
+        flags = C.c_uint32(0)
+        rc = lib.tpc_mpc_rollout_plant(s._h, C.byref(p), C.byref(io), C.byref(pl), capi.LOOP_NEWTON, S, ptr(arrs[9]),
+                                       C.byref(pol), capi.NEWTON_FALLBACK_NONE, ptr(u), ptr(x), None, ptr(q),
+                                       ptr(first), C.byref(flags), m, None)
+        assert rc == capi.OK and flags.value == wflags
+        for got, ref, pad in ((u, want[0], 3.0), (x, want[1], 3.0), (q, want[2], 3.0), (st, want[3], 9)):
+            g = back(got)
+            assert same_bits(np.ascontiguousarray(g[:, off:off + n]), ref)
+            assert (g[:, :off] == pad).all() and (g[:, off + n:] == pad).all()
+        assert same_bits(np.ascontiguousarray(back(first)[0, off:off + n]), want[5])
+        # backward: dA, dAp with ld, ddisturbance with ld_d
+        gx = hold(wide(G_x, ld))
+        dA, dAp, dd = hold(np.full((4, ld), 3.0)), hold(np.full((4, ld), 3.0)), hold(np.full((2 * S, ld_d), 3.0))
+        g = capi.RolloutGrad(sequences=ptr(q), states=ptr(x), grad_states=ptr(gx), dA=ptr(dA))
+        pg = capi.PlantGrad(dA=ptr(dAp), ddisturbance=ptr(dd))
+        rc = lib.tpc_mpc_rollout_plant_backward(s._h, C.byref(p), C.byref(io), C.byref(pl), S, ptr(arrs[9]), C.byref(g),
+                                                C.byref(pg), C.byref(flags), m, None)
+        assert rc == capi.OK and flags.value == 0
+        for got, ref in ((dA, wg["A"]), (dAp, wg["Ap"]), (dd, wg["disturbance"])):
+            g_ = back(got)
+            assert same_bits(np.ascontiguousarray(g_[:, off:off + n]), ref)
+            assert (g_[:, :off] == 3.0).all() and (g_[:, off + n:] == 3.0).all()
+        # forward: tdisturbance with ld_d, K stacked blocks
+        wtA, wtd = hold(wide(tAp, ld, 0.0)), hold(wide(td, ld_d, 0.0))
+        tu, tx = hold(np.full((K * S * I, ld), 3.0)), hold(np.full((K * 2 * S, ld), 3.0))
+        tan = capi.Tangents(directions=K)
+        ptan = capi.PlantTangents(tA=ptr(wtA), tdisturbance=ptr(wtd))
+        rc = lib.tpc_mpc_rollout_plant_forward(s._h, C.byref(p), C.byref(io), C.byref(pl), S, ptr(arrs[9]), ptr(q),
+                                               ptr(x), C.byref(tan), C.byref(ptan), ptr(tu), ptr(tx), C.byref(flags), m,
+                                               None)
+        assert rc == capi.OK and flags.value == 0
+        for got, ref in ((tu, wt[0]), (tx, wt[1])):
+            g_ = back(got)
+            assert same_bits(np.ascontiguousarray(g_[:, off:off + n]), ref.reshape(-1, n))
+            assert (g_[:, :off] == 3.0).all() and (g_[:, off + n:] == 3.0).all()
+
+
+# ---- autograd ----------------------------------------------------------------------------------------------------------
+
+def test_autograd_backward_forward_ad_and_central_differences():
+    """mpc_rollout(..., polish=True, newton_first=True, plant=, disturbance=): backward against the dense checker
+    (1e-9 normwise, as the parent's test) on the carried instances, forward_ad against the direct call bit for bit,
+    and both against central differences of the plant Newton loop in Ap and in the disturbance (tol 1e-12, step 1e-6,
+    the 1e-4 assertion)."""
+    import torch.autograd.forward_ad as fwAD
+    from tests.model import mpc_rollout_plant_dense as pd
+    from tests.test_rollout_newton_host import inputs, soa_inputs
+    from trajectory_controller_amd import mpc_rollout
+    I, H, S, n = 2, 10, 5, 40
+    th, nlt = inputs("general", I, H, S, n=n)
+    ins, nl = soa_inputs(th, nlt, n)
+    plant, dist = make_plant(ins, I, S)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    rng = np.random.default_rng(9)
+    G_u, G_x = rng.standard_normal((S * I, n)), rng.standard_normal((2 * S, n))
+    tAp, td = rng.standard_normal((4, n)), rng.standard_normal((2 * S, n))
+    with MpcSolver(horizon=H, device=0) as s:
+        t_ins = [up(a).requires_grad_() for a in ins]
+        t_nl, t_plant, t_dist = up(nl).requires_grad_(), [up(a).requires_grad_() for a in plant], up(dist).requires_grad_()
+        u, x = mpc_rollout(s, S, *t_ins, t_nl, polish=True, newton_first=True, plant=tuple(t_plant), disturbance=t_dist)
+        ((u * up(G_u)).sum() + (x * up(G_x)).sum()).backward()
+        direct = s.rollout_newton(S, *ins, nl, inputs=I, tol=1e-9, max_rounds=8, plant=plant, disturbance=dist)
+        assert same_bits(u.detach().cpu().numpy(), direct[0]) and same_bits(x.detach().cpu().numpy(), direct[1])
+        first = s.rollout_newton(S, *ins, nl, inputs=I, tol=1e-9, max_rounds=8, fallback="none", plant=plant,
+                                 disturbance=dist)[5]
+        carried = np.flatnonzero(first == S)
+        assert carried.size >= 0.9 * n
+        got = dict(zip(("A", "B", "C", "Q", "R", "lo", "hi", "x0", "targets"), [t.grad.cpu().numpy() for t in t_ins]))
+        got.update(nlt=t_nl.grad.cpu().numpy(), d=t_dist.grad.cpu().numpy(),
+                   **{k: t.grad.cpu().numpy() for k, t in zip(("Ap", "Bp", "Cp"), t_plant)})
+        seqs = np.ascontiguousarray(direct[2].T).reshape(n, S, H, I)
+        aos = lambda a, shape: np.ascontiguousarray(a.T).reshape((n,) + shape)
+        for i in carried[:12]:
+            ref, *_ = pd.closed_loop(I, H, S, {k: th[k][i] for k in dense.NAMES}, nlt[i], seqs[i],
+                                     aos(G_u, (S, I))[i], aos(G_x, (S, 2))[i], tuple(a[:, i] for a in plant),
+                                     aos(dist, (S, 2))[i])
+            for k, g in got.items():
+                want = ref[k].ravel()
+                err = np.linalg.norm(g[:, i] - want)
+                assert err <= 1e-9 * np.linalg.norm(want) + 1e-12, (i, k, err, np.linalg.norm(want))
+        # forward_ad against the direct call, bit for bit
+        with fwAD.dual_level():
+            d_ins = [up(a) for a in ins]
+            d_plant = (fwAD.make_dual(up(plant[0]), up(tAp)), up(plant[1]), up(plant[2]))
+            d_dist = fwAD.make_dual(up(dist), up(td))
+            du, dx = mpc_rollout(s, S, *d_ins, up(nl), polish=True, newton_first=True, plant=d_plant, disturbance=d_dist)
+            ju, jx = fwAD.unpack_dual(du).tangent.cpu().numpy(), fwAD.unpack_dual(dx).tangent.cpu().numpy()
+        tu, tx = s.rollout_forward(S, *ins, nl, sequences=direct[2], states=direct[1], inputs=I, plant=plant,
+                                   tangents={"Ap": tAp[None], "disturbance": td[None]})
+        assert same_bits(ju, tu[0]) and same_bits(jx, tx[0])
+        # central differences of the plant Newton loop along (tAp, td)
+        h = 1e-6
+        def loop(sgn):
+            o = s.rollout_newton(S, *ins, nl, inputs=I, tol=1e-12, max_rounds=8, fallback="none",
+                                 plant=(plant[0] + sgn * h * tAp, plant[1], plant[2]), disturbance=dist + sgn * h * td)
+            return o[0], o[1], o[2], o[5]
+        (pu, px, pq, pf), (mu_, mx, mq, mf) = loop(1.0), loop(-1.0)
+        act = lambda q: (q <= np.tile(ins[5], (S * H, 1))) | (q >= np.tile(ins[6], (S * H, 1)))
+        stable = (pf == S) & (mf == S) & (first == S) & (act(pq) == act(mq)).all(0) & (act(pq) == act(direct[2])).all(0)
+        assert stable.sum() >= n // 2
+        fu, fx = (pu - mu_) / (2 * h), (px - mx) / (2 * h)
+        for got_, fd in ((ju, fu), (jx, fx)):
+            assert (np.abs(got_ - fd)[:, stable] <= 1e-4 * np.maximum(1.0, np.abs(fd[:, stable]))).all()
+        # ... and the backward through the same differences: <G, J t> = <grad, t>
+        lhs = (G_u * fu).sum(0) + (G_x * fx).sum(0)
+        rhs = (got["Ap"] * tAp).sum(0) + (got["d"] * td).sum(0)
+        assert (np.abs(lhs - rhs)[stable] <= 1e-4 * np.maximum(1.0, np.abs(rhs[stable]))).all()
+
+
+def test_one_full_size_run():
+    """262 144 x N = 20 x 10 steps on the device: the plant Newton loop, its backward and one direction of its forward,
+    with the transpose identity on a 1 024 sample (DESIGN.md section 17's bound)."""
+    from tests.test_rollout_tangent_host import BOUND, mismatch
+    from trajectory_controller_amd.synth import general_inputs
+    I, H, S, n = 2, 20, 10, 262144
+    g = general_inputs(H, n, I=I, seed=5)
+    ins = [np.ascontiguousarray(g[k].reshape(n, -1).T) for k in rd.NAMES]
+    plant, dist = make_plant(ins, I, S)
+    up = lambda a: torch.from_numpy(a).cuda()
+    rng = np.random.default_rng(8)
+    d_ins, d_plant, d_dist = [up(a) for a in ins], tuple(up(a) for a in plant), up(dist)
+    G_u, G_x = up(rng.standard_normal((S * I, n))), up(rng.standard_normal((2 * S, n)))
+    tan = {"Ap": up(rng.standard_normal((1, 4, n))), "Bp": up(rng.standard_normal((1, 2 * I, n))),
+           "Q": up(rng.standard_normal((1, 2, n))), "disturbance": up(rng.standard_normal((1, 2 * S, n)))}
+    with MpcSolver(horizon=H, device=0) as s:
+        u, x, q, st, _, first = s.rollout_newton(S, *d_ins, None, inputs=I, tol=TOL, max_rounds=ROUNDS, plant=d_plant,
+                                                 disturbance=d_dist)
+        assert not (s.last_flags & capi.FLAG_NONFINITE)
+        gr = s.rollout_backward(S, *d_ins, None, sequences=q, states=x, grad_controls=G_u, grad_states=G_x, inputs=I,
+                                plant=d_plant, want=("Ap", "Bp", "Q", "disturbance"))
+        assert s.last_flags == 0
+        tu, tx = s.rollout_forward(S, *d_ins, None, sequences=q, states=x, tangents=tan, inputs=I, plant=d_plant)
+        assert s.last_flags == 0
+        assert bool(torch.isfinite(u).all()) and bool(torch.isfinite(x).all())
+    idx = torch.from_numpy(rng.choice(n, 1024, replace=False)).cuda()
+    c = lambda t: t.index_select(-1, idx).cpu().numpy()
+    m = mismatch([c(G_u) * c(tu[0]), c(G_x) * c(tx[0])], [c(gr[k]) * c(tan[k][0]) for k in tan])
+    assert float(m.max()) <= BOUND, float(m.max())
+
+
+def test_existing_entries_keep_their_bytes_around_plant_calls():
+    I, H, S, n = 2, 10, 4, 70
+    ins, nl, (plant, dist) = _case(I, H, S, n)
+    with MpcSolver(horizon=H, device=0) as s:
+        def parents():
+            a = s.rollout_newton(S, *ins, nl, inputs=I, tol=TOL, max_rounds=ROUNDS)
+            b = s.rollout_polished(S, *ins, nl, inputs=I, tol=TOL, max_rounds=ROUNDS)
+            c = s.rollout_record(S, *ins, nl, inputs=I)
+            g = s.rollout_backward(S, *ins, nl, sequences=a[2], states=a[1], grad_states=np.ones_like(a[1]), inputs=I)
+            t = s.rollout_forward(S, *ins, nl, sequences=a[2], states=a[1], tangents={"A": np.ones((1, 4, n))}, inputs=I)
+            return [np.asarray(v) for v in a[:3] + b[:3] + c[:3] + tuple(g.values()) + t]
+        before = parents()
+        out = s.rollout_newton(S, *ins, nl, inputs=I, tol=TOL, max_rounds=ROUNDS, plant=plant, disturbance=dist)
+        s.rollout_backward(S, *ins, nl, sequences=out[2], states=out[1], grad_states=np.ones_like(out[1]), inputs=I,
+                           plant=plant)
+        s.rollout_forward(S, *ins, nl, sequences=out[2], states=out[1], tangents={"Ap": np.ones((1, 4, n))}, inputs=I,
+                          plant=plant)
+        after = parents()
+    for a, b in zip(before, after):
+        assert same_bits(a, b)

@@ -129,8 +129,70 @@ class _MpcRollout(torch.autograd.Function):
         return (None, None, None, None) + tuple(g.get(k) for k in names)
 
 
+class _MpcRolloutPlant(torch.autograd.Function):
+    """_MpcRollout against a separate plant (tpc_mpc_rollout_plant and its backward / forward): four more inputs, Ap,
+    Bp, Cp (all or none) and the disturbance, each of which may be None."""
+    NAMES = ("A", "B", "C", "Q", "R", "lower", "upper", "x0", "targets", "new_last_targets", "Ap", "Bp", "Cp",
+             "disturbance")
+
+    @staticmethod
+    def forward(ctx, solver, steps, over, polish, A, B, Cc, Q, R, lower, upper, x0, targets, new_last_targets, Ap, Bp,
+                Cp, disturbance):
+        I = R.shape[0]
+        ins = [t.detach().contiguous() for t in (A, B, Cc, Q, R, lower, upper, x0, targets)]
+        opt = [None if t is None else t.detach().contiguous() for t in (new_last_targets, Ap, Bp, Cp, disturbance)]
+        nlt, plant, dist = opt[0], (None if Ap is None else tuple(opt[1:4])), opt[4]
+        if polish:
+            tol, rounds, newton_first = polish
+            forward = solver.rollout_newton if newton_first else solver.rollout_polished
+            controls, states, sequences, *_ = forward(steps, *ins, nlt, inputs=I, tol=tol, max_rounds=rounds,
+                                                      want_status=False, plant=plant, disturbance=dist, **over)
+        else:
+            controls, states, sequences, _ = solver.rollout_record(steps, *ins, nlt, inputs=I, plant=plant,
+                                                                   disturbance=dist, **over)
+        ctx.solver, ctx.steps, ctx.over, ctx.I = solver, steps, over, I
+        ctx.given = [t is not None for t in opt]
+        kept = [t for t in opt if t is not None]
+        ctx.save_for_backward(*ins, *kept, states, sequences)
+        ctx.save_for_forward(*ins, *kept, states, sequences, controls)
+        return controls, states
+
+    @staticmethod
+    def _unpack(ctx):
+        saved = list(ctx.saved_tensors)
+        ins, rest = saved[:9], saved[9:]
+        opt = [rest.pop(0) if g else None for g in ctx.given]
+        plant = None if opt[1] is None else tuple(opt[1:4])
+        return ins, opt[0], plant, opt[4], rest
+
+    @staticmethod
+    def jvp(ctx, _solver, _steps, _over, _polish, *tangents):
+        ins, nlt, plant, dist, (states, sequences, controls) = _MpcRolloutPlant._unpack(ctx)
+        tan = {k: t.contiguous() for k, t in zip(_MpcRolloutPlant.NAMES, tangents) if t is not None}
+        if not tan:
+            return torch.zeros_like(controls), torch.zeros_like(states)
+        tu, tx = ctx.solver.rollout_forward(ctx.steps, *ins, nlt, sequences=sequences, states=states, tangents=tan,
+                                            inputs=ctx.I, want_flags=False, plant=plant, disturbance=dist, **ctx.over)
+        return tu[0], tx[0]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_controls, grad_states):
+        ins, nlt, plant, dist, (states, sequences) = _MpcRolloutPlant._unpack(ctx)
+        names = _MpcRolloutPlant.NAMES
+        want = tuple(k for k, need in zip(names, ctx.needs_input_grad[4:]) if need)
+        if not want:
+            return (None,) * 18
+        g = ctx.solver.rollout_backward(ctx.steps, *ins, nlt, sequences=sequences, states=states,
+                                        grad_controls=None if grad_controls is None else grad_controls.contiguous(),
+                                        grad_states=None if grad_states is None else grad_states.contiguous(),
+                                        inputs=ctx.I, want=want, want_flags=False, plant=plant, disturbance=dist,
+                                        **ctx.over)
+        return (None, None, None, None) + tuple(g.get(k) for k in names)
+
+
 def mpc_rollout(solver, steps, A, B, Cc, Q, R, lower, upper, x0, targets, new_last_targets=None, polish=False,
-                newton_first=False, **over):
+                newton_first=False, plant=None, disturbance=None, **over):
     """The closed loop of n fresh dlib::mpc<2,I,H> controllers (MpcSolver.rollout: `steps` warm-started operator()
     calls with the target shift and the plant update x <- A x + B u + C between them) as a differentiable function.
     Returns (controls [steps*I, n], states [steps*2, n]); gradients reach A, B, C, Q, R, lower, upper, x0, targets and
@@ -145,7 +207,11 @@ def mpc_rollout(solver, steps, A, B, Cc, Q, R, lower, upper, x0, targets, new_la
     polish=False is the unpolished loop, bit for bit.  newton_first=True (with polish) makes the forward
     MpcSolver.rollout_newton: every step is polished from the shifted warm start first, all steps in one launch, and
     only the instances it does not verify run rollout_polished's loop; both forwards return the verified optimum of
-    every step, so they agree to rounding, and the backward is the same.  `over` overrides the solver's parameters."""
+    every step, so they agree to rounding, and the backward is the same.  `over` overrides the solver's parameters.
+    plant=(Ap, Bp, Cp) [4, n] [2I, n] [2, n] and / or disturbance [steps*2, n]: the state moves with
+    x <- Ap x + Bp u + Cp + d_k while every step's controller keeps A, B, C (tpc_mpc_rollout_plant); gradients and
+    forward_ad tangents then reach Ap, Bp, Cp and the disturbance too, and those of A, B, C are what the controller's
+    belief alone contributes.  Both None is the function above, untouched."""
     if newton_first and not polish:
         raise ValueError("newton_first needs polish")
     if polish:
@@ -153,6 +219,13 @@ def mpc_rollout(solver, steps, A, B, Cc, Q, R, lower, upper, x0, targets, new_la
     for t in (A, B, Cc, Q, R, lower, upper, x0, targets) + (() if new_last_targets is None else (new_last_targets,)):
         if not (t.is_cuda and t.dtype == torch.float64):
             raise ValueError("mpc_rollout takes CUDA fp64 tensors")
+    if plant is not None or disturbance is not None:
+        Ap, Bp, Cp = plant if plant is not None else (None, None, None)
+        for t in (Ap, Bp, Cp, disturbance):
+            if t is not None and not (t.is_cuda and t.dtype == torch.float64):
+                raise ValueError("mpc_rollout takes CUDA fp64 tensors")
+        return _MpcRolloutPlant.apply(solver, int(steps), over, polish, A, B, Cc, Q, R, lower, upper, x0, targets,
+                                      new_last_targets, Ap, Bp, Cp, disturbance)
     return _MpcRollout.apply(solver, int(steps), over, polish, A, B, Cc, Q, R, lower, upper, x0, targets,
                              new_last_targets)
 

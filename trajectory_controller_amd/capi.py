@@ -22,6 +22,7 @@ DEVICE_NONE = -1   # tpc_mpc_create: a host-only handle
 FLAG_NONFINITE, FLAG_MAX_ITER, FLAG_BAD_MODEL, FLAG_NOT_POLISHED = 0x1, 0x2, 0x4, 0x8
 NEWTON_FALLBACK_SOLVE, NEWTON_FALLBACK_NONE = 0, 1   # tpc_mpc_rollout_newton
 NEWTON_FALLBACKS = {"solve": NEWTON_FALLBACK_SOLVE, "none": NEWTON_FALLBACK_NONE}
+LOOP_RECORD, LOOP_POLISHED, LOOP_NEWTON = 0, 1, 2   # tpc_mpc_rollout_plant
 PARAM_FAST_CAPPED = 0x1   # tpc_mpc_params.options
 
 STATUS_NAMES = {0: "OK", 1: "BAD_ARG", 2: "BAD_WEIGHTS", 3: "BAD_BOUNDS", 4: "BAD_HORIZON",
@@ -43,7 +44,8 @@ EXPORTS = ("tpc_mpc_default_params", "tpc_mpc_create", "tpc_mpc_destroy", "tpc_m
            "tpc_mpc_shard_map", "tpc_mpc_solve_batch_compact_sharded_split", "tpc_mpc_gather_shards_split",
            "tpc_mpc_solve_batch_general_backward", "tpc_mpc_rollout_record", "tpc_mpc_rollout_backward",
            "tpc_mpc_polish_batch_general", "tpc_mpc_rollout_polished", "tpc_mpc_rollout_newton",
-           "tpc_mpc_solve_batch_general_forward", "tpc_mpc_rollout_forward")
+           "tpc_mpc_solve_batch_general_forward", "tpc_mpc_rollout_forward", "tpc_mpc_rollout_plant",
+           "tpc_mpc_rollout_plant_backward", "tpc_mpc_rollout_plant_forward")
 SPLIT_BLOCK, SPLIT_INTERLEAVED = 0, 1
 SPLITS = {"block": SPLIT_BLOCK, "interleaved": SPLIT_INTERLEAVED}
 
@@ -95,6 +97,22 @@ class Tangents(C.Structure):
                 ("tC", C.c_void_p), ("tQ", C.c_void_p), ("tR", C.c_void_p), ("tlower", C.c_void_p),
                 ("tupper", C.c_void_p), ("tx0", C.c_void_p), ("ttargets", C.c_void_p),
                 ("tnew_last_targets", C.c_void_p)]
+
+
+class Plant(C.Structure):
+    """struct tpc_mpc_plant"""
+    _fields_ = [("A", C.c_void_p), ("B", C.c_void_p), ("C", C.c_void_p), ("disturbance", C.c_void_p),
+                ("ld_d", C.c_int64)]
+
+
+class PlantGrad(C.Structure):
+    """struct tpc_mpc_plant_grad"""
+    _fields_ = [("dA", C.c_void_p), ("dB", C.c_void_p), ("dC", C.c_void_p), ("ddisturbance", C.c_void_p)]
+
+
+class PlantTangents(C.Structure):
+    """struct tpc_mpc_plant_tangents"""
+    _fields_ = [("tA", C.c_void_p), ("tB", C.c_void_p), ("tC", C.c_void_p), ("tdisturbance", C.c_void_p)]
 
 
 class Trajectories(C.Structure):
@@ -168,6 +186,15 @@ def load_library(path: str | None = None) -> C.CDLL:
                                                         C.POINTER(Tangents), vp, u32p, C.c_int, vp]
     lib.tpc_mpc_rollout_forward.argtypes = [vp, C.POINTER(Params), C.POINTER(GeneralIO), C.c_int32, vp, vp, vp,
                                             C.POINTER(Tangents), vp, vp, u32p, C.c_int, vp]
+    lib.tpc_mpc_rollout_plant.argtypes = [vp, C.POINTER(Params), C.POINTER(GeneralIO), C.POINTER(Plant), C.c_int32,
+                                          C.c_int32, vp, C.POINTER(Polish), C.c_int32, vp, vp, vp, vp, vp, u32p,
+                                          C.c_int, vp]
+    lib.tpc_mpc_rollout_plant_backward.argtypes = [vp, C.POINTER(Params), C.POINTER(GeneralIO), C.POINTER(Plant),
+                                                   C.c_int32, vp, C.POINTER(RolloutGrad), C.POINTER(PlantGrad), u32p,
+                                                   C.c_int, vp]
+    lib.tpc_mpc_rollout_plant_forward.argtypes = [vp, C.POINTER(Params), C.POINTER(GeneralIO), C.POINTER(Plant),
+                                                  C.c_int32, vp, vp, vp, C.POINTER(Tangents),
+                                                  C.POINTER(PlantTangents), vp, vp, u32p, C.c_int, vp]
     lib.tpc_mpc_set_profiling.argtypes = [vp, C.c_int]
     lib.tpc_mpc_last_kernel_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                               C.POINTER(C.c_int)]

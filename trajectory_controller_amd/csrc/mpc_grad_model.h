@@ -57,6 +57,24 @@ struct RollArgs {
     double *dA, *dB, *dC, *dQ, *dR, *dlo, *dhi, *dx0, *dtargets, *dnlt, *kkt;
 };
 
+// The separate plant of tpc_mpc_rollout_plant_backward: x_{k+1} = Ap x_k + Bp u0_k + Cp (+ d_k).  A, B, C are never
+// null here: the caller passes the controller's arrays again when it gave no plant, with separate = 0, and the plant
+// terms then go into the controller's dA, dB, dC as in rollout_instance<I, false>.  With separate = 1 they go to dA,
+// dB, dC below (any may be null) and the controller's receive qp_step's contributions only.  dd [steps*2] (leading
+// dimension ld_d, may be null) receives mu_k = dL/dx_{k+1}, the gradient of the disturbance's row k.
+struct RollPlant {
+    const double *A, *B, *C;
+    double *dA, *dB, *dC, *dd;
+    int64_t ld_d;
+    int separate;
+};
+
+// the plant's own gradient sums (RollPlant::separate): the fields of Sums the plant line adds to
+struct PlantSums {
+    double A00 = 0.0, A01 = 0.0, A10 = 0.0, A11 = 0.0, C0 = 0.0, C1 = 0.0;
+    double B0[2] = {0.0, 0.0}, B1[2] = {0.0, 0.0};
+};
+
 // workspace doubles per step: gain + feed-forward (3 I) in pass 1, x, dx, w (4 + I) from pass 2 on
 TPC_GRAD_HD constexpr int slots(int I) { return 4 + I; }
 
@@ -318,8 +336,11 @@ TPC_GRAD_HD uint32_t instance(const Args& a, int H, int64_t k, double* ws, int64
 //   T_k[t] = targets[t+k] for t + k <= H-1, else nlt[t+k-(H-1)] (targets[H-1] without nlt).
 // dL/dT_k is added into dtargets / dnlt through the same map, so both are zeroed first.  lambda = dL/dx_k carries the
 // state gradient from step to step in registers; the workspace is reused by every step.
-template <int I>
-TPC_GRAD_HD uint32_t rollout_instance(const RollArgs& a, int H, int64_t k, double* ws, int64_t wn) {
+// With Plant (tpc_mpc_rollout_plant_backward) the state moves with pl's arrays: they are read at the step, where the
+// update's terms are formed, and not held across the horizon passes.
+template <int I, bool Plant = false>
+TPC_GRAD_HD uint32_t rollout_instance(const RollArgs& a, int H, int64_t k, double* ws, int64_t wn,
+                                      const RollPlant* pl = nullptr) {
     const int64_t ld = a.ld;
     const int S = a.steps;
     const int HI = H * I;
@@ -334,6 +355,7 @@ TPC_GRAD_HD uint32_t rollout_instance(const RollArgs& a, int H, int64_t k, doubl
         for (int64_t c = 0; c < 2 * (int64_t)S; ++c) at(a.dnlt, c) = 0.0;
 
     Sums s;
+    PlantSums ps;   // the plant's own sums (Plant with pl->separate; unused otherwise)
     double l0 = 0.0, l1 = 0.0;   // lambda = dL/dx_{k+1} from the steps after k
     for (int kk = S - 1; kk >= 0; --kk) {
         const double gx0 = a.gx ? in(a.gx, 2 * (int64_t)kk) : 0.0, gx1 = a.gx ? in(a.gx, 2 * (int64_t)kk + 1) : 0.0;
@@ -342,22 +364,35 @@ TPC_GRAD_HD uint32_t rollout_instance(const RollArgs& a, int H, int64_t k, doubl
         const double xs1 = kk == 0 ? in(a.x0, 1) : in(a.states, 2 * (int64_t)kk - 1);
         fin = fin && gfinite(gx0) && gfinite(gx1) && gfinite(xs0) && gfinite(xs1);
         const int64_t sq = (int64_t)kk * HI;   // first row of U_k
-        // the plant update x_{k+1} = A x_k + B u0_k + C
-        s.A00 = gfma(mu0, xs0, s.A00);
-        s.A01 = gfma(mu0, xs1, s.A01);
-        s.A10 = gfma(mu1, xs0, s.A10);
-        s.A11 = gfma(mu1, xs1, s.A11);
-        s.C0 = s.C0 + mu0;
-        s.C1 = s.C1 + mu1;
+        // the plant update x_{k+1} = A x_k + B u0_k + C: its terms go into t
         double g0[2];   // dL/du0_k = G_u[k] + B' mu
+        auto plant_terms = [&](auto& t) {
+            t.A00 = gfma(mu0, xs0, t.A00);
+            t.A01 = gfma(mu0, xs1, t.A01);
+            t.A10 = gfma(mu1, xs0, t.A10);
+            t.A11 = gfma(mu1, xs1, t.A11);
+            t.C0 = t.C0 + mu0;
+            t.C1 = t.C1 + mu1;
 #pragma unroll
-        for (int j = 0; j < I; ++j) {
-            const double u0 = in(a.seq, sq + j);
-            const double gu = a.gu ? in(a.gu, (int64_t)kk * I + j) : 0.0;
-            fin = fin && gfinite(gu);
-            s.B0[j] = gfma(mu0, u0, s.B0[j]);
-            s.B1[j] = gfma(mu1, u0, s.B1[j]);
-            g0[j] = gfma(m.b0[j], mu0, gfma(m.b1[j], mu1, gu));
+            for (int j = 0; j < I; ++j) {
+                const double u0 = in(a.seq, sq + j);
+                const double gu = a.gu ? in(a.gu, (int64_t)kk * I + j) : 0.0;
+                fin = fin && gfinite(gu);
+                t.B0[j] = gfma(mu0, u0, t.B0[j]);
+                t.B1[j] = gfma(mu1, u0, t.B1[j]);
+                double b0 = m.b0[j], b1 = m.b1[j];
+                if (Plant) {
+                    b0 = in(pl->B, j); b1 = in(pl->B, I + j);
+                    fin = fin && gfinite(b0) && gfinite(b1);
+                }
+                g0[j] = gfma(b0, mu0, gfma(b1, mu1, gu));
+            }
+        };
+        if (Plant && pl->separate) plant_terms(ps);
+        else plant_terms(s);
+        if (Plant && pl->dd) {
+            pl->dd[(2 * (int64_t)kk) * pl->ld_d + k] = mu0;
+            pl->dd[(2 * (int64_t)kk + 1) * pl->ld_d + k] = mu1;
         }
         // the target map of step kk: component c of T_kk[t] as (base array, component index)
         auto tmap = [&](int t, int c, const double** base) -> int64_t {
@@ -387,8 +422,16 @@ TPC_GRAD_HD uint32_t rollout_instance(const RollArgs& a, int H, int64_t k, doubl
                   },
                   ws, wn, s, dx00, dx01) && fin;
         // lambda_k = A' mu + dL/dx_k of the solve
-        l0 = gfma(m.a00, mu0, gfma(m.a10, mu1, dx00));
-        l1 = gfma(m.a01, mu0, gfma(m.a11, mu1, dx01));
+        if (Plant) {
+            const double a00 = in(pl->A, 0), a01 = in(pl->A, 1), a10 = in(pl->A, 2), a11 = in(pl->A, 3);
+            fin = fin && gfinite(a00) && gfinite(a01) && gfinite(a10) && gfinite(a11) && gfinite(in(pl->C, 0)) &&
+                  gfinite(in(pl->C, 1));
+            l0 = gfma(a00, mu0, gfma(a10, mu1, dx00));
+            l1 = gfma(a01, mu0, gfma(a11, mu1, dx01));
+        } else {
+            l0 = gfma(m.a00, mu0, gfma(m.a10, mu1, dx00));
+            l1 = gfma(m.a01, mu0, gfma(m.a11, mu1, dx01));
+        }
     }
 
     const uint32_t flags = (fin ? 0u : 0x1u) | (m.ok ? 0u : 0x4u);
@@ -398,6 +441,17 @@ TPC_GRAD_HD uint32_t rollout_instance(const RollArgs& a, int H, int64_t k, doubl
     if (zero && a.dnlt)
         for (int64_t c = 0; c < 2 * (int64_t)S; ++c) at(a.dnlt, c) = 0.0;
     store_sums<I>(s, zero, ld, k, a.dA, a.dB, a.dC, a.dQ, a.dR, a.dlo, a.dhi, a.kkt);
+    if (Plant) {
+        if (pl->separate) {
+            auto out = [&](double* base, int c, double v) { if (base) base[(int64_t)c * ld + k] = zero ? 0.0 : v; };
+            out(pl->dA, 0, ps.A00); out(pl->dA, 1, ps.A01); out(pl->dA, 2, ps.A10); out(pl->dA, 3, ps.A11);
+            out(pl->dC, 0, ps.C0); out(pl->dC, 1, ps.C1);
+#pragma unroll
+            for (int j = 0; j < I; ++j) { out(pl->dB, j, ps.B0[j]); out(pl->dB, I + j, ps.B1[j]); }
+        }
+        if (zero && pl->dd)
+            for (int64_t c = 0; c < 2 * (int64_t)S; ++c) pl->dd[c * pl->ld_d + k] = 0.0;
+    }
     if (a.dx0) {
         at(a.dx0, 0) = zero ? 0.0 : l0;
         at(a.dx0, 1) = zero ? 0.0 : l1;

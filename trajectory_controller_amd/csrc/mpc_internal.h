@@ -117,7 +117,10 @@ struct RolloutStepArgs {
     const int32_t* iters_step;    // [n] or null
     int32_t* iters_out;           // [steps] or null (ld_out)
     void* sequences_out;          // [steps*H*I] or null (ld_out): every step's solved sequence (tpc_mpc_rollout_record)
+    const void* disturbance;      // [steps*2] or null (ld_d): row `step` is added to the new state (tpc_mpc_rollout_plant)
+    int64_t ld_d;
 };
+// (a.disturbance != null selects the kernel built with the disturbance's add; the plant's arrays go in a.A, a.B, a.C)
 hipError_t launch_rollout_step(int dtype, const RolloutStepArgs& a, hipStream_t s);
 
 // mpc_follow.hip: batched front and back ends of the tobiMPC branch of cycle().

@@ -17,6 +17,8 @@ struct NewtonArgs {
     int32_t* fb_index;           // [n] the instances for the fallback, in no particular order; null: not collected
     uint32_t* fb_count;          // how many
     int32_t raise_not_polished;  // FALLBACK_NONE: an unverified instance raises TPC_MPC_FLAG_NOT_POLISHED here
+    int32_t plant;               // tpc_mpc_rollout_plant: r.A, r.B, r.C are set by the caller (the plant's arrays) and
+                                 // r.disturbance may be given; 0: the tail reads p's model, as tpc_mpc_rollout_newton
 };
 
 // Rows of `ld`-strided fp64 (or int32) SoA arrays moved between the batch (column index[j]) and the compact fallback

@@ -30,20 +30,34 @@ TPC_GRAD_HD int64_t per_step(int64_t k) {
 
 // One instance, every step.  Returns the flags of the step it stopped at (0: verified at every step) and that step in
 // *first.  Rows of the per-step outputs from *first on are cleared: status -1, everything else 0, and so is the
-// carried sequence.
-template <int I>
+// carried sequence.  With Plant (tpc_mpc_rollout_plant) the tail keeps the arrays a.r names -- the plant's, or the
+// controller's again where the caller gave none -- and adds the disturbance's row; a non-finite plant or disturbance
+// value stops the instance at step 0 with TPC_MPC_FLAG_NONFINITE, as a non-finite model does.
+template <int I, bool Plant = false>
 TPC_GRAD_HD uint32_t newton_instance(const NewtonArgs& a, int64_t k, double* ws0, int64_t wn, int32_t* first) {
     double* ws = ws0;
     polish::Args p = a.p;
     RolloutStepArgs r = a.r;
     // one working set (mpc_rollout_newton.h): naming it once keeps a single copy of these in scalar registers
     r.n = p.n; r.ld = p.ld; r.I = I;
-    r.A = p.A; r.B = p.B; r.C = p.C;
+    if (!Plant) { r.A = p.A; r.B = p.B; r.C = p.C; }
     r.x = const_cast<double*>(p.x0); r.targets = const_cast<double*>(p.targets); r.controls = p.u;
     const int H = r.H, S = r.steps;
     const int64_t ld = p.ld, lo = r.ld_out, k0 = k;
     uint32_t f = 0;
     int st = 0;
+    if (Plant) {   // a non-finite plant or disturbance value makes the state non-finite: step 0's polish then stops the
+                   // instance with TPC_MPC_FLAG_NONFINITE, and nothing has to be remembered across the steps
+        bool plant_fin = true;
+        const double *A = (const double*)r.A + k, *B = (const double*)r.B + k, *Cc = (const double*)r.C + k;
+        for (int c = 0; c < 4; ++c) plant_fin = plant_fin && grad::gfinite(A[(int64_t)c * ld]);
+        for (int c = 0; c < 2 * I; ++c) plant_fin = plant_fin && grad::gfinite(B[(int64_t)c * ld]);
+        for (int c = 0; c < 2; ++c) plant_fin = plant_fin && grad::gfinite(Cc[(int64_t)c * ld]);
+        if (r.disturbance)
+            for (int64_t c = 0; c < 2 * (int64_t)S; ++c)
+                plant_fin = plant_fin && grad::gfinite(((const double*)r.disturbance)[c * r.ld_d + k]);
+        if (!plant_fin) ((double*)r.x)[k] = __builtin_nan("");
+    }
     for (; st < S; ++st) {
         k = per_step(k0);
         ws = ws0 + (k - k0);
@@ -53,7 +67,7 @@ TPC_GRAD_HD uint32_t newton_instance(const NewtonArgs& a, int64_t k, double* ws0
         if (f) break;
         r.step = st;
         k = per_step(k0);
-        rollout_step_tail<double>(r, k);
+        rollout_step_tail<double, Plant>(r, k);
         if (r.iters_out) r.iters_out[(int64_t)st * lo + k] = 0;
         if (p.status) p.status += lo;
         if (p.res_in) p.res_in += lo;
@@ -79,12 +93,9 @@ TPC_GRAD_HD uint32_t newton_instance(const NewtonArgs& a, int64_t k, double* ws0
     return f;
 }
 
-template <int I>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(I == 2 ? 4 : 5))) void rollout_newton_kernel(NewtonArgs a, double* ws, uint32_t* flags) {
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= a.p.n) return;
-    int32_t first;
-    const uint32_t f = newton_instance<I>(a, k, ws + k, a.p.n, &first);
+// What a lane does with its instance's result: first_unverified, the flags, and its place in the fallback's queue
+// (one atomicAdd per wavefront).  Shared by the two kernels below.
+__device__ __forceinline__ void newton_finish(const NewtonArgs& a, int64_t k, uint32_t f, int32_t first, uint32_t* flags) {
     a.first_unverified[k] = first;
     const uint32_t raise = a.raise_not_polished ? f : (f & ~0x8u);
     if (raise) atomicOr(flags, raise);
@@ -98,6 +109,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(I == 2 ? 4 
     if (lane == leader) base = atomicAdd(a.fb_count, (uint32_t)__popcll(m));
     base = __shfl(base, leader);
     if (fb) a.fb_index[base + __popcll(m & ((1ull << lane) - 1ull))] = (int32_t)k;
+}
+
+template <int I>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(I == 2 ? 4 : 5))) void rollout_newton_kernel(NewtonArgs a, double* ws, uint32_t* flags) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= a.p.n) return;
+    int32_t first;
+    const uint32_t f = newton_instance<I>(a, k, ws + k, a.p.n, &first);
+    newton_finish(a, k, f, first, flags);
+}
+
+// ... against a separate plant (tpc_mpc_rollout_plant): the same lane, the same occupancy
+template <int I>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(I == 2 ? 4 : 5))) void rollout_plant_newton_kernel(NewtonArgs a, double* ws, uint32_t* flags) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= a.p.n) return;
+    int32_t first;
+    const uint32_t f = newton_instance<I, true>(a, k, ws + k, a.p.n, &first);
+    newton_finish(a, k, f, first, flags);
 }
 
 // column index[j] of the batch <-> column j of the compact batch, every row of every set
@@ -135,7 +165,11 @@ hipError_t rollout_newton(int I, const NewtonArgs& a, void* ws, uint32_t* flags,
     if (a.p.n <= 0) return hipSuccess;
     const int block = rollout_grad_block(a.p.n);
     const unsigned grid = (unsigned)((a.p.n + block - 1) / block);
-    if (I == 2)
+    if (a.plant && I == 2)
+        hipLaunchKernelGGL(rollout_plant_newton_kernel<2>, dim3(grid), dim3(block), 0, s, a, (double*)ws, flags);
+    else if (a.plant)
+        hipLaunchKernelGGL(rollout_plant_newton_kernel<1>, dim3(grid), dim3(block), 0, s, a, (double*)ws, flags);
+    else if (I == 2)
         hipLaunchKernelGGL(rollout_newton_kernel<2>, dim3(grid), dim3(block), 0, s, a, (double*)ws, flags);
     else
         hipLaunchKernelGGL(rollout_newton_kernel<1>, dim3(grid), dim3(block), 0, s, a, (double*)ws, flags);
@@ -148,8 +182,12 @@ uint32_t rollout_newton_host(int I, const NewtonArgs& a) {
     uint32_t flags = 0;
     for (int64_t k = 0; k < a.p.n; ++k) {
         int32_t first;
-        const uint32_t f = I == 2 ? newton_instance<2>(a, k, ws.data(), 1, &first)
-                                  : newton_instance<1>(a, k, ws.data(), 1, &first);
+        uint32_t f;
+        if (a.plant)
+            f = I == 2 ? newton_instance<2, true>(a, k, ws.data(), 1, &first)
+                       : newton_instance<1, true>(a, k, ws.data(), 1, &first);
+        else
+            f = I == 2 ? newton_instance<2>(a, k, ws.data(), 1, &first) : newton_instance<1>(a, k, ws.data(), 1, &first);
         a.first_unverified[k] = first;
         flags |= a.raise_not_polished ? f : (f & ~0x8u);
     }

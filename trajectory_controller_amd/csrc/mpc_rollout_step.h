@@ -4,13 +4,15 @@
 // (mpc_rollout.hip), the fused polish + step kernel (mpc_rollout_polish.hip) and the Newton-first loop
 // (mpc_rollout_newton.hip, kernel and host path); no fused multiply-add in it, and the units that include it are built
 // with -ffp-contract=off, so all give the same bits.
+// With Plant (tpc_mpc_rollout_plant) a.A, a.B, a.C are the plant's arrays and row `step` of a.disturbance, when there
+// is one, is added to the new state: one more plain add after the parent's arithmetic, none without a disturbance.
 #pragma once
 
 #include "mpc_internal.h"
 
 namespace tpc {
 
-template <typename T>
+template <typename T, bool Plant = false>
 __host__ __device__ __forceinline__ void rollout_step_tail(const RolloutStepArgs& a, int64_t k) {
     const int64_t ld = a.ld;
     const T* A = (const T*)a.A + k;
@@ -22,8 +24,13 @@ __host__ __device__ __forceinline__ void rollout_step_tail(const RolloutStepArgs
     T bu0 = B[0] * u[0], bu1 = B[(int64_t)a.I * ld] * u[0];
     if (a.I == 2) { bu0 = bu0 + B[ld] * u[ld]; bu1 = bu1 + B[3 * ld] * u[ld]; }
     const T x0 = x[0], x1 = x[ld];
-    const T n0 = ((A[0] * x0 + A[ld] * x1) + bu0) + Cc[0];
-    const T n1 = ((A[2 * ld] * x0 + A[3 * ld] * x1) + bu1) + Cc[ld];
+    T n0 = ((A[0] * x0 + A[ld] * x1) + bu0) + Cc[0];
+    T n1 = ((A[2 * ld] * x0 + A[3 * ld] * x1) + bu1) + Cc[ld];
+    if (Plant && a.disturbance) {
+        const T* d = (const T*)a.disturbance + k;
+        n0 = n0 + d[(2 * (int64_t)a.step) * a.ld_d];
+        n1 = n1 + d[(2 * (int64_t)a.step + 1) * a.ld_d];
+    }
     x[0] = n0; x[ld] = n1;
     const int64_t lo = a.ld_out;
     for (int j = 0; j < a.I; ++j) ((T*)a.controls_out)[((int64_t)a.step * a.I + j) * lo + k] = u[(int64_t)j * ld];

@@ -61,6 +61,17 @@ struct RollArgs {
     double *tu, *tx;
 };
 
+// The separate plant of tpc_mpc_rollout_plant_forward: tx_{k+1} = tAp x_k + Ap tx_k + tBp u0_k + Bp tu0_k + tCp + td_k.
+// A, B, C are never null here and tA, tB, tC ([K*4], [K*2I], [K*2] stacked blocks, null = zero) are their tangents:
+// the plant's, while the model's enter the step's QP only -- or, when the caller gave no plant, the controller's arrays
+// and tangents again, which then move the state as in rollout_instance<I, false>.  The tangents are read through their
+// arrays at the plant line (a choice between a read and a held value there costs the lane a wave of occupancy).
+// td [K*steps*2] with the leading dimension ld_d, null = zero: no add at all.
+struct RollPlant {
+    const double *A, *B, *C, *tA, *tB, *tC, *td;
+    int64_t ld_d;
+};
+
 // workspace doubles per step: x_{t+1}, tx_{t+1}; the single solve adds gain (2 I) and feed-forward (I)
 TPC_GRAD_HD constexpr int slots(int I, bool whole) { return whole ? 4 + 3 * I : 4; }
 
@@ -71,6 +82,13 @@ TPC_GRAD_HD int64_t per_step(int64_t k) {
     asm volatile("" : "+v"(k));
 #endif
     return k;
+}
+
+// Nothing is scheduled across this point (device only): a group of loads is consumed before the next is issued.
+TPC_GRAD_HD void group_end() {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_amdgcn_sched_barrier(0);
+#endif
 }
 
 // the model's tangent in direction d of instance k (the fields of Model that carry a tangent; fin = all finite)
@@ -272,9 +290,11 @@ TPC_GRAD_HD uint32_t instance(const Args& a, int H, int d, int64_t k, double* ws
 // Direction d of instance k of the closed loop: the sweep over the steps (include/tpc_mpc.h, tpc_mpc_rollout_forward).
 // Step kk solves from x_kk (x0, then the recorded states[kk-1]) with the targets T_kk of grad::rollout_instance's map;
 // tT_kk comes from ttargets / tnlt through the same map.  tx_kk is carried from step to step in registers; the
-// workspace is reused by every step.
-template <int I>
-TPC_GRAD_HD uint32_t rollout_instance(const RollArgs& a, int H, int d, int64_t k0, double* ws0, int64_t wn) {
+// workspace is reused by every step.  With Plant (tpc_mpc_rollout_plant_forward) the state's tangent moves with pl's
+// arrays and tangents: they are read at the step's last line and not held across the horizon passes.
+template <int I, bool Plant = false>
+TPC_GRAD_HD uint32_t rollout_instance(const RollArgs& a, int H, int d, int64_t k0, double* ws0, int64_t wn,
+                                      const RollPlant* pl = nullptr) {
     const int64_t ld = a.ld;
     const int S = a.steps;
     const int HI = H * I;
@@ -319,6 +339,61 @@ TPC_GRAD_HD uint32_t rollout_instance(const RollArgs& a, int H, int d, int64_t k
                       return w ? tin(a.t.tnlt, 2 * (int64_t)S, i) : tin(a.t.ttargets, 2 * H, i);
                   },
                   [](int, int, double) {}, ws, wn, tu0) && fin;
+        if (Plant) {   // the same line on the plant's values, then the disturbance's tangent
+            // (read in three groups, the index re-made before each: the values' addresses are formed where they are
+            // used and no group is held while the next is read, so the lane stays in its parent's occupancy bracket)
+            // a null tangent is zero: the read goes to the primal array instead and its value is dropped, so that the
+            // plant line holds no branch (a branch per array costs the lane its parent's occupancy)
+            // (the direction is re-made opaque like the index: its row offsets are per lane and would be held too)
+            int64_t dq = d;
+            auto ptin = [&](const double* t, const double* primal, int64_t C, int64_t c) -> double {
+                const double* b = t ? t : primal;
+                const double v = b[((t ? dq : 0) * C + c) * ld + k];
+                return t ? v : 0.0;
+            };
+            k = per_step(k0);
+            dq = per_step(d);
+            const double tc0 = ptin(pl->tC, pl->C, 2, 0), tc1 = ptin(pl->tC, pl->C, 2, 1);
+            const double A00 = in(pl->A, 0), A01 = in(pl->A, 1), A10 = in(pl->A, 2), A11 = in(pl->A, 3);
+            fin = fin && gfinite(A00) && gfinite(A01) && gfinite(A10) && gfinite(A11) && gfinite(tc0) && gfinite(tc1) &&
+                  gfinite(in(pl->C, 0)) && gfinite(in(pl->C, 1));
+            double y0 = gfma(A00, tx0, gfma(A01, tx1, tc0));
+            double y1 = gfma(A10, tx0, gfma(A11, tx1, tc1));
+            group_end();
+            k = per_step(k0);
+            dq = per_step(d);
+            const double T00 = ptin(pl->tA, pl->A, 4, 0), T01 = ptin(pl->tA, pl->A, 4, 1);
+            const double T10 = ptin(pl->tA, pl->A, 4, 2), T11 = ptin(pl->tA, pl->A, 4, 3);
+            fin = fin && gfinite(T00) && gfinite(T01) && gfinite(T10) && gfinite(T11);
+            y0 = gfma(T00, xs0, gfma(T01, xs1, y0));
+            y1 = gfma(T10, xs0, gfma(T11, xs1, y1));
+            group_end();
+            k = per_step(k0);
+            dq = per_step(d);
+#pragma unroll
+            for (int j = 0; j < I; ++j) {
+                const double u0 = in(a.seq, sq + j);
+                const double b0 = in(pl->B, j), b1 = in(pl->B, I + j);
+                const double tb0 = ptin(pl->tB, pl->B, 2 * I, j), tb1 = ptin(pl->tB, pl->B, 2 * I, I + j);
+                fin = fin && gfinite(b0) && gfinite(b1) && gfinite(tb0) && gfinite(tb1);
+                y0 = gfma(tb0, u0, gfma(b0, tu0[j], y0));
+                y1 = gfma(tb1, u0, gfma(b1, tu0[j], y1));
+                a.tu[(urow + (int64_t)kk * I + j) * ld + k] = tu0[j];
+            }
+            if (pl->td) {
+                const double* td = pl->td + (dq * 2 * S + 2 * (int64_t)kk) * pl->ld_d + k;
+                const double e0 = td[0], e1 = td[pl->ld_d];
+                fin = fin && gfinite(e0) && gfinite(e1);
+                y0 = y0 + e0;
+                y1 = y1 + e1;
+            }
+            tx0 = y0; tx1 = y1;
+            if (a.tx) {
+                a.tx[(xrow + 2 * (int64_t)kk) * ld + k] = tx0;
+                a.tx[(xrow + 2 * (int64_t)kk + 1) * ld + k] = tx1;
+            }
+            continue;
+        }
         // the plant's tangent: tx_{kk+1} = tA x + A tx + tB u0 + B tu0 + tC
         double y0 = gfma(tm.a00, xs0, gfma(tm.a01, xs1, gfma(m.a00, tx0, gfma(m.a01, tx1, tm.c0))));
         double y1 = gfma(tm.a10, xs0, gfma(tm.a11, xs1, gfma(m.a10, tx0, gfma(m.a11, tx1, tm.c1))));

@@ -52,6 +52,9 @@ uint32_t grad_general_host(int I, int H, const grad::Args& a);
 // ... and of the closed loop (mpc_rollout_grad.hip), on the same per-step workspace
 hipError_t rollout_grad(int I, int H, const grad::RollArgs& a, void* ws, uint32_t* flags, hipStream_t s);
 uint32_t rollout_grad_host(int I, int H, const grad::RollArgs& a);
+hipError_t rollout_plant_grad(int I, int H, const grad::RollArgs& a, const grad::RollPlant& pl, void* ws, uint32_t* flags,
+                              hipStream_t s);
+uint32_t rollout_plant_grad_host(int I, int H, const grad::RollArgs& a, const grad::RollPlant& pl);
 // the polish of the general form (mpc_polish.hip), on the gradient workspace grown by the working copy of u
 int64_t polish_scratch_bytes(int I, int H, int64_t n);
 hipError_t polish_general(int I, int H, const polish::Args& a, void* ws, uint32_t* flags, hipStream_t s);
@@ -67,6 +70,9 @@ hipError_t tangent_general(int I, int H, const tangent::Args& a, void* ws, uint3
 uint32_t tangent_general_host(int I, int H, const tangent::Args& a);
 hipError_t rollout_tangent(int I, int H, const tangent::RollArgs& a, void* ws, uint32_t* flags, hipStream_t s);
 uint32_t rollout_tangent_host(int I, int H, const tangent::RollArgs& a);
+hipError_t rollout_plant_tangent(int I, int H, const tangent::RollArgs& a, const tangent::RollPlant& pl, void* ws,
+                                 uint32_t* flags, hipStream_t s);
+uint32_t rollout_plant_tangent_host(int I, int H, const tangent::RollArgs& a, const tangent::RollPlant& pl);
 
 thread_local char g_create_error[kTpcErrLen] = "";
 }  // namespace tpc
@@ -812,7 +818,7 @@ namespace {
 template <class Run>
 int forward_run(tpc_mpc_context* h, const tpc_mpc_general_io* io, int mem, void* stream, uint32_t* flags_out,
                 int64_t ws_bytes, const void* const* src, void* const* dst, const int64_t* rows, int nin, int nout,
-                Run run) {
+                Run run, const int64_t* src_ld = nullptr) {   // src_ld[c]: leading dimension of src[c] where not io->ld (0: io->ld)
     const int64_t n = io->n;
     if (h->host_only) {   // on the calling thread, straight from and into the caller's arrays
         uint32_t f = 0;
@@ -846,7 +852,8 @@ int forward_run(tpc_mpc_context* h, const tpc_mpc_general_io* io, int mem, void*
         for (int c = 0; c < nin; ++c) {
             sin[c] = src[c] ? b + off[c] : nullptr;
             if (src[c])
-                HIP_TRY(h, copy_rows(b + off[c], lds * 8, src[c], io->ld * 8, n * 8, rows[c], hipMemcpyHostToDevice, s));
+                HIP_TRY(h, copy_rows(b + off[c], lds * 8, src[c], (src_ld && src_ld[c] ? src_ld[c] : io->ld) * 8, n * 8,
+                                     rows[c], hipMemcpyHostToDevice, s));
         }
         for (int c = 0; c < nout; ++c) sout[c] = dst[c] ? b + off[nin + c] : nullptr;
         ld = lds;
@@ -1378,10 +1385,11 @@ namespace {
 int rollout_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io, int32_t steps,
                  const void* new_last_targets, void* controls_out, void* states_out, int32_t* iters_out,
                  void* sequences_out, bool record, bool polished, const tpc_mpc_polish* q, uint32_t* flags_out, int mem,
-                 void* stream) {
+                 void* stream, const tpc_mpc_plant* plant = nullptr) {
     return guarded(h, [&]() -> int {
         // the polished loop checks its arguments before it asks for the device, so that a host-only handle reports them
-        int rc = check_common(h, p, polished);
+        // (plant: tpc_mpc_rollout_plant, which has checked the plant itself; null: the controller's model moves the state)
+        int rc = check_common(h, p, polished || plant);
         if (rc) return rc;
         if (polished && p->dtype != TPC_MPC_F64)
             return fail(h, TPC_MPC_ERR_BAD_ARG, "tpc_mpc_rollout_polished is fp64 only: p->dtype must be TPC_MPC_F64");
@@ -1424,6 +1432,12 @@ int rollout_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_genera
         int64_t off[12], total = 0;
         for (int c = 0; c < 12; ++c) { off[c] = total; total += pad256((int64_t)comps[c] * ldw * es); }
         const int64_t o_iters = total; total += pad256(ldw * 4);
+        // ... and the plant's arrays and (HOST memory) the disturbance, behind everything the parent loop has
+        const bool plant_abc = plant && plant->A, plant_d = plant && plant->disturbance;
+        const int64_t o_pa = total; if (plant_abc) total += pad256(4 * ldw * es);
+        const int64_t o_pb = total; if (plant_abc) total += pad256(2 * I * ldw * es);
+        const int64_t o_pc = total; if (plant_abc) total += pad256(2 * ldw * es);
+        const int64_t o_pd = total; if (plant_d && mem == TPC_MPC_HOST) total += pad256((int64_t)steps * 2 * ldw * es);
         rc = ensure(h, &h->roll, &h->roll_bytes, total);
         if (rc) return rc;
         if (polished) {
@@ -1486,6 +1500,20 @@ int rollout_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_genera
         r.x = w + off[7]; r.targets = w + off[8]; r.controls = w + off[9]; r.new_last_targets = d_nlt;
         r.controls_out = d_ctrl; r.states_out = d_states;
         r.iters_step = a.iters; r.iters_out = d_iters; r.sequences_out = d_seq;
+        if (plant_abc) {
+            HIP_TRY(h, copy_rows(w + o_pa, ldw * es, plant->A, ld * es, n * es, 4, in_kind, s));
+            HIP_TRY(h, copy_rows(w + o_pb, ldw * es, plant->B, ld * es, n * es, 2 * I, in_kind, s));
+            HIP_TRY(h, copy_rows(w + o_pc, ldw * es, plant->C, ld * es, n * es, 2, in_kind, s));
+            r.A = w + o_pa; r.B = w + o_pb; r.C = w + o_pc;
+        }
+        if (plant_d) {
+            r.disturbance = plant->disturbance; r.ld_d = plant->ld_d;
+            if (host) {
+                HIP_TRY(h, copy_rows(w + o_pd, ldw * es, plant->disturbance, plant->ld_d * es, n * es, (int64_t)steps * 2,
+                                     hipMemcpyHostToDevice, s));
+                r.disturbance = w + o_pd; r.ld_d = ldw;
+            }
+        }
 
         polish::Args pa;
         std::memset(&pa, 0, sizeof(pa));
@@ -1572,10 +1600,12 @@ int tpc_mpc_rollout_record(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_
 // with TPC_MPC_NEWTON_FALLBACK_SOLVE the instances it could not verify are gathered into a compact batch, run through
 // rollout_impl's polished mode from step 0 and scattered back.  One 4-byte read-back (the fallback's count) sits between
 // the phases; a host-only handle runs phase 1 on the calling thread.
-int tpc_mpc_rollout_newton(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io, int32_t steps,
-                           const void* new_last_targets, const tpc_mpc_polish* q, int32_t fallback, void* controls_out,
-                           void* states_out, int32_t* iters_out, void* sequences_out, int32_t* first_unverified,
-                           uint32_t* flags_out, int mem, void* stream) {
+// (plant: tpc_mpc_rollout_plant, which has checked it; null: tpc_mpc_rollout_newton)
+static int rollout_newton_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io, int32_t steps,
+                               const void* new_last_targets, const tpc_mpc_polish* q, int32_t fallback,
+                               void* controls_out, void* states_out, int32_t* iters_out, void* sequences_out,
+                               int32_t* first_unverified, uint32_t* flags_out, int mem, void* stream,
+                               const tpc_mpc_plant* plant) {
     return guarded(h, [&]() -> int {
         int rc = check_common(h, p, true);
         if (rc) return rc;
@@ -1603,19 +1633,24 @@ int tpc_mpc_rollout_newton(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_
         // the working set: a copy of the model, then x0, targets, controls and v AS GIVEN (what the fallback restarts
         // from), row after row with one leading dimension
         //   0 A[4] 1 B[2I] 2 C[2] 3 Q[2] 4 R[I] 5 lo[I] 6 hi[I] 7 x[2] 8 targets[2H] 9 controls[HI] 10 v[HI]
-        const int comps[11] = {4, 2 * I, 2, 2, I, I, I, 2, 2 * H, H * I, H * I};
-        const void* src[11] = {io->A, io->B, io->C, io->Q, io->R, io->lower, io->upper, io->x0, io->targets,
-                               io->controls_inout, io->v_inout};
-        int64_t row[12];
+        //   11 Ap[4] 12 Bp[2I] 13 Cp[2]: the plant's arrays when tpc_mpc_rollout_plant gave some (no rows otherwise)
+        const bool plant_abc = plant && plant->A, plant_d = plant && plant->disturbance;
+        const int comps[14] = {4, 2 * I, 2, 2, I, I, I, 2, 2 * H, H * I, H * I,
+                               plant_abc ? 4 : 0, plant_abc ? 2 * I : 0, plant_abc ? 2 : 0};
+        const void* src[14] = {io->A, io->B, io->C, io->Q, io->R, io->lower, io->upper, io->x0, io->targets,
+                               io->controls_inout, io->v_inout, plant_abc ? plant->A : nullptr,
+                               plant_abc ? plant->B : nullptr, plant_abc ? plant->C : nullptr};
+        int64_t row[15];
         row[0] = 0;
-        for (int c = 0; c < 11; ++c) row[c + 1] = row[c] + comps[c];
-        const int64_t rows_in = row[11], rows_work = 2 + 2 * H + H * I;   // ... and the state the loop carries: x, targets, controls
+        for (int c = 0; c < 14; ++c) row[c + 1] = row[c] + comps[c];
+        const int64_t rows_in = row[14], rows_work = 2 + 2 * H + H * I;   // ... and the state the loop carries: x, targets, controls
 
         NewtonArgs a;
         std::memset(&a, 0, sizeof(a));
         a.p.n = n; a.p.tol = q->tol; a.p.max_rounds = q->max_rounds;
         a.r.n = n; a.r.I = I; a.r.H = H; a.r.steps = steps;
         a.raise_not_polished = solve ? 0 : 1;
+        a.plant = (plant_abc || plant_d) ? 1 : 0;
         auto bind = [&](char* w, int64_t ldw) {   // w: rows_in rows as given, then rows_work rows of carried state
             auto at = [&](int64_t r) { return (double*)(w + r * ldw * 8); };
             a.p.ld = a.r.ld = ldw;
@@ -1623,6 +1658,7 @@ int tpc_mpc_rollout_newton(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_
             a.p.lo = at(row[5]); a.p.hi = at(row[6]);
             a.p.x0 = at(rows_in); a.p.targets = at(rows_in + 2); a.p.u = at(rows_in + 2 + 2 * H);
             a.r.A = a.p.A; a.r.B = a.p.B; a.r.C = a.p.C;
+            if (plant_abc) { a.r.A = at(row[11]); a.r.B = at(row[12]); a.r.C = at(row[13]); }
             a.r.x = at(rows_in); a.r.targets = at(rows_in + 2); a.r.controls = a.p.u;
         };
 
@@ -1633,6 +1669,10 @@ int tpc_mpc_rollout_newton(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_
                 if (src[c])
                     for (int64_t r = 0; r < comps[c]; ++r)
                         std::memcpy(&w[(size_t)((row[c] + r) * n)], (const double*)src[c] + r * ld, (size_t)n * 8);
+            for (int c = 11; c < 14; ++c)
+                for (int64_t r = 0; r < comps[c]; ++r)
+                    std::memcpy(&w[(size_t)((row[c] + r) * n)], (const double*)src[c] + r * ld, (size_t)n * 8);
+            if (plant_d) { a.r.disturbance = plant->disturbance; a.r.ld_d = plant->ld_d; }
             std::memcpy(&w[(size_t)(rows_in * n)], &w[(size_t)(row[7] * n)], (size_t)(rows_work * n) * 8);
             bind((char*)w.data(), n);
             a.r.ld_out = a.r.ld_nlt = ld;
@@ -1665,7 +1705,8 @@ int tpc_mpc_rollout_newton(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_
         rc = ensure(h, &h->grad_ws, &h->grad_ws_bytes, pad256(polish_scratch_bytes(I, H, n)));
         if (rc) return rc;
         char* w = (char*)h->newton;
-        for (int c = 0; c < 11; ++c) {
+        for (int c = 0; c < 14; ++c) {
+            if (comps[c] == 0) continue;
             if (src[c]) HIP_TRY(h, copy_rows(w + row[c] * ldw * 8, ldw * 8, src[c], ld * 8, n * 8, comps[c], in_kind, s));
             else HIP_TRY(h, hipMemsetAsync(w + row[c] * ldw * 8, 0, (size_t)(comps[c] * ldw * 8), s));
         }
@@ -1682,6 +1723,8 @@ int tpc_mpc_rollout_newton(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_
         char *d_ctrl = (char*)controls_out, *d_states = (char*)states_out, *d_seq = (char*)sequences_out;
         int32_t *d_iters = iters_out, *d_status = q->status;
         char *d_rin = (char*)q->residual_in, *d_rout = (char*)q->residual_out;
+        const void* d_dist = plant_d ? plant->disturbance : nullptr;
+        int64_t ld_dist = plant_d ? plant->ld_d : 0;
         if (host) {
             const int64_t s_nlt = 0, s_ctrl = s_nlt + pad256((int64_t)steps * 2 * ldw * 8);
             const int64_t s_states = s_ctrl + pad256((int64_t)steps * I * ldw * 8);
@@ -1690,7 +1733,8 @@ int tpc_mpc_rollout_newton(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_
             const int64_t s_status = s_seq + (sequences_out ? pad256((int64_t)steps * H * I * ldw * 8) : 0);
             const int64_t s_rin = s_status + (d_status ? pad256((int64_t)steps * ldw * 4) : 0);
             const int64_t s_rout = s_rin + (d_rin ? pad256((int64_t)steps * ldw * 8) : 0);
-            const int64_t s_end = s_rout + (d_rout ? pad256((int64_t)steps * ldw * 8) : 0);
+            const int64_t s_dist = s_rout + (d_rout ? pad256((int64_t)steps * ldw * 8) : 0);
+            const int64_t s_end = s_dist + (plant_d ? pad256((int64_t)steps * 2 * ldw * 8) : 0);
             rc = ensure(h, &h->stage, &h->stage_bytes, s_end);
             if (rc) return rc;
             char* b = (char*)h->stage;
@@ -1698,6 +1742,11 @@ int tpc_mpc_rollout_newton(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_
                 HIP_TRY(h, copy_rows(b + s_nlt, ldw * 8, new_last_targets, ld * 8, n * 8, (int64_t)steps * 2,
                                      hipMemcpyHostToDevice, s));
                 d_nlt = b + s_nlt;
+            }
+            if (plant_d) {
+                HIP_TRY(h, copy_rows(b + s_dist, ldw * 8, plant->disturbance, plant->ld_d * 8, n * 8, (int64_t)steps * 2,
+                                     hipMemcpyHostToDevice, s));
+                d_dist = b + s_dist; ld_dist = ldw;
             }
             ld_nlt = ld_out = ldw;
             d_ctrl = b + s_ctrl;
@@ -1712,6 +1761,7 @@ int tpc_mpc_rollout_newton(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_
         bind(w, ldw);
         a.r.ld_out = ld_out; a.r.ld_nlt = ld_nlt;
         a.r.new_last_targets = d_nlt;
+        a.r.disturbance = d_dist; a.r.ld_d = ld_dist;
         a.r.controls_out = d_ctrl; a.r.states_out = d_states; a.r.iters_out = d_iters; a.r.sequences_out = d_seq;
         a.p.status = d_status; a.p.res_in = (double*)d_rin; a.p.res_out = (double*)d_rout;
         a.first_unverified = d_fu;
@@ -1736,6 +1786,7 @@ int tpc_mpc_rollout_newton(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_
             const int64_t r_nlt = take(d_nlt != nullptr, S * 2), r_ctrl = take(true, S * I);
             const int64_t r_states = take(d_states != nullptr, S * 2), r_seq = take(d_seq != nullptr, S * H * I);
             const int64_t r_rin = take(d_rin != nullptr, S), r_rout = take(d_rout != nullptr, S);
+            const int64_t r_dist = take(d_dist != nullptr, S * 2);
             const int64_t o_i32 = r_total * ldc * 8;   // int32 rows behind the fp64 ones: iters, status
             rc = ensure(h, &h->newton_fb, &h->newton_fb_bytes, o_i32 + 2 * S * ldc * 4);
             if (rc) return rc;
@@ -1749,6 +1800,7 @@ int tpc_mpc_rollout_newton(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_
             g.count = cnt; g.index = d_idx;
             g.set[g.sets++] = NewtonRows{w, fb, rows_in, ldw, ldc, 8};
             if (d_nlt) g.set[g.sets++] = NewtonRows{d_nlt, fat(r_nlt), S * 2, ld_nlt, ldc, 8};
+            if (d_dist) g.set[g.sets++] = NewtonRows{d_dist, fat(r_dist), S * 2, ld_dist, ldc, 8};
             e = rollout_newton_move(g, false, s);
             if (e != hipSuccess) return hip_fail(h, e, "gather launch");
 
@@ -1761,8 +1813,13 @@ int tpc_mpc_rollout_newton(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_
             tpc_mpc_polish q2 = *q;
             q2.status = f_status; q2.residual_in = fat(r_rin); q2.residual_out = fat(r_rout);
             // its flags stay in the handle's word (no flags_out: no synchronisation); phase 1's are merged in below
+            // ... against the same plant: its gathered arrays and disturbance rows
+            tpc_mpc_plant plant2;
+            std::memset(&plant2, 0, sizeof(plant2));
+            if (plant_abc) { plant2.A = fat(row[11]); plant2.B = fat(row[12]); plant2.C = fat(row[13]); }
+            plant2.disturbance = fat(r_dist); plant2.ld_d = ldc;
             rc = rollout_impl(h, p, &io2, steps, fat(r_nlt), fat(r_ctrl), fat(r_states), f_iters, fat(r_seq), false, true,
-                              &q2, nullptr, TPC_MPC_DEVICE, stream);
+                              &q2, nullptr, TPC_MPC_DEVICE, stream, a.plant ? &plant2 : nullptr);
             if (rc) return rc;
 
             if (io->v_inout) {   // v out: the sequence for a Newton-only instance, the polished loop's v for the others
@@ -1816,17 +1873,74 @@ int tpc_mpc_rollout_newton(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_
     });
 }
 
-int tpc_mpc_rollout_backward(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io, int32_t steps,
-                             const void* new_last_targets, const tpc_mpc_rollout_grad* g, uint32_t* flags_out,
-                             int mem, void* stream) {
+int tpc_mpc_rollout_newton(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io, int32_t steps,
+                           const void* new_last_targets, const tpc_mpc_polish* q, int32_t fallback, void* controls_out,
+                           void* states_out, int32_t* iters_out, void* sequences_out, int32_t* first_unverified,
+                           uint32_t* flags_out, int mem, void* stream) {
+    return rollout_newton_impl(h, p, io, steps, new_last_targets, q, fallback, controls_out, states_out, iters_out,
+                               sequences_out, first_unverified, flags_out, mem, stream, nullptr);
+}
+
+// what the three plant entries check of a tpc_mpc_plant (after check_common and check_general_io)
+static int check_plant(tpc_mpc_context* h, const tpc_mpc_general_io* io, const tpc_mpc_plant* plant) {
+    if (!plant) return fail(h, TPC_MPC_ERR_BAD_ARG, "null plant struct");
+    const int given = (plant->A ? 1 : 0) + (plant->B ? 1 : 0) + (plant->C ? 1 : 0);
+    if (given != 0 && given != 3)
+        return fail(h, TPC_MPC_ERR_BAD_ARG, "the plant's A, B, C: all three or none");
+    if (plant->disturbance && plant->ld_d < io->n)
+        return fail(h, TPC_MPC_ERR_BAD_ARG, "the disturbance needs ld_d >= n");
+    return TPC_MPC_OK;
+}
+
+int tpc_mpc_rollout_plant(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io,
+                          const tpc_mpc_plant* plant, int32_t loop, int32_t steps, const void* new_last_targets,
+                          const tpc_mpc_polish* q, int32_t fallback, void* controls_out, void* states_out,
+                          int32_t* iters_out, void* sequences_out, int32_t* first_unverified, uint32_t* flags_out,
+                          int mem, void* stream) {
+    int rc = guarded(h, [&]() -> int {
+        int rc = check_common(h, p, true);
+        if (rc) return rc;
+        if (p->dtype != TPC_MPC_F64)
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "tpc_mpc_rollout_plant is fp64 only: p->dtype must be TPC_MPC_F64");
+        rc = check_general_io(h, io, mem);
+        if (rc) return rc;
+        rc = check_plant(h, io, plant);
+        if (rc) return rc;
+        if (loop != TPC_MPC_LOOP_RECORD && loop != TPC_MPC_LOOP_POLISHED && loop != TPC_MPC_LOOP_NEWTON)
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "unknown loop %d", (int)loop);
+        return TPC_MPC_OK;
+    });
+    if (rc) return rc;
+    if (loop == TPC_MPC_LOOP_NEWTON)
+        return rollout_newton_impl(h, p, io, steps, new_last_targets, q, fallback, controls_out, states_out, iters_out,
+                                   sequences_out, first_unverified, flags_out, mem, stream, plant);
+    const bool polished = loop == TPC_MPC_LOOP_POLISHED;
+    return rollout_impl(h, p, io, steps, new_last_targets, controls_out, states_out, iters_out, sequences_out, !polished,
+                        polished, polished ? q : nullptr, flags_out, mem, stream, plant);
+}
+
+// tpc_mpc_rollout_backward (plant and pg null) and tpc_mpc_rollout_plant_backward (both given, the plant checked below)
+static int rollout_backward_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io, int32_t steps,
+                                 const void* new_last_targets, const tpc_mpc_rollout_grad* g, uint32_t* flags_out,
+                                 int mem, void* stream, const char* name, bool with_plant, const tpc_mpc_plant* plant,
+                                 const tpc_mpc_plant_grad* pg) {
     return guarded(h, [&]() -> int {
         int rc = check_common(h, p, true);
         if (rc) return rc;
         if (p->dtype != TPC_MPC_F64)
-            return fail(h, TPC_MPC_ERR_BAD_ARG, "tpc_mpc_rollout_backward is fp64 only: p->dtype must be TPC_MPC_F64");
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "%s is fp64 only: p->dtype must be TPC_MPC_F64", name);
         rc = check_general_io(h, io, mem);
         if (rc) return rc;
         if (!g) return fail(h, TPC_MPC_ERR_BAD_ARG, "null gradient struct");
+        if (with_plant) {
+            rc = check_plant(h, io, plant);
+            if (rc) return rc;
+            if (!pg) return fail(h, TPC_MPC_ERR_BAD_ARG, "null plant gradient struct");
+            if (!plant->A && (pg->dA || pg->dB || pg->dC))
+                return fail(h, TPC_MPC_ERR_BAD_ARG, "the plant's dA, dB, dC asked for without the plant's A, B, C");
+            if (pg->ddisturbance && plant->ld_d != 0 && plant->ld_d < io->n)
+                return fail(h, TPC_MPC_ERR_BAD_ARG, "ddisturbance needs ld_d >= n (or 0: the io's ld)");
+        }
         if (steps < 0 || steps > (1 << 24)) return fail(h, TPC_MPC_ERR_BAD_ARG, "need 0 <= steps <= 2^24");
         if (g->dnew_last_targets && !new_last_targets)
             return fail(h, TPC_MPC_ERR_BAD_ARG, "dnew_last_targets asked for without new_last_targets");
@@ -1838,15 +1952,24 @@ int tpc_mpc_rollout_backward(tpc_mpc_handle h, const tpc_mpc_params* p, const tp
         if (!g->sequences || !g->states) return fail(h, TPC_MPC_ERR_BAD_ARG, "null sequences / states");
         const int I = io->inputs, H = p->horizon;
         const int64_t n = io->n, S = steps;
-        // the io's and g's arrays in order: 14 inputs (the optional ones may be null), then 11 outputs, with their
-        // component counts
-        const void* src[14] = {io->A, io->B, io->C, io->Q, io->R, io->lower, io->upper, io->x0, io->targets,
-                               new_last_targets, g->sequences, g->states, g->grad_controls, g->grad_states};
-        void* dst[11] = {g->dA, g->dB, g->dC, g->dQ, g->dR, g->dlower, g->dupper, g->dx0, g->dtargets,
-                         g->dnew_last_targets, g->kkt_residual};
-        const int64_t comps[25] = {4, 2 * I, 2, 2, I, I, I, 2, 2 * H, 2 * S, S * H * I, 2 * S, S * I, 2 * S,
-                                   4, 2 * I, 2, 2, I, I, I, 2, 2 * H, 2 * S, 1};
-        auto bind = [](grad::RollArgs* a, const void* const* in, void* const* out) {
+        // the plant kernel runs when the plant changes anything: its own arrays, or the disturbance's gradient
+        const bool sep = with_plant && plant->A, use_plant = sep || (with_plant && pg->ddisturbance);
+        const int64_t ld_dd = with_plant && plant->ld_d ? plant->ld_d : io->ld;   // of ddisturbance, in the caller's memory
+        // the io's, g's and the plant's arrays in order: 17 inputs (the optional ones may be null), then 15 outputs,
+        // with their component counts
+        constexpr int kIn = 17, kOut = 15;
+        const void* src[kIn] = {io->A, io->B, io->C, io->Q, io->R, io->lower, io->upper, io->x0, io->targets,
+                                new_last_targets, g->sequences, g->states, g->grad_controls, g->grad_states,
+                                sep ? plant->A : nullptr, sep ? plant->B : nullptr, sep ? plant->C : nullptr};
+        void* dst[kOut] = {g->dA, g->dB, g->dC, g->dQ, g->dR, g->dlower, g->dupper, g->dx0, g->dtargets,
+                           g->dnew_last_targets, g->kkt_residual, sep ? pg->dA : nullptr, sep ? pg->dB : nullptr,
+                           sep ? pg->dC : nullptr, use_plant ? pg->ddisturbance : nullptr};
+        const int64_t comps[kIn + kOut] = {4, 2 * I, 2, 2, I, I, I, 2, 2 * H, 2 * S, S * H * I, 2 * S, S * I, 2 * S,
+                                           4, 2 * I, 2,
+                                           4, 2 * I, 2, 2, I, I, I, 2, 2 * H, 2 * S, 1, 4, 2 * I, 2, 2 * S};
+        grad::RollPlant pl;
+        std::memset(&pl, 0, sizeof(pl));
+        auto bind = [&](grad::RollArgs* a, const void* const* in, void* const* out, int64_t ld_d) {
             a->A = (const double*)in[0]; a->B = (const double*)in[1]; a->C = (const double*)in[2];
             a->Q = (const double*)in[3]; a->R = (const double*)in[4]; a->lo = (const double*)in[5];
             a->hi = (const double*)in[6]; a->x0 = (const double*)in[7]; a->targets = (const double*)in[8];
@@ -1855,6 +1978,11 @@ int tpc_mpc_rollout_backward(tpc_mpc_handle h, const tpc_mpc_params* p, const tp
             a->dA = (double*)out[0]; a->dB = (double*)out[1]; a->dC = (double*)out[2]; a->dQ = (double*)out[3];
             a->dR = (double*)out[4]; a->dlo = (double*)out[5]; a->dhi = (double*)out[6]; a->dx0 = (double*)out[7];
             a->dtargets = (double*)out[8]; a->dnlt = (double*)out[9]; a->kkt = (double*)out[10];
+            pl.separate = sep ? 1 : 0;
+            pl.A = sep ? (const double*)in[14] : a->A; pl.B = sep ? (const double*)in[15] : a->B;
+            pl.C = sep ? (const double*)in[16] : a->C;
+            pl.dA = (double*)out[11]; pl.dB = (double*)out[12]; pl.dC = (double*)out[13]; pl.dd = (double*)out[14];
+            pl.ld_d = ld_d;
         };
         grad::RollArgs a;
         std::memset(&a, 0, sizeof(a));
@@ -1862,8 +1990,8 @@ int tpc_mpc_rollout_backward(tpc_mpc_handle h, const tpc_mpc_params* p, const tp
         a.steps = steps;
         if (h->host_only) {   // on the calling thread, straight from and into the caller's arrays
             a.ld = io->ld;
-            bind(&a, src, dst);
-            const uint32_t f = rollout_grad_host(I, H, a);
+            bind(&a, src, dst, ld_dd);
+            const uint32_t f = use_plant ? rollout_plant_grad_host(I, H, a, pl) : rollout_grad_host(I, H, a);
             if (flags_out) *flags_out = f;
             return TPC_MPC_OK;
         }
@@ -1875,48 +2003,64 @@ int tpc_mpc_rollout_backward(tpc_mpc_handle h, const tpc_mpc_params* p, const tp
         rc = ensure(h, &h->grad_ws, &h->grad_ws_bytes, pad256(grad_scratch_bytes(I, H, n)));
         if (rc) return rc;
         const int64_t lds = (n + 63) / 64 * 64;
-        int64_t off[25] = {0};
+        int64_t off[kIn + kOut] = {0};
         if (mem == TPC_MPC_DEVICE) {
             a.ld = io->ld;
-            bind(&a, src, dst);
+            bind(&a, src, dst, ld_dd);
         } else {
             // HOST arrays: every component row copied on its own (n elements, never ld), as tpc_mpc_solve_batch_general;
             // only the arrays given are staged
             int64_t total = 0;
-            for (int c = 0; c < 25; ++c) {
-                const bool given = c < 14 ? src[c] != nullptr : dst[c - 14] != nullptr;
+            for (int c = 0; c < kIn + kOut; ++c) {
+                const bool given = c < kIn ? src[c] != nullptr : dst[c - kIn] != nullptr;
                 off[c] = total;
                 if (given) total += pad256(comps[c] * lds * 8);
             }
             rc = ensure(h, &h->stage, &h->stage_bytes, total);
             if (rc) return rc;
             char* b = (char*)h->stage;
-            const void* sin[14];
-            void* sout[11];
-            for (int c = 0; c < 14; ++c) {
+            const void* sin[kIn];
+            void* sout[kOut];
+            for (int c = 0; c < kIn; ++c) {
                 sin[c] = src[c] ? b + off[c] : nullptr;
                 if (src[c])
                     HIP_TRY(h, copy_rows(b + off[c], lds * 8, src[c], io->ld * 8, n * 8, comps[c], hipMemcpyHostToDevice, s));
             }
-            for (int c = 0; c < 11; ++c) sout[c] = dst[c] ? b + off[14 + c] : nullptr;
+            for (int c = 0; c < kOut; ++c) sout[c] = dst[c] ? b + off[kIn + c] : nullptr;
             a.ld = lds;
-            bind(&a, sin, sout);
+            bind(&a, sin, sout, lds);
         }
         HIP_TRY(h, hipMemsetAsync(h->ws_words + 1, 0, sizeof(uint32_t), s));
-        hipError_t e = rollout_grad(I, H, a, h->grad_ws, h->ws_words + 1, s);
+        hipError_t e = use_plant ? rollout_plant_grad(I, H, a, pl, h->grad_ws, h->ws_words + 1, s)
+                                 : rollout_grad(I, H, a, h->grad_ws, h->ws_words + 1, s);
         if (e != hipSuccess) return hip_fail(h, e, "kernel launch");
         if (mem == TPC_MPC_HOST) {
             const char* b = (const char*)h->stage;
-            for (int c = 0; c < 11; ++c)
+            for (int c = 0; c < kOut; ++c)
                 if (dst[c])
-                    HIP_TRY(h, copy_rows(dst[c], io->ld * 8, b + off[14 + c], lds * 8, n * 8, comps[14 + c],
-                                         hipMemcpyDeviceToHost, s));
+                    HIP_TRY(h, copy_rows(dst[c], (c == 14 ? ld_dd : io->ld) * 8, b + off[kIn + c], lds * 8, n * 8,
+                                         comps[kIn + c], hipMemcpyDeviceToHost, s));
             HIP_TRY(h, hipStreamSynchronize(s));
         }
         rc = order.end();
         if (rc) return rc;
         return finish_flags(h, flags_out, s);
     });
+}
+
+int tpc_mpc_rollout_backward(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io, int32_t steps,
+                             const void* new_last_targets, const tpc_mpc_rollout_grad* g, uint32_t* flags_out,
+                             int mem, void* stream) {
+    return rollout_backward_impl(h, p, io, steps, new_last_targets, g, flags_out, mem, stream,
+                                 "tpc_mpc_rollout_backward", false, nullptr, nullptr);
+}
+
+int tpc_mpc_rollout_plant_backward(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io,
+                                   const tpc_mpc_plant* plant, int32_t steps, const void* new_last_targets,
+                                   const tpc_mpc_rollout_grad* g, const tpc_mpc_plant_grad* pg, uint32_t* flags_out,
+                                   int mem, void* stream) {
+    return rollout_backward_impl(h, p, io, steps, new_last_targets, g, flags_out, mem, stream,
+                                 "tpc_mpc_rollout_plant_backward", true, plant, pg);
 }
 
 int tpc_mpc_solve_batch_general_forward(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io,
@@ -1964,18 +2108,31 @@ int tpc_mpc_solve_batch_general_forward(tpc_mpc_handle h, const tpc_mpc_params* 
     });
 }
 
-int tpc_mpc_rollout_forward(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io, int32_t steps,
-                            const void* new_last_targets, const void* sequences, const void* states,
-                            const tpc_mpc_tangents* t, void* tcontrols, void* tstates, uint32_t* flags_out, int mem,
-                            void* stream) {
+// tpc_mpc_rollout_forward (with_plant false) and tpc_mpc_rollout_plant_forward
+static int rollout_forward_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io, int32_t steps,
+                                const void* new_last_targets, const void* sequences, const void* states,
+                                const tpc_mpc_tangents* t, void* tcontrols, void* tstates, uint32_t* flags_out, int mem,
+                                void* stream, const char* name, bool with_plant, const tpc_mpc_plant* plant,
+                                const tpc_mpc_plant_tangents* pt) {
     return guarded(h, [&]() -> int {
         int rc = check_common(h, p, true);
         if (rc) return rc;
         if (p->dtype != TPC_MPC_F64)
-            return fail(h, TPC_MPC_ERR_BAD_ARG, "tpc_mpc_rollout_forward is fp64 only: p->dtype must be TPC_MPC_F64");
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "%s is fp64 only: p->dtype must be TPC_MPC_F64", name);
         rc = check_general_io(h, io, mem);
         if (rc) return rc;
         if (!t) return fail(h, TPC_MPC_ERR_BAD_ARG, "null tangent struct");
+        tpc_mpc_plant_tangents none;
+        std::memset(&none, 0, sizeof(none));
+        if (with_plant) {
+            rc = check_plant(h, io, plant);
+            if (rc) return rc;
+            if (!pt) pt = &none;
+            if (!plant->A && (pt->tA || pt->tB || pt->tC))
+                return fail(h, TPC_MPC_ERR_BAD_ARG, "the plant's tA, tB, tC given without the plant's A, B, C");
+            if (pt->tdisturbance && plant->ld_d != 0 && plant->ld_d < io->n)
+                return fail(h, TPC_MPC_ERR_BAD_ARG, "tdisturbance needs ld_d >= n (or 0: the io's ld)");
+        }
         if (steps < 0 || steps > (1 << 24)) return fail(h, TPC_MPC_ERR_BAD_ARG, "need 0 <= steps <= 2^24");
         if (t->directions < 1 || (int64_t)t->directions * io->n > 0x7fffffffll)
             return fail(h, TPC_MPC_ERR_BAD_ARG, "need directions >= 1 and directions * n < 2^31");
@@ -1989,16 +2146,28 @@ int tpc_mpc_rollout_forward(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc
         if (!sequences || !states || !tcontrols) return fail(h, TPC_MPC_ERR_BAD_ARG, "null sequences / states / tcontrols");
         const int I = io->inputs, H = p->horizon, K = t->directions;
         const int64_t n = io->n, S = steps;
-        // twelve primal inputs (new_last_targets may be null), ten tangents (K stacked blocks each), two outputs
-        const void* src[22] = {io->A, io->B, io->C, io->Q, io->R, io->lower, io->upper, io->x0, io->targets,
-                               new_last_targets, sequences, states,
-                               t->tA, t->tB, t->tC, t->tQ, t->tR, t->tlower, t->tupper, t->tx0, t->ttargets,
-                               t->tnew_last_targets};
+        // the plant kernel runs when the plant changes anything: its own arrays, or the disturbance's tangent
+        const bool sep = with_plant && plant->A, use_plant = sep || (with_plant && pt->tdisturbance);
+        const int64_t ld_td = with_plant && plant->ld_d ? plant->ld_d : io->ld;   // of tdisturbance, in the caller's memory
+        const bool staged = !h->host_only && mem == TPC_MPC_HOST;
+        // twelve primal inputs (new_last_targets may be null), ten tangents (K stacked blocks each), the plant's three
+        // arrays, three tangents and the disturbance's tangent; two outputs
+        constexpr int kIn = 29;
+        const void* src[kIn] = {io->A, io->B, io->C, io->Q, io->R, io->lower, io->upper, io->x0, io->targets,
+                                new_last_targets, sequences, states,
+                                t->tA, t->tB, t->tC, t->tQ, t->tR, t->tlower, t->tupper, t->tx0, t->ttargets,
+                                t->tnew_last_targets,
+                                sep ? plant->A : nullptr, sep ? plant->B : nullptr, sep ? plant->C : nullptr,
+                                sep ? pt->tA : nullptr, sep ? pt->tB : nullptr, sep ? pt->tC : nullptr,
+                                use_plant ? pt->tdisturbance : nullptr};
+        int64_t src_ld[kIn] = {0};
+        src_ld[28] = ld_td;
         void* dst[2] = {tcontrols, tstates};
-        const int64_t rows[24] = {4, 2 * I, 2, 2, I, I, I, 2, 2 * H, 2 * S, S * H * I, 2 * S,
-                                  4 * K, 2 * I * K, 2 * K, 2 * K, I * K, I * K, I * K, 2 * K, 2 * H * K, 2 * S * K,
-                                  S * I * K, 2 * S * K};
-        return forward_run(h, io, mem, stream, flags_out, tangent_scratch_bytes(I, H, n, K, false), src, dst, rows, 22, 2,
+        const int64_t rows[kIn + 2] = {4, 2 * I, 2, 2, I, I, I, 2, 2 * H, 2 * S, S * H * I, 2 * S,
+                                       4 * K, 2 * I * K, 2 * K, 2 * K, I * K, I * K, I * K, 2 * K, 2 * H * K, 2 * S * K,
+                                       4, 2 * I, 2, 4 * K, 2 * I * K, 2 * K, 2 * S * K,
+                                       S * I * K, 2 * S * K};
+        return forward_run(h, io, mem, stream, flags_out, tangent_scratch_bytes(I, H, n, K, false), src, dst, rows, kIn, 2,
                            [&](int64_t ld, const void* const* in, void* const* out, hipStream_t s, uint32_t* hf) {
                                tangent::RollArgs a;
                                std::memset(&a, 0, sizeof(a));
@@ -2010,10 +2179,40 @@ int tpc_mpc_rollout_forward(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc
                                a.seq = (const double*)in[10]; a.states = (const double*)in[11];
                                a.t = bind_dirs(in + 12);
                                a.tu = (double*)out[0]; a.tx = (double*)out[1];
-                               if (hf) { *hf = rollout_tangent_host(I, H, a); return hipSuccess; }
-                               return rollout_tangent(I, H, a, h->grad_ws, h->ws_words + 1, s);
-                           });
+                               if (!use_plant) {
+                                   if (hf) { *hf = rollout_tangent_host(I, H, a); return hipSuccess; }
+                                   return rollout_tangent(I, H, a, h->grad_ws, h->ws_words + 1, s);
+                               }
+                               tangent::RollPlant pl;
+                               std::memset(&pl, 0, sizeof(pl));
+                               pl.A = sep ? (const double*)in[22] : a.A; pl.B = sep ? (const double*)in[23] : a.B;
+                               pl.C = sep ? (const double*)in[24] : a.C;
+                               pl.tA = sep ? (const double*)in[25] : a.t.tA; pl.tB = sep ? (const double*)in[26] : a.t.tB;
+                               pl.tC = sep ? (const double*)in[27] : a.t.tC;
+                               pl.td = (const double*)in[28];
+                               pl.ld_d = staged ? ld : ld_td;
+                               if (hf) { *hf = rollout_plant_tangent_host(I, H, a, pl); return hipSuccess; }
+                               return rollout_plant_tangent(I, H, a, pl, h->grad_ws, h->ws_words + 1, s);
+                           },
+                           src_ld);
     });
+}
+
+int tpc_mpc_rollout_forward(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io, int32_t steps,
+                            const void* new_last_targets, const void* sequences, const void* states,
+                            const tpc_mpc_tangents* t, void* tcontrols, void* tstates, uint32_t* flags_out, int mem,
+                            void* stream) {
+    return rollout_forward_impl(h, p, io, steps, new_last_targets, sequences, states, t, tcontrols, tstates, flags_out,
+                                mem, stream, "tpc_mpc_rollout_forward", false, nullptr, nullptr);
+}
+
+int tpc_mpc_rollout_plant_forward(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io,
+                                  const tpc_mpc_plant* plant, int32_t steps, const void* new_last_targets,
+                                  const void* sequences, const void* states, const tpc_mpc_tangents* t,
+                                  const tpc_mpc_plant_tangents* pt, void* tcontrols, void* tstates,
+                                  uint32_t* flags_out, int mem, void* stream) {
+    return rollout_forward_impl(h, p, io, steps, new_last_targets, sequences, states, t, tcontrols, tstates, flags_out,
+                                mem, stream, "tpc_mpc_rollout_plant_forward", true, plant, pt);
 }
 
 namespace {

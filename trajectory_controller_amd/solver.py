@@ -539,6 +539,15 @@ class MpcSolver:
             out["kkt_residual"] = out["kkt_residual"].reshape(n)
         return out
 
+    def _plant(self, plant, disturbance, ptr, I, steps):
+        """capi.Plant of plant=(Ap, Bp, Cp) | None and disturbance [steps*2, n] | None, through the call's ptr()."""
+        if plant is not None and len(plant) != 3:
+            raise ValueError("plant must be (Ap, Bp, Cp)")
+        Ap, Bp, Cp = plant if plant is not None else (None, None, None)
+        d = ptr(disturbance, 2 * steps)
+        ld_d = 0 if disturbance is None else int(disturbance.shape[-1])
+        return capi.Plant(A=ptr(Ap, 4), B=ptr(Bp, 2 * I), C=ptr(Cp, 2), disturbance=d, ld_d=ld_d)
+
     def rollout(self, steps: int, A, B, Cc, Q, R, lower, upper, x0, targets, new_last_targets=None,
                 controls=None, v_state=None, inputs: Optional[int] = None, want_states: bool = True,
                 want_iters: bool = False, **over):
@@ -552,17 +561,19 @@ class MpcSolver:
         return c_out, s_out, i_out
 
     def rollout_record(self, steps: int, A, B, Cc, Q, R, lower, upper, x0, targets, new_last_targets=None,
-                       controls=None, v_state=None, inputs: Optional[int] = None, want_iters: bool = False, **over):
+                       controls=None, v_state=None, inputs: Optional[int] = None, want_iters: bool = False,
+                       plant=None, disturbance=None, **over):
         """rollout that also records every step's solved sequence (tpc_mpc_rollout_record), what rollout_backward
         differentiates at.  Returns (controls[steps*I, n], states[steps*2, n], sequences[steps*H*I, n],
-        iters[steps, n] | None); the first two and iters are rollout's, bit for bit."""
+        iters[steps, n] | None); the first two and iters are rollout's, bit for bit.  plant=(Ap, Bp, Cp) and / or
+        disturbance [steps*2, n] move the state instead of the controller's model (tpc_mpc_rollout_plant, fp64)."""
         c_out, s_out, i_out, q_out = self._rollout(True, steps, A, B, Cc, Q, R, lower, upper, x0, targets,
                                                    new_last_targets, controls, v_state, inputs, True, want_iters,
-                                                   **over)
+                                                   plant=plant, disturbance=disturbance, **over)
         return c_out, s_out, q_out, i_out
 
     def _rollout(self, record, steps, A, B, Cc, Q, R, lower, upper, x0, targets, new_last_targets, controls, v_state,
-                 inputs, want_states, want_iters, **over):
+                 inputs, want_states, want_iters, plant=None, disturbance=None, **over):
         p = self._params(**over)
         H = p.horizon
         if _is_torch(A):
@@ -614,7 +625,13 @@ class MpcSolver:
                             targets=ptr(targets, 2 * H), controls_inout=ptr(controls, H * I),
                             v_inout=ptr(v_state, H * I), u0=None, iters=None)
         flags = C.c_uint32(0)
-        if record:
+        if plant is not None or disturbance is not None:
+            pl = self._plant(plant, disturbance, ptr, I, steps)
+            self._check(self._lib.tpc_mpc_rollout_plant(self._h, C.byref(p), C.byref(io), C.byref(pl), capi.LOOP_RECORD,
+                                                        int(steps), ptr(new_last_targets, 2 * steps), None, 0,
+                                                        optr(c_out), optr(s_out), optr(i_out), optr(q_out), None,
+                                                        C.byref(flags), mem, stream))
+        elif record:
             self._check(self._lib.tpc_mpc_rollout_record(self._h, C.byref(p), C.byref(io), int(steps),
                                                          ptr(new_last_targets, 2 * steps), optr(c_out), optr(s_out),
                                                          optr(i_out), optr(q_out), C.byref(flags), mem, stream))
@@ -628,7 +645,7 @@ class MpcSolver:
     def rollout_polished(self, steps: int, A, B, Cc, Q, R, lower, upper, x0, targets, new_last_targets=None,
                          controls=None, v_state=None, inputs: Optional[int] = None, tol: float = 1e-9,
                          max_rounds: int = 8, want_status: bool = True, want_iters: bool = False, residuals=None,
-                         **over):
+                         plant=None, disturbance=None, **over):
         """rollout with every step's solved sequence polished onto the verified optimum before the plant moves
         (tpc_mpc_rollout_polished: the solve of rollout's step, then polish_batch_general's rule and the step in one
         kernel), fp64 only.  Arrays as in rollout (numpy: HOST memory, CUDA torch tensors: DEVICE memory on the
@@ -637,7 +654,9 @@ class MpcSolver:
         takes -- and status holds the polish rounds of each (step, instance), or -1 where the step kept the solver's
         sequence (last_flags then carries FLAG_NOT_POLISHED).  want_status=False returns None for status, leaves
         last_flags at 0 and keeps a DEVICE call asynchronous.  residuals: optionally a pair of fp64 arrays [steps, n]
-        of the inputs' kind that receive the polish's residual_in and residual_out of every (step, instance)."""
+        of the inputs' kind that receive the polish's residual_in and residual_out of every (step, instance).
+        plant=(Ap, Bp, Cp) and / or disturbance [steps*2, n]: the state moves with x <- Ap x + Bp u0 + Cp + d_k
+        instead of the controller's model (tpc_mpc_rollout_plant); both None is the existing entry."""
         p = self._params(**over)
         H = p.horizon
         if _is_torch(A):
@@ -693,6 +712,15 @@ class MpcSolver:
         q = capi.Polish(tol=float(tol), max_rounds=int(max_rounds), reserved=0, status=optr(status),
                         residual_in=ptr(rin, steps), residual_out=ptr(rout, steps))
         flags = C.c_uint32(0)
+        if plant is not None or disturbance is not None:   # the same loop against a separate plant
+            pl = self._plant(plant, disturbance, ptr, I, steps)
+            self._check(self._lib.tpc_mpc_rollout_plant(self._h, C.byref(p), C.byref(io), C.byref(pl),
+                                                        capi.LOOP_POLISHED, int(steps),
+                                                        ptr(new_last_targets, 2 * steps), C.byref(q), 0, optr(c_out),
+                                                        optr(s_out), optr(i_out), optr(q_out), None,
+                                                        C.byref(flags) if want_status else None, mem, stream))
+            self.last_flags = flags.value
+            return c_out, s_out, q_out, status, i_out
         self._check(self._lib.tpc_mpc_rollout_polished(self._h, C.byref(p), C.byref(io), int(steps),
                                                        ptr(new_last_targets, 2 * steps), C.byref(q), optr(c_out),
                                                        optr(s_out), optr(i_out), optr(q_out),
@@ -703,7 +731,7 @@ class MpcSolver:
     def rollout_newton(self, steps: int, A, B, Cc, Q, R, lower, upper, x0, targets, new_last_targets=None,
                        controls=None, v_state=None, inputs: Optional[int] = None, tol: float = 1e-9,
                        max_rounds: int = 8, fallback: str = "solve", want_status: bool = True,
-                       want_iters: bool = False, residuals=None, **over):
+                       want_iters: bool = False, residuals=None, plant=None, disturbance=None, **over):
         """The polished closed loop with the Newton rounds first (tpc_mpc_rollout_newton), fp64 only: every step is
         polished from the shifted warm start without a first-order solve, all steps in one launch; an instance is
         carried as long as the polish verifies.  fallback="solve": the instances that stopped are run from step 0
@@ -712,7 +740,8 @@ class MpcSolver:
         Arguments and arrays as rollout_polished.  Returns rollout_polished's tuple plus first_unverified:
         (controls[steps*I, n], states[steps*2, n], sequences[steps*H*I, n], status[steps, n] | None,
         iters[steps, n] | None, first_unverified[n]) -- int32, the step phase 1 stopped at, `steps` for an instance
-        it carried to the end.  iters is 0 for the steps of such an instance."""
+        it carried to the end.  iters is 0 for the steps of such an instance.  plant, disturbance: as
+        rollout_polished."""
         p = self._params(**over)
         H = p.horizon
         if _is_torch(A):
@@ -769,6 +798,15 @@ class MpcSolver:
         q = capi.Polish(tol=float(tol), max_rounds=int(max_rounds), reserved=0, status=optr(status),
                         residual_in=ptr(rin, steps), residual_out=ptr(rout, steps))
         flags = C.c_uint32(0)
+        if plant is not None or disturbance is not None:   # the same loop against a separate plant
+            pl = self._plant(plant, disturbance, ptr, I, steps)
+            self._check(self._lib.tpc_mpc_rollout_plant(self._h, C.byref(p), C.byref(io), C.byref(pl), capi.LOOP_NEWTON,
+                                                        int(steps), ptr(new_last_targets, 2 * steps), C.byref(q),
+                                                        capi.NEWTON_FALLBACKS[fallback], optr(c_out), optr(s_out),
+                                                        optr(i_out), optr(q_out), optr(first),
+                                                        C.byref(flags) if want_status else None, mem, stream))
+            self.last_flags = flags.value
+            return c_out, s_out, q_out, status, i_out, first[0]
         self._check(self._lib.tpc_mpc_rollout_newton(self._h, C.byref(p), C.byref(io), int(steps),
                                                      ptr(new_last_targets, 2 * steps), C.byref(q),
                                                      capi.NEWTON_FALLBACKS[fallback], optr(c_out), optr(s_out),
@@ -778,10 +816,11 @@ class MpcSolver:
         return c_out, s_out, q_out, status, i_out, first[0]
 
     ROLLOUT_GRAD_NAMES = GRAD_NAMES[:-1] + ("new_last_targets", "kkt_residual")
+    PLANT_GRAD_NAMES = ("Ap", "Bp", "Cp", "disturbance")
 
     def rollout_backward(self, steps: int, A, B, Cc, Q, R, lower, upper, x0, targets, new_last_targets=None, *,
                          sequences, states, grad_controls=None, grad_states=None, inputs: Optional[int] = None,
-                         want=None, want_flags: bool = True, **over):
+                         want=None, want_flags: bool = True, plant=None, disturbance=None, **over):
         """Backward pass of rollout (tpc_mpc_rollout_backward), fp64 only: the gradient of a loss of the rollout's
         controls and states, taken at what rollout_record returned (`sequences` [steps*H*I, n], `states`
         [steps*2, n]).  grad_controls [steps*I, n] / grad_states [steps*2, n] are dL/d(controls) / dL/d(states)
@@ -789,12 +828,21 @@ class MpcSolver:
         stream).  Returns a dict keyed "A", "B", "C", "Q", "R", "lower", "upper", "x0", "targets",
         "new_last_targets" (only when new_last_targets is given) and "kkt_residual" [n] (max over the steps); `want`
         names the outputs to compute.  Flagged instances get zeros (last_flags; want_flags=False leaves it at 0 and
-        keeps a DEVICE call asynchronous)."""
+        keeps a DEVICE call asynchronous).  With plant=(Ap, Bp, Cp) (tpc_mpc_rollout_plant_backward) the keys "Ap",
+        "Bp", "Cp" hold the plant's gradients and "A", "B", "C" the controller's alone; "disturbance" [steps*2, n] is
+        the gradient of the disturbance's rows (at zero when disturbance is None) and has to be named in `want`
+        unless a plant or a disturbance is given."""
         p = self._params(**over)
         H = p.horizon
+        plant_call = plant is not None or disturbance is not None
         if want is None:
             want = tuple(k for k in self.ROLLOUT_GRAD_NAMES if k != "new_last_targets" or new_last_targets is not None)
-        unknown = set(want) - set(self.ROLLOUT_GRAD_NAMES)
+            if plant is not None:
+                want += ("Ap", "Bp", "Cp")
+            if plant_call:
+                want += ("disturbance",)
+        plant_call = plant_call or bool(set(want) & set(self.PLANT_GRAD_NAMES))
+        unknown = set(want) - set(self.ROLLOUT_GRAD_NAMES) - set(self.PLANT_GRAD_NAMES)
         if unknown:
             raise ValueError(f"unknown gradient names {sorted(unknown)}")
         if _is_torch(A):
@@ -833,7 +881,8 @@ class MpcSolver:
             stream = None
             mem = capi.HOST
         rows = {"A": 4, "B": 2 * I, "C": 2, "Q": 2, "R": I, "lower": I, "upper": I, "x0": 2, "targets": 2 * H,
-                "new_last_targets": 2 * steps, "kkt_residual": 1}
+                "new_last_targets": 2 * steps, "kkt_residual": 1, "Ap": 4, "Bp": 2 * I, "Cp": 2,
+                "disturbance": 2 * steps}
         out = {k: new(rows[k]) for k in want}
 
         def optr(k):
@@ -849,6 +898,17 @@ class MpcSolver:
                              dlower=optr("lower"), dupper=optr("upper"), dx0=optr("x0"), dtargets=optr("targets"),
                              dnew_last_targets=optr("new_last_targets"), kkt_residual=optr("kkt_residual"))
         flags = C.c_uint32(0)
+        if plant_call:
+            pl = self._plant(plant, None, ptr, I, steps)   # (the disturbance itself is not read: the states are recorded)
+            pg = capi.PlantGrad(dA=optr("Ap"), dB=optr("Bp"), dC=optr("Cp"), ddisturbance=optr("disturbance"))
+            self._check(self._lib.tpc_mpc_rollout_plant_backward(self._h, C.byref(p), C.byref(io), C.byref(pl),
+                                                                 int(steps), ptr(new_last_targets, 2 * steps),
+                                                                 C.byref(g), C.byref(pg),
+                                                                 C.byref(flags) if want_flags else None, mem, stream))
+            self.last_flags = flags.value
+            if "kkt_residual" in out:
+                out["kkt_residual"] = out["kkt_residual"].reshape(n)
+            return out
         self._check(self._lib.tpc_mpc_rollout_backward(self._h, C.byref(p), C.byref(io), int(steps),
                                                        ptr(new_last_targets, 2 * steps), C.byref(g),
                                                        C.byref(flags) if want_flags else None, mem, stream))
@@ -858,11 +918,13 @@ class MpcSolver:
         return out
 
     TANGENT_NAMES = ("A", "B", "C", "Q", "R", "lower", "upper", "x0", "targets", "new_last_targets")
+    PLANT_TANGENT_NAMES = ("Ap", "Bp", "Cp", "disturbance")
 
     def _forward_setup(self, A, R, inputs, tangents, rows):
         """What the two forward-mode calls share: (n, I, K, ptr, new, stream, mem, Tangents factory).  `tangents` maps
-        names of TANGENT_NAMES to arrays [K, c, n] (2-D [c, n]: K = 1); rows(I) gives c per name."""
-        unknown = set(tangents) - set(self.TANGENT_NAMES)
+        names of TANGENT_NAMES (and PLANT_TANGENT_NAMES -> the PlantTangents struct) to arrays [K, c, n] (2-D [c, n]: K = 1);
+        rows(I) gives c per name."""
+        unknown = set(tangents) - set(self.TANGENT_NAMES) - set(self.PLANT_TANGENT_NAMES)
         if unknown:
             raise ValueError(f"unknown tangent names {sorted(unknown)}")
         tangents = {k: v for k, v in tangents.items() if v is not None}
@@ -914,7 +976,10 @@ class MpcSolver:
         c = rows(I)
         fields = {("t" + name): ptr(tangents.get(name), K * c[name]) for name in self.TANGENT_NAMES}
         tan = capi.Tangents(directions=K, reserved=0, **fields)
-        return n, I, K, ptr, new, optr, stream, mem, tan
+        ptan = capi.PlantTangents(
+            tA=ptr(tangents.get("Ap"), K * 4), tB=ptr(tangents.get("Bp"), K * 2 * I), tC=ptr(tangents.get("Cp"), K * 2),
+            tdisturbance=ptr(tangents.get("disturbance"), K * c.get("disturbance", 0)))
+        return n, I, K, ptr, new, optr, stream, mem, tan, ptan
 
     def solve_batch_general_forward(self, A, B, Cc, Q, R, lower, upper, x0, targets, controls, tangents,
                                     inputs: Optional[int] = None, want_flags: bool = True, **over):
@@ -926,9 +991,9 @@ class MpcSolver:
         flagged (direction, instance) pair gets zeros (last_flags)."""
         p = self._params(**over)
         H = p.horizon
-        if "new_last_targets" in tangents:
-            raise ValueError("the single solve has no new_last_targets")
-        n, I, K, ptr, new, optr, stream, mem, tan = self._forward_setup(
+        if set(tangents) & ({"new_last_targets"} | set(self.PLANT_TANGENT_NAMES)):
+            raise ValueError("the single solve has no new_last_targets and no plant")
+        n, I, K, ptr, new, optr, stream, mem, tan, ptan = self._forward_setup(
             A, R, inputs, tangents, lambda I: {"A": 4, "B": 2 * I, "C": 2, "Q": 2, "R": I, "lower": I, "upper": I,
                                                "x0": 2, "targets": 2 * H, "new_last_targets": 0})
         io = capi.GeneralIO(inputs=I, n=n, ld=n, A=ptr(A, 4), B=ptr(B, 2 * I), C=ptr(Cc, 2), Q=ptr(Q, 2),
@@ -944,24 +1009,38 @@ class MpcSolver:
 
     def rollout_forward(self, steps: int, A, B, Cc, Q, R, lower, upper, x0, targets, new_last_targets=None, *,
                         sequences, states, tangents, inputs: Optional[int] = None, want_states: bool = True,
-                        want_flags: bool = True, **over):
+                        want_flags: bool = True, plant=None, disturbance=None, **over):
         """Forward mode of rollout (tpc_mpc_rollout_forward), fp64 only: the directional derivatives of the rollout's
         controls and states along K directions, taken at what rollout_record / rollout_polished / rollout_newton
         returned (`sequences` [steps*H*I, n], `states` [steps*2, n]); all K directions and all steps run in one
         launch.  `tangents`: as in solve_batch_general_forward, plus "new_last_targets" [K, steps*2, n] (only with
         new_last_targets).  Returns (tcontrols [K, steps*I, n], tstates [K, steps*2, n] | None); a flagged (direction,
-        instance) pair gets zeros (last_flags; want_flags=False keeps a DEVICE call asynchronous)."""
+        instance) pair gets zeros (last_flags; want_flags=False keeps a DEVICE call asynchronous).  With
+        plant=(Ap, Bp, Cp) (tpc_mpc_rollout_plant_forward) `tangents` may hold "Ap", "Bp", "Cp" and the tangents "A",
+        "B", "C" enter the steps' QPs only; "disturbance" [K, steps*2, n] is the tangent of the disturbance's rows."""
         p = self._params(**over)
         H = p.horizon
-        n, I, K, ptr, new, optr, stream, mem, tan = self._forward_setup(
+        plant_call = plant is not None or disturbance is not None or bool(set(tangents) & set(self.PLANT_TANGENT_NAMES))
+        n, I, K, ptr, new, optr, stream, mem, tan, ptan = self._forward_setup(
             A, R, inputs, tangents, lambda I: {"A": 4, "B": 2 * I, "C": 2, "Q": 2, "R": I, "lower": I, "upper": I,
-                                               "x0": 2, "targets": 2 * H, "new_last_targets": 2 * steps})
+                                               "x0": 2, "targets": 2 * H, "new_last_targets": 2 * steps,
+                                               "disturbance": 2 * steps})
         io = capi.GeneralIO(inputs=I, n=n, ld=n, A=ptr(A, 4), B=ptr(B, 2 * I), C=ptr(Cc, 2), Q=ptr(Q, 2),
                             R=ptr(R, I), lower=ptr(lower, I), upper=ptr(upper, I), x0=ptr(x0, 2),
                             targets=ptr(targets, 2 * H), controls_inout=None, v_inout=None, u0=None, iters=None)
         tu = new(K, steps * I)
         tx = new(K, steps * 2) if want_states else None
         flags = C.c_uint32(0)
+        if plant_call:
+            pl = self._plant(plant, None, ptr, I, steps)   # (the disturbance itself is not read: the states are recorded)
+            self._check(self._lib.tpc_mpc_rollout_plant_forward(self._h, C.byref(p), C.byref(io), C.byref(pl), int(steps),
+                                                                ptr(new_last_targets, 2 * steps),
+                                                                ptr(sequences, steps * H * I), ptr(states, 2 * steps),
+                                                                C.byref(tan), C.byref(ptan), optr(tu),
+                                                                optr(tx), C.byref(flags) if want_flags else None, mem,
+                                                                stream))
+            self.last_flags = flags.value
+            return tu, tx
         self._check(self._lib.tpc_mpc_rollout_forward(self._h, C.byref(p), C.byref(io), int(steps),
                                                       ptr(new_last_targets, 2 * steps),
                                                       ptr(sequences, steps * H * I), ptr(states, 2 * steps),
