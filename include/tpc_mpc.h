@@ -694,7 +694,9 @@ int tpc_mpc_follow_batch(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mp
  * (position.y, atan2(directory)) of the polyline point at arc length look_ahead + t * spacing, fed
  * through dlib::mpc::set_target(val, t) semantics (mpc.h:142-155) to the general-form solver; the
  * model, weights and bounds are the compact ones (p).  spacing = step_spacing[k] (float, optional) or,
- * when NULL, |v| * step_size -- the distance driven per step.  Step 0 is tpc_mpc_follow_batch's point,
+ * when NULL, |v| * step_size -- the distance driven per step; a negative step_spacing[k] is taken as it is
+ * (the arc lengths shrink with t, each step's point is the one getTrajectoryPoint returns for its arc
+ * length; such an instance walks its polyline once per step).  Step 0 is tpc_mpc_follow_batch's point,
  * so target_speed / target_distance and the crossing rule are the same; with spacing 0 the whole
  * call equals tpc_mpc_follow_batch.  targets_out (optional, double, SoA [2N][n]) receives the targets
  * used.  The reference module itself sets one target for all steps (src/...follower.cpp:368-371):

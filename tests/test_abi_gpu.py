@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from conftest import bits_equal, load_golden
+from tests.model.follow_ref import random_trajectories as _random_trajectories, walk_single_pass as _walk_np
 
 pytestmark = pytest.mark.gpu
 
@@ -449,52 +450,6 @@ def test_product_solver_under_two_rank_sharding(torch_cuda, tmp_path):
 
 # ---------------------------------------------------------------------------------------------
 # one trajectory point per horizon step
-
-def _random_trajectories(n, P, seed):
-    rng = np.random.default_rng(seed)
-    seg = rng.uniform(0.02, 0.25, size=(P, n)).astype(np.float32)
-    ang = np.cumsum(rng.uniform(-0.15, 0.15, size=(P, n)), axis=0).astype(np.float32)
-    px = np.cumsum(seg * np.cos(ang), axis=0, dtype=np.float32)
-    py = (np.cumsum(seg * np.sin(ang), axis=0, dtype=np.float32) + rng.uniform(-0.2, 0.2, size=n).astype(np.float32))
-    dx, dy = np.cos(ang).astype(np.float32), np.sin(ang).astype(np.float32)
-    vel = rng.uniform(0.0, 2.0, size=(P, n)).astype(np.float32)
-    count = rng.integers(0, P + 1, size=n).astype(np.int32)
-    count[:3] = (0, 1, 2)
-    carv = rng.uniform(-0.2, 4.0, size=n).astype(np.float32)
-    look = rng.uniform(0.2, 1.5, size=n).astype(np.float32)
-    return px, py, dx, dy, vel, count, carv, look
-
-
-def _walk_np(px, py, dx, dy, vel, count, first, spacing, H):
-    """float32 restatement of traj_horizon_kernel's walk for one polyline -- test infrastructure.
-    Returns per step (ox, oy, odx, ody, ovel)."""
-    f = np.float32
-    out = []
-    t = 0
-    want = lambda t: f(first) if t == 0 else f(f(first) + f(f(t) * f(spacing)))
-    if count > 0:
-        walked = f(0)
-        for i in range(1, count):
-            if t >= H:
-                break
-            ex, ey = f(px[i - 1] - px[i]), f(py[i - 1] - py[i])
-            ln = f(np.sqrt(f(f(ex * ex) + f(ey * ey))))
-            walked = f(walked + ln)
-            while t < H and walked > want(t):
-                back = f(walked - want(t))
-                nx, ny = (f(ex / ln), f(ey / ln)) if ln > 0 else (f(0), f(0))
-                out.append((f(px[i] + f(nx * back)), f(py[i] + f(ny * back)), dx[i], dy[i], vel[i]))
-                t += 1
-        j = count - 1
-        while t < H:
-            out.append((px[j], py[j], dx[j], dy[j], vel[j]))
-            t += 1
-    else:
-        while t < H:
-            out.append((want(t), f(0), f(1), f(0), f(0)))
-            t += 1
-    return out
-
 
 def test_follow_batch_horizon(torch_cuda, oracle):
     """(1) spacing 0 puts every horizon step on tpc_mpc_follow_batch's single point: the general-form

@@ -8,6 +8,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests.model.follow_ref import traj_point as _traj_point_np   # float32 restatement of the shim's getTrajectoryPoint
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "trajectory_controller_amd", "host")
 LIB = os.path.join(ROOT, "trajectory_controller_amd", "lib")
@@ -56,29 +58,6 @@ def test_cycle_matches_reference_solver(tmp_path, oracle, H):
     assert lines[-3] == {"indicator_left": True, "indicator_right": False, "reset_left": False, "reset_right": False}
     assert lines[-2] == {"idle_state": True, "priority": 100, "idle_speed": 0, "removed_after": True}
     assert lines[-1] == {"other_backend_refused": True}
-
-
-def _traj_point_np(px, py, dx, dy, vel, count, want):
-    """float32 restatement of the module shim's getTrajectoryPoint (host/trajectory_point_controller.cpp,
-    reference src/trajectory_point_follower.cpp:392-443) for one polyline -- test infrastructure."""
-    f = np.float32
-    ox, oy, odx, ody, ovel = f(want), f(0), f(1), f(0), f(0)
-    if count > 0:
-        walked, found = f(0), False
-        for i in range(1, count):
-            ex, ey = f(px[i - 1] - px[i]), f(py[i - 1] - py[i])
-            ln = f(np.sqrt(f(f(ex * ex) + f(ey * ey))))
-            walked = f(walked + ln)
-            if walked > want:
-                back = f(walked - want)
-                nx, ny = (f(ex / ln), f(ey / ln)) if ln > 0 else (f(0), f(0))
-                ox, oy = f(px[i] + f(nx * back)), f(py[i] + f(ny * back))
-                odx, ody, ovel, found = dx[i], dy[i], vel[i], True
-                break
-        if not found:
-            j = count - 1
-            ox, oy, odx, ody, ovel = px[j], py[j], dx[j], dy[j], vel[j]
-    return ox, oy, odx, ody, ovel, f(np.sqrt(f(f(ox * ox) + f(oy * oy))))
 
 
 @pytest.mark.gpu

@@ -30,6 +30,29 @@ __device__ __forceinline__ float lut_search(const float* vx, const float* vy, in
     return vy[n - 1];
 }
 
+// getTrajectoryPoint(want) on the cnt > 0 points of instance k (:408-443): walk the polyline until the accumulated
+// length passes `want`, step back along that segment; never passed: the last point (:439-442).
+struct TrajPoint { float x, y, dx, dy, vel; };
+__device__ __forceinline__ TrajPoint walk_to(const FollowArgs& a, int64_t k, int cnt, float want) {
+    float walked = 0.0f;
+    float bx = a.px[k], by = a.py[k];
+    for (int i = 1; i < cnt; ++i) {
+        const int64_t o = (int64_t)i * a.ld + k;
+        const float tx = a.px[o], ty = a.py[o];
+        const float ex = bx - tx, ey = by - ty;                 // bot - top
+        const float len = sqrtf(ex * ex + ey * ey);             // bot.distance(top)
+        walked += len;
+        if (walked > want) {
+            const float back = walked - want;
+            const float nx = len > 0.0f ? ex / len : 0.0f, ny = len > 0.0f ? ey / len : 0.0f;
+            return {tx + nx * back, ty + ny * back, a.dx[o], a.dy[o], a.vel[o]};   // top + normalize(bot-top)*back
+        }
+        bx = tx; by = ty;
+    }
+    const int64_t o = (int64_t)(cnt - 1) * a.ld + k;
+    return {a.px[o], a.py[o], a.dx[o], a.dy[o], a.vel[o]};
+}
+
 __global__ void traj_point_kernel(FollowArgs a) {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= a.n) return;
@@ -38,29 +61,8 @@ __global__ void traj_point_kernel(FollowArgs a) {
     // default when there is nothing to follow: idle straight ahead (:394-407)
     float ox = want, oy = 0.0f, odx = 1.0f, ody = 0.0f, ovel = 0.0f;
     if (cnt > 0) {
-        float walked = 0.0f;
-        bool found = false;
-        float bx = a.px[k], by = a.py[k];
-        for (int i = 1; i < cnt; ++i) {
-            const int64_t o = (int64_t)i * a.ld + k;
-            const float tx = a.px[o], ty = a.py[o];
-            const float ex = bx - tx, ey = by - ty;                 // bot - top
-            const float len = sqrtf(ex * ex + ey * ey);             // bot.distance(top)
-            walked += len;
-            if (walked > want) {
-                const float back = walked - want;
-                const float nx = len > 0.0f ? ex / len : 0.0f, ny = len > 0.0f ? ey / len : 0.0f;
-                ox = tx + nx * back; oy = ty + ny * back;           // top + normalize(bot-top)*back
-                odx = a.dx[o]; ody = a.dy[o]; ovel = a.vel[o];
-                found = true;
-                break;
-            }
-            bx = tx; by = ty;
-        }
-        if (!found) {                                               // :439-442 last point
-            const int64_t o = (int64_t)(cnt - 1) * a.ld + k;
-            ox = a.px[o]; oy = a.py[o]; odx = a.dx[o]; ody = a.dy[o]; ovel = a.vel[o];
-        }
+        const TrajPoint p = walk_to(a, k, cnt, want);
+        ox = p.x; oy = p.y; odx = p.dx; ody = p.dy; ovel = p.vel;
     }
     double v = (double)a.car_velocity[k];
     if (fabs(v) < 0.1) v = 0.1;                                     // :78-82
@@ -79,6 +81,9 @@ __global__ void traj_point_kernel(FollowArgs a) {
 // feeds dlib::mpc::set_target(val, t) (mpc.h:142-155) as (y_soll, phi_soll) = (position.y,
 // atan2(directory)).  Step 0 is exactly traj_point_kernel's point, so target_speed / target_distance
 // and the crossing rule do not change.  The model is the compact one written out in general form.
+// A lane whose spacing is not >= 0 (negative: the distances shrink with t; NaN) cannot be served by one
+// pass: it walks the polyline from its first point once per step, which is what the header's definition
+// says (H getTrajectoryPoint calls) and costs only that lane's wavefront.
 __global__ void traj_horizon_kernel(FollowArgs a, FollowHorizonArgs f) {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= a.n) return;
@@ -102,8 +107,15 @@ __global__ void traj_horizon_kernel(FollowArgs a, FollowHorizonArgs f) {
             a.target_distance[k] = sqrtf(ox * ox + oy * oy);         // :117
         }
     };
+    // arc length of step t; step 0 is the look-ahead itself, whatever the spacing (0 * Inf is NaN)
+    auto want_of = [&](int t) { return t == 0 ? first : first + (float)t * spacing; };
     int t = 0;
-    if (cnt > 0) {
+    if (cnt > 0 && !(spacing >= 0.0f)) {
+        for (; t < f.H; ++t) {
+            const TrajPoint p = walk_to(a, k, cnt, want_of(t));
+            emit(t, p.x, p.y, p.dx, p.dy, p.vel);
+        }
+    } else if (cnt > 0) {
         float walked = 0.0f;
         float bx = a.px[k], by = a.py[k];
         for (int i = 1; i < cnt && t < f.H; ++i) {
@@ -112,13 +124,13 @@ __global__ void traj_horizon_kernel(FollowArgs a, FollowHorizonArgs f) {
             const float ex = bx - tx, ey = by - ty;
             const float len = sqrtf(ex * ex + ey * ey);
             walked += len;
-            float want = t == 0 ? first : first + (float)t * spacing;
+            float want = want_of(t);
             while (t < f.H && walked > want) {
                 const float back = walked - want;
                 const float nx = len > 0.0f ? ex / len : 0.0f, ny = len > 0.0f ? ey / len : 0.0f;
                 emit(t, tx + nx * back, ty + ny * back, a.dx[o], a.dy[o], a.vel[o]);
                 ++t;
-                want = first + (float)t * spacing;
+                want = want_of(t);
             }
             bx = tx; by = ty;
         }
@@ -126,7 +138,7 @@ __global__ void traj_horizon_kernel(FollowArgs a, FollowHorizonArgs f) {
         for (; t < f.H; ++t) emit(t, a.px[o], a.py[o], a.dx[o], a.dy[o], a.vel[o]);
     } else {
         // nothing to follow: idle straight ahead (:394-407)
-        for (; t < f.H; ++t) emit(t, first + (float)t * spacing, 0.0f, 1.0f, 0.0f, 0.0f);
+        for (; t < f.H; ++t) emit(t, want_of(t), 0.0f, 1.0f, 0.0f, 0.0f);
     }
     // A=[1,Tv;0,1]  B=[0,Tv;Tv/l,-Tv/l]  C=0  (:326-333), Q, R (:359-363), bounds (:16-18), x0 = 0 (:377-378)
     const double av = f.step * v, cv = f.step * v / f.wheelbase;
