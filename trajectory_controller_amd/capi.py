@@ -205,6 +205,9 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.tpc_mpc_set_option.argtypes = [vp, C.c_int, C.c_int64]
     lib.tpc_mpc_x_set_group_share.argtypes = [vp, C.c_int, C.c_int]       # experimental
     lib.tpc_mpc_x_set_lanex_below.argtypes = [vp, C.c_int64]               # experimental
+    lib.tpc_mpc_x_set_queue_key.argtypes = [vp, C.c_int]                   # experimental
+    lib.tpc_mpc_x_last_queue_key.argtypes = [vp, C.POINTER(C.c_int)]       # experimental
+    lib.tpc_mpc_x_queue_key_predict.argtypes = [vp, vp, vp, C.c_int64, vp]   # experimental
     lib.tpc_mpc_gather_shards.argtypes = [vp, C.c_int64, C.POINTER(C.c_void_p), C.c_int, C.c_int, vp]
     lib.tpc_mpc_reserve.argtypes = [vp, C.POINTER(Params), C.c_int64, C.c_int]
     lib.tpc_mpc_build_info.restype = C.c_char_p

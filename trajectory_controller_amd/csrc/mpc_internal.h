@@ -26,7 +26,11 @@ struct CompactArgs {
     const int32_t* work_hint;      // [n] or null: caller's iteration-count estimate (LANE queue order only)
     double step, wheelbase;        // T, l
     double q[2], r[2], lo[2], hi[2];
+    int table_key;                 // 1: these ARE the parameters of mpc_queue_key_table.h (the host compared): LANE_FMA fp64 N = 20 keys its queue by the table
 };
+
+// which estimate ordered the work queue of a handle's last compact solve (tpc_mpc_x_last_queue_key)
+constexpr int kQueueKeyLambda = 0, kQueueKeyTableUsed = 1, kQueueKeyHint = 2;
 
 // One compact instance whose inputs are already in registers (the resident solve_one wavefront,
 // tpc_mpc_one.hip): no input arrays; the two outputs are stored system-wide into out[0], out[1].

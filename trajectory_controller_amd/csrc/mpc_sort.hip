@@ -1,11 +1,15 @@
 // Longest-first ordering of the projected-gradient work queue.
 //
-// Iteration counts differ ~30x between instances and are predicted almost perfectly by lambda, the
-// Hessian trace bound dlib already computes (Spearman 0.97 with the iteration count on the
+// Iteration counts differ ~30x between instances.  lambda, the Hessian trace bound dlib already
+// computes, predicts them well but not perfectly (Spearman 0.97 with the iteration count on the
 // reference's input distribution): the step is 1/lambda, so a large lambda
-// means many small steps.  The CD kernel emits a 32-bit key per instance (the bits of
-// float(lambda), 0 for instances that already stopped); the PG kernel pulls instances in
-// descending key order, which is the LPT rule for the makespan of its persistent lanes.
+// means many small steps -- but lambda is a function of the speed alone, and at a given speed the
+// count still varies +-15 % with the target.  The CD kernel emits a 32-bit key per instance (the
+// bits of float(lambda); LANE_FMA at fp64, N = 20 with the reference controller's parameters: of
+// the count a table predicts from (v, dy, dphi), Spearman 0.99, to the fourth power -- mpc_queue_key.h, mpc_ub.h; small values
+// for instances that already stopped); the PG kernel pulls instances in descending key order,
+// which is the LPT rule for the makespan of its persistent lanes and puts instances of similar
+// length side by side in a wavefront.
 //
 // A counting sort on the top 16 key bits (sign, exponent, 7 mantissa bits: 0.8 % resolution):
 // histogram (by the key producer) -> exclusive scan from the largest bin down -> scatter.  Positions inside a bin come

@@ -17,6 +17,7 @@
 #include "mpc_lane.h"
 #include "mpc_ub_model.h"
 #include "mpc_ub_cd_asm.h"
+#include "mpc_queue_key.h"
 
 namespace tpc {
 
@@ -88,8 +89,22 @@ __global__ __launch_bounds__(64, (CdOcc<T, H>::value)) void ub_cd_kernel(Compact
     ub::Unit<T, EQB> m;
     ub_set_uniform(m, (T)1, g);
     const T ty = ((const T*)g.dy)[k], tphi = ((const T*)g.dphi)[k];
-    m.set_instance((T)g.step, (T)g.wheelbase, ((const T*)g.v)[k], ty, tphi);
+    const T tv = ((const T*)g.v)[k];
+    m.set_instance((T)g.step, (T)g.wheelbase, tv, ty, tphi);
     const bool nonfinite = m.nonfinite_inputs(ty, tphi);
+    // the table's queue key (mpc_queue_key.h; used at the end, where g.table_key says so): looked up HERE, unconditionally and
+    // in the set-up's own basic block, so that its eight dependent table loads are in flight under the set-up's divisions.
+    // Behind a branch at the end of the kernel every wavefront waited for them with nothing else to do: +0.014 ms of
+    // kernel time per 262 144 instances.  (Any input reads inside the table, so a call that keeps lambda loses nothing but the loads.)
+    // The key is the prediction's FOURTH POWER: the same order, spread over four times as many of the sort's bins (128 per
+    // octave, mpc_sort.hip).  Counts span 4.4 octaves where lambda spans 10.5, and every instance ends this kernel with a
+    // returning atomic on its bin: on ~560 bins instead of ~1 700 those cost the kernel +0.011 ms, on a handful of bins
+    // (a diagnostic build with a flat table) +0.035 ms, on ONE bin 2.5 ms (NOTEBOOK round 7).
+    float table_lf = 0.0f;
+    if constexpr (sizeof(T) == 8 && H == kQueueKeyH) {
+        const float c = queue_key_predict((double)tv, (double)ty, (double)tphi);
+        table_lf = (c * c) * (c * c);
+    }
     const T q0 = (T)g.q[0], q1 = (T)g.q[1], r0 = (T)g.r[0], r1 = (T)g.r[1];
 
     T x[XL ? 1 : 2 * H], w[ub::Reverse<T, H>::value ? 1 : 2 * H];
@@ -226,11 +241,17 @@ __global__ __launch_bounds__(64, (CdOcc<T, H>::value)) void ub_cd_kernel(Compact
         T* ex = rec + LaneRec<T, H>::kExtra;
         ex[0] = il0; ex[1] = il1; ex[2] = beta; ex[3] = m.a; ex[4] = m.c; ex[5] = ty; ex[6] = tphi;
     }
-    // queue key: as lane_cd_kernel (longest first by lambda, the floor rule, finished instances last)
+    // queue key: as lane_cd_kernel (longest first by lambda, the floor rule, finished instances last) -- except that fp64
+    // N = 20 with the parameters its table was made for (g.table_key: the host compared them) takes the iteration count
+    // predicted from (v, dy, dphi) where the others take lambda (mpc_queue_key.h); a caller's hint still wins
     const bool finished = stopped || iter >= kn.max_iter;
     const T lambda_floor = (r0 + r1) * (T)H;
     const bool uninformative = lambda < (T)1.5 * lambda_floor;
-    const float lf = g.work_hint ? (float)(g.work_hint[k] > 0 ? g.work_hint[k] : 1) : (float)lambda;
+    float lf = (float)lambda;
+    if constexpr (sizeof(T) == 8 && H == kQueueKeyH) {
+        if (g.table_key) lf = table_lf;
+    }
+    if (g.work_hint) lf = (float)(g.work_hint[k] > 0 ? g.work_hint[k] : 1);
     const uint32_t spread = (uint32_t)k & 127u;
     uint32_t key = __float_as_uint(lf);
     if (finished) key = spread << 16;

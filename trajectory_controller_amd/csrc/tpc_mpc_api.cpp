@@ -6,6 +6,7 @@
 #include "tpc_mpc_context.h"
 #include "tpc_mpc_experimental.h"
 #include "auto_table.h"
+#include "mpc_queue_key_table.h"
 #include "mpc_grad_model.h"
 #include "mpc_polish_model.h"
 #include "mpc_rollout_newton.h"
@@ -770,6 +771,20 @@ int presolve_finish(tpc_mpc_context* h, const tpc_mpc_params* p, int64_t n, cons
     return TPC_MPC_OK;
 }
 
+// Does mpc_queue_key_table.h speak about this solve?  Its counts were made with ONE parameter set, and an iteration count
+// depends on every one of them: exact comparison against the header's constants, once per call; the kernel gets a flag.
+// LANE_FMA only: GROUP at N = 20 runs the same coordinate-descent kernel, but is AUTO's choice for the small batches,
+// which its persistent grid does not fill -- nothing measured says the order matters there, so it keeps lambda.
+static bool queue_key_table_applies(const tpc_mpc_params* p, int algo) {
+    return algo == TPC_MPC_ALGO_LANE_FMA && p->dtype == TPC_MPC_F64 && p->horizon == kQueueKeyH &&
+           p->weight_y == kQueueKeyWeights[0] && p->weight_phi == kQueueKeyWeights[1] &&
+           p->weight_steering_front == kQueueKeyWeights[2] && p->weight_steering_rear == kQueueKeyWeights[3] &&
+           p->step_size == kQueueKeyStep && p->wheelbase == kQueueKeyWheelbase &&
+           p->lower[0] == kQueueKeyLower && p->lower[1] == kQueueKeyLower &&
+           p->upper[0] == kQueueKeyUpper && p->upper[1] == kQueueKeyUpper && p->eps == kQueueKeyEps &&
+           p->max_iter == kQueueKeyMaxIter && p->smo_iters == kQueueKeySmoIters;
+}
+
 // the tolerance (or whatever pick_algo says) pass; with `ps`: AUTO's guarantee is the caller's business (presolve_finish),
 // immediately unless ps->deferred
 int compact_launch_ps(tpc_mpc_context* h, const tpc_mpc_params* p, int64_t n, const void* v, const void* dy,
@@ -779,6 +794,8 @@ int compact_launch_ps(tpc_mpc_context* h, const tpc_mpc_params* p, int64_t n, co
     CompactArgs a;
     compact_args(h, p, n, v, dy, dphi, front, rear, iters, &a);
     a.work_hint = take_hint(h, n);
+    a.table_key = h->opt_queue_key && queue_key_table_applies(p, algo) ? 1 : 0;
+    h->last_queue_key = a.work_hint ? kQueueKeyHint : (a.table_key ? kQueueKeyTableUsed : kQueueKeyLambda);
     const bool fix = wants_cap_resolve(p, algo) && a.flags;
     int rc = TPC_MPC_OK;
     if (fix && !a.iters) rc = cap_iters_buffer(h, n, &a.iters);
@@ -2424,6 +2441,24 @@ int tpc_mpc_x_set_work_hint(tpc_mpc_handle h, const int32_t* hint, int64_t n, in
                              mem == TPC_MPC_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice));
         h->hint = (const int32_t*)h->hint_own;
         h->hint_n = n;
+        return TPC_MPC_OK;
+    });
+}
+
+int tpc_mpc_x_set_queue_key(tpc_mpc_handle h, int on) {
+    return guarded(h, [&]() -> int {
+        if (!h) return fail(nullptr, TPC_MPC_ERR_BAD_ARG, "null handle");
+        if (on != 0 && on != 1) return fail(h, TPC_MPC_ERR_BAD_ARG, "tpc_mpc_x_set_queue_key takes 0 or 1");
+        h->opt_queue_key = on != 0;
+        return TPC_MPC_OK;
+    });
+}
+
+int tpc_mpc_x_last_queue_key(tpc_mpc_handle h, int* key) {
+    return guarded(h, [&]() -> int {
+        if (!h) return fail(nullptr, TPC_MPC_ERR_BAD_ARG, "null handle");
+        if (!key) return fail(h, TPC_MPC_ERR_BAD_ARG, "null key");
+        *key = h->last_queue_key;
         return TPC_MPC_OK;
     });
 }

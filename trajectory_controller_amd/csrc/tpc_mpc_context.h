@@ -73,6 +73,9 @@ struct tpc_mpc_context {
     int64_t hint_n = 0;
     void* hint_own = nullptr;
     int64_t hint_own_bytes = 0;
+    // the table-predicted queue key (mpc_queue_key.h; tpc_mpc_x_set_queue_key) and what ordered the last compact batch's queue
+    bool opt_queue_key = true;
+    int last_queue_key = 0;          // tpc::kQueueKeyLambda / kQueueKeyTableUsed / kQueueKeyHint
     // internal solves without a flags output skip the flag word's atomicOr
     bool collect_flags = true;
     // what the last tpc_mpc_solve_one reported (tpc_mpc_last_flags)

@@ -19,6 +19,17 @@ extern "C" {
  * cycle old, inputs moved by 0.5 % of their range, buy nothing -- which is why this is not in the public header. */
 int tpc_mpc_x_set_work_hint(tpc_mpc_handle h, const int32_t* hint, int64_t n, int mem);
 
+/* The queue key of LANE_FMA at fp64, N = 20.  Where a handle's parameters are exactly those csrc/mpc_queue_key_table.h was
+ * made for (the reference controller's: weights, T, l, bounds, eps, max_iter, smo_iters), the work queue of a compact batch
+ * is ordered by the iteration count that table predicts from (v, dy, dphi) instead of by lambda; any other parameter set,
+ * family, precision or horizon keeps lambda, and a work hint wins over both.  tpc_mpc_x_set_queue_key(h, 0) turns the table
+ * off for this handle (A/B runs, tests), 1 (the default) on.  tpc_mpc_x_last_queue_key: what ordered the queue of the
+ * handle's last compact batch: 0 lambda, 1 the table, 2 a work hint.  tpc_mpc_x_queue_key_predict: the table lookup
+ * itself on the host, predicted[k] = expected iteration count of (v[k], dy[k], dphi[k]); needs no handle. */
+int tpc_mpc_x_set_queue_key(tpc_mpc_handle h, int on);
+int tpc_mpc_x_last_queue_key(tpc_mpc_handle h, int* key);
+int tpc_mpc_x_queue_key_predict(const double* v, const double* dy, const double* dphi, int64_t n, float* predicted);
+
 /* The share of the chip a handle's GROUP solves take: `waves` persistent wavefronts (0 = one per SIMD, the default) and
  * the CU count AUTO's crossover table is scaled to (0 = back to the device's own).  What tpc_mpc_solve_batch_compact_mixed sets on
  * the child handles of its bins; exported to measure one bin on a share by itself (scripts/group_share.py). */

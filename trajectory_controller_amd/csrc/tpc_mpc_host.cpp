@@ -14,6 +14,8 @@
 // calls in here (tpc::host_path_usable).
 #include "../../include/tpc_mpc.h"
 #include "mpc_ub_host.h"
+#include "mpc_queue_key.h"
+#include "tpc_mpc_experimental.h"
 
 namespace tpc {
 
@@ -45,3 +47,11 @@ int host_solve_one(const tpc_mpc_params* p, double v, double dy, double dphi, do
 }
 
 }  // namespace tpc
+
+// The queue key's lookup on the host (mpc_queue_key.h: the function the fp64 N = 20 coordinate-descent kernel calls, compiled
+// for the CPU): what the tests hold to a numpy interpolation of the committed table.  No handle, no device.
+extern "C" int tpc_mpc_x_queue_key_predict(const double* v, const double* dy, const double* dphi, int64_t n, float* predicted) {
+    if (n < 0 || (n > 0 && (!v || !dy || !dphi || !predicted))) return TPC_MPC_ERR_BAD_ARG;
+    for (int64_t k = 0; k < n; ++k) predicted[k] = tpc::queue_key_predict(v[k], dy[k], dphi[k]);
+    return TPC_MPC_OK;
+}

@@ -154,6 +154,20 @@ class MpcSolver:
             h = np.ascontiguousarray(hint, dtype=np.int32)
             self._check(self._lib.tpc_mpc_x_set_work_hint(self._h, h.ctypes.data, h.shape[0], capi.HOST))
 
+    QUEUE_KEYS = ("lambda", "table", "hint")
+
+    def set_queue_key(self, table: bool = True):
+        """LANE_FMA, fp64, N = 20 with the reference controller's parameters: order the work queue by the iteration count
+        csrc/mpc_queue_key_table.h predicts (True, the default) or by lambda like everything else (False).  Experimental
+        (tpc_mpc_x_set_queue_key): for A/B runs and tests; never changes a result."""
+        self._check(self._lib.tpc_mpc_x_set_queue_key(self._h, int(bool(table))))
+
+    def last_queue_key(self) -> str:
+        """What ordered the work queue of the last compact batch: "lambda", "table" or "hint" (tpc_mpc_x_last_queue_key)."""
+        k = C.c_int()
+        self._check(self._lib.tpc_mpc_x_last_queue_key(self._h, C.byref(k)))
+        return self.QUEUE_KEYS[k.value]
+
     def solve_batch_compact(self, v, delta_y, delta_phi, want_iters: bool = False,
                             want_flags: bool = True, out=None, **over):
         """n independent mpcControllerTobi calls.  Returns (front, rear[, iters])."""
