@@ -1,6 +1,8 @@
 """`-m gpu` tests of the table-predicted queue key of LANE_FMA at fp64, N = 20 (csrc/mpc_queue_key.h, ub_cd_kernel in
 csrc/mpc_ub.h): the key decides which lane solves which instance when, and nothing else.  4 096 + 37 instances: a partial last
-wavefront, 65 wavefronts of the persistent grid with one instance per lane.
+wavefront, 65 wavefronts of the persistent grid with one instance per lane.  Where lanes see more than one instance -- the
+grid pinned to one wavefront, every lane refilled four or five times, the table's key, lambda's and hints in both orders
+against the CPU model -- is tests/test_refill_gpu.py (test_refill_lane_fma_queue_order_changes_nothing_n20).
 """
 import numpy as np
 import pytest

@@ -69,7 +69,12 @@ hipError_t pg_launch(const CompactArgs& a, const Knobs& k, const Workspace& ws, 
     }
 #endif
     int cap = ub_grid<TagPg<T, EQB, MODE>>(ub_pg_kernel<T, kH, EQB, MODE>, bt);
-    if (ws.max_waves > 0 && cap > ws.max_waves / UbPlan<T, kH>::occ) cap = ws.max_waves / UbPlan<T, kH>::occ;   // (a presolve holds the other SIMDs: tpc_mpc_api.cpp)
+    if (ws.max_waves > 0) {   // (a presolve holds the other SIMDs: tpc_mpc_api.cpp)
+        // whole workgroups, and never none: a share below one workgroup (fp32, N = 10 / 20: two wavefronts each) used to
+        // round down to a grid of zero, which the launch refuses (hipErrorInvalidConfiguration) -- no solve at all
+        const int lim = ws.max_waves / UbPlan<T, kH>::occ > 1 ? ws.max_waves / UbPlan<T, kH>::occ : 1;
+        if (cap > lim) cap = lim;
+    }
     hipLaunchKernelGGL((ub_pg_kernel<T, kH, EQB, MODE>), dim3((unsigned)(need < cap ? need : cap)), dim3(bt), 0, s, a, k,
                        (const T*)ws.state, (const uint32_t*)ws.order, ws.ticket, ws.stats, order_queue_len(ws.sort_temp));
     return hipGetLastError();
