@@ -479,6 +479,44 @@ int tpc_mpc_rollout_newton(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_
                            void* controls_out, void* states_out, int32_t* iters_out, void* sequences_out,
                            int32_t* first_unverified, uint32_t* flags_out, int mem, void* stream);
 
+/* No reference counterpart.  mpcControllerTobi for n instances with the VERIFIED OPTIMUM as the answer, not dlib's
+ * eps-0.01 point: the polish's Newton rounds from a cold start, the first-order solve only where they do not verify.
+ * Instance k has the general-form model the reference controller builds from (v, delta_y, delta_phi)
+ * (src/trajectory_point_follower.cpp:326-371), with T = p->step_size, l = p->wheelbase, Tv = T * v:
+ *     A = [1, Tv; 0, 1]   B = [0, Tv; Tv/l, -Tv/l] (Tv/l: one multiply, one divide)   C = 0   x0 = 0
+ *     Q = (weight_y, weight_phi)   R = (weight_steering_front, weight_steering_rear)   lower, upper from p
+ *     every one of the H targets (delta_y, delta_phi)
+ *   Phase 1, every instance.  U <- polish(U = 0) by the rule of tpc_mpc_polish_batch_general, unchanged, with q->tol and
+ *   q->max_rounds, in ONE launch that reads three doubles and writes two per instance (csrc/mpc_newton_compact.hip; at
+ *   horizons 4 and 5 the per-step values stay in registers and no workspace memory is touched).
+ *     verified: steering_front / steering_rear = row 0 of U, sequence_out = U, status = the rounds used, and the two
+ *            residuals.  All of them equal, bit for bit (signed zeros included), what tpc_mpc_polish_batch_general
+ *            returns for the expanded arrays with zero controls.
+ *   Phase 2, fallback TPC_MPC_NEWTON_FALLBACK_SOLVE.  The unverified instances are gathered and expanded to the general
+ *   form on the device (those instances only), solved cold with p's eps / max_iter / smo_iters / algo as
+ *   tpc_mpc_solve_batch_general does with zeroed controls_inout, polished with the same q and scattered back: their
+ *   outputs are exactly what those two entries return for the gathered batch.  status -1 and
+ *   TPC_MPC_FLAG_NOT_POLISHED are raised only where that polish also fails; the solver's u0 and sequence are then
+ *   returned.  fell_back[k] = 1 for them, 0 for everyone else.  The order of the instances inside the gathered batch is
+ *   not defined.  One 4-byte read-back (the number of such instances) sits between the phases.
+ *   Fallback TPC_MPC_NEWTON_FALLBACK_NONE.  Phase 1 only: an unverified instance returns (0, 0), a zero sequence,
+ *   status -1, residual_out 0 (residual_in: the residual at U = 0) and raises TPC_MPC_FLAG_NOT_POLISHED.  With
+ *   flags_out == NULL and DEVICE memory the call is asynchronous.
+ *   Invalid instances.  A non-finite v, delta_y or delta_phi (or a model value that stops being finite) raises
+ *   TPC_MPC_FLAG_NONFINITE; the instance returns (0, 0), a zero sequence, status -1 and zero residuals, is NOT sent to
+ *   the fallback and does not raise TPC_MPC_FLAG_NOT_POLISHED by itself.
+ * p is validated as tpc_mpc_solve_batch_compact validates it.  q->status (int32), q->residual_in, q->residual_out and
+ * fell_back (int32) are optional rows [n]; sequence_out is optional, SoA [H*2] with leading dimension n.  A null q,
+ * tol <= 0 (or NaN), max_rounds < 0, an unknown fallback or a dtype other than TPC_MPC_F64 return TPC_MPC_ERR_BAD_ARG.
+ * fp64 only, horizons 1..64.  n == 0 returns TPC_MPC_OK with flags 0.  HOST arrays are staged: three rows in, two
+ * (+ 2H and the optional rows) out.
+ * A host-only handle (TPC_MPC_DEVICE_NONE) runs FALLBACK_NONE on the calling thread with the kernel's bits (HOST memory
+ * only); with FALLBACK_SOLVE it returns TPC_MPC_ERR_NO_DEVICE, after the argument checks above. */
+int tpc_mpc_solve_batch_compact_exact(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t n, const void* v,
+                                      const void* delta_y, const void* delta_phi, const tpc_mpc_polish* q,
+                                      int32_t fallback, void* steering_front, void* steering_rear, void* sequence_out,
+                                      int32_t* fell_back, uint32_t* flags_out, int mem, void* stream);
+
 /* Inputs and outputs of tpc_mpc_rollout_backward, SoA with the io's leading dimension ld:
  *   sequences[steps*H*I]  the recorded sequences, as tpc_mpc_rollout_record returns them (required)
  *   states[steps*2]       the recorded states_out of the same call (required)

@@ -20,7 +20,7 @@ ALGO_AUTO, ALGO_WAVE, ALGO_LANE, ALGO_LANE_FMA, ALGO_GROUP = 0, 1, 2, 3, 4
 OPT_WAVE_GROUP, OPT_MAILBOX_HOST, OPT_GROUP_LANES, OPT_HOST_SOLVE_ONE = 1, 2, 3, 4
 DEVICE_NONE = -1   # tpc_mpc_create: a host-only handle
 FLAG_NONFINITE, FLAG_MAX_ITER, FLAG_BAD_MODEL, FLAG_NOT_POLISHED = 0x1, 0x2, 0x4, 0x8
-NEWTON_FALLBACK_SOLVE, NEWTON_FALLBACK_NONE = 0, 1   # tpc_mpc_rollout_newton
+NEWTON_FALLBACK_SOLVE, NEWTON_FALLBACK_NONE = 0, 1   # tpc_mpc_rollout_newton, tpc_mpc_solve_batch_compact_exact
 NEWTON_FALLBACKS = {"solve": NEWTON_FALLBACK_SOLVE, "none": NEWTON_FALLBACK_NONE}
 LOOP_RECORD, LOOP_POLISHED, LOOP_NEWTON = 0, 1, 2   # tpc_mpc_rollout_plant
 PARAM_FAST_CAPPED = 0x1   # tpc_mpc_params.options
@@ -45,7 +45,8 @@ EXPORTS = ("tpc_mpc_default_params", "tpc_mpc_create", "tpc_mpc_destroy", "tpc_m
            "tpc_mpc_solve_batch_general_backward", "tpc_mpc_rollout_record", "tpc_mpc_rollout_backward",
            "tpc_mpc_polish_batch_general", "tpc_mpc_rollout_polished", "tpc_mpc_rollout_newton",
            "tpc_mpc_solve_batch_general_forward", "tpc_mpc_rollout_forward", "tpc_mpc_rollout_plant",
-           "tpc_mpc_rollout_plant_backward", "tpc_mpc_rollout_plant_forward")
+           "tpc_mpc_rollout_plant_backward", "tpc_mpc_rollout_plant_forward",
+           "tpc_mpc_solve_batch_compact_exact")
 SPLIT_BLOCK, SPLIT_INTERLEAVED = 0, 1
 SPLITS = {"block": SPLIT_BLOCK, "interleaved": SPLIT_INTERLEAVED}
 
@@ -180,6 +181,8 @@ def load_library(path: str | None = None) -> C.CDLL:
                                              C.POINTER(Polish), vp, vp, vp, vp, u32p, C.c_int, vp]
     lib.tpc_mpc_rollout_newton.argtypes = [vp, C.POINTER(Params), C.POINTER(GeneralIO), C.c_int32, vp,
                                            C.POINTER(Polish), C.c_int32, vp, vp, vp, vp, vp, u32p, C.c_int, vp]
+    lib.tpc_mpc_solve_batch_compact_exact.argtypes = [vp, C.POINTER(Params), C.c_int64, vp, vp, vp, C.POINTER(Polish),
+                                                      C.c_int32, vp, vp, vp, vp, u32p, C.c_int, vp]
     lib.tpc_mpc_rollout_backward.argtypes = [vp, C.POINTER(Params), C.POINTER(GeneralIO), C.c_int32, vp,
                                              C.POINTER(RolloutGrad), u32p, C.c_int, vp]
     lib.tpc_mpc_solve_batch_general_forward.argtypes = [vp, C.POINTER(Params), C.POINTER(GeneralIO), vp,

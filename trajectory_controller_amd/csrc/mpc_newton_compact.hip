@@ -1,0 +1,131 @@
+// The exact compact solve (tpc_mpc_solve_batch_compact_exact): one lane per instance runs the Newton rounds of the
+// polish from U = 0 on the reference controller's model, built in registers from v (mpc_newton_compact_model.h) --
+// three doubles in, two out, one launch.  Two kernel shapes on the same function, so the same bits:
+//   compact_exact_ws_kernel        run-time H (1 .. 64), per-step values in the handle's gradient workspace
+//                                  ([quantity][step][instance]), as the polish keeps them
+//   compact_exact_reg_kernel<HC>   the reference's horizons 4 and 5: the horizon at compile time, every loop over it
+//                                  unrolled, the per-step values in an array of the lane's own that the compiler keeps
+//                                  in registers -- no workspace memory is touched
+// The instances phase 1 could not verify are collected for the fallback (one atomicAdd per wavefront, as
+// mpc_rollout_newton.hip); gather-expand writes their general form into a compact batch for tpc_mpc_solve_batch_general
+// and tpc_mpc_polish_batch_general, scatter brings the results back.  Explicit fma() only (-ffp-contract=off): device and
+// host path give the same bits, and both equal tpc_mpc_polish_batch_general on the expanded arrays.
+#include "mpc_newton_compact.h"
+
+#include <vector>
+
+namespace tpc {
+
+namespace {
+
+// What a lane does with its instance's result: the flags and its place in the fallback's queue
+__device__ __forceinline__ void exact_finish(const cexact::Args& a, int64_t k, uint32_t f, uint32_t* flags) {
+    const uint32_t raise = a.raise_not_polished ? f : (f & ~0x8u);
+    if (raise) atomicOr(flags, raise);
+    if (!a.fb_index) return;
+    // the fallback's queue: not verified, and nothing else wrong with the instance
+    const bool fb = f == 0x8u;
+    const unsigned long long m = __ballot(fb);
+    if (!m) return;
+    const int lane = __lane_id(), leader = __ffsll((long long)m) - 1;
+    uint32_t base = 0;
+    if (lane == leader) base = atomicAdd(a.fb_count, (uint32_t)__popcll(m));
+    base = __shfl(base, leader);
+    if (fb) a.fb_index[base + __popcll(m & ((1ull << lane) - 1ull))] = (int32_t)k;
+}
+
+__global__ __launch_bounds__(256) void compact_exact_ws_kernel(cexact::Args a, int H, double* ws, uint32_t* flags) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= a.n) return;
+    const uint32_t f = cexact::exact_instance<0>(a, H, k, ws + k, a.n);
+    exact_finish(a, k, f, flags);
+}
+
+template <int HC>
+__global__ __launch_bounds__(256) void compact_exact_reg_kernel(cexact::Args a, uint32_t* flags) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= a.n) return;
+    double regs[cexact::kSlots * HC];   // every index into it is a constant once the horizon's loops are unrolled
+    const uint32_t f = cexact::exact_instance<HC>(a, HC, k, regs, 1);
+    exact_finish(a, k, f, flags);
+}
+
+__global__ __launch_bounds__(256) void compact_exact_gather_kernel(cexact::Args a, CompactExactBatch b) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= b.count) return;
+    const int64_t k = b.index[j], ld = b.ld;
+    const grad::Model m = cexact::build_model(a, a.v[k]);
+    const double tg0 = a.dy[k], tg1 = a.dphi[k];
+    auto out = [&](double* base, int c, double x) { base[(int64_t)c * ld + j] = x; };
+    out(b.A, 0, m.a00); out(b.A, 1, m.a01); out(b.A, 2, m.a10); out(b.A, 3, m.a11);
+    out(b.B, 0, m.b0[0]); out(b.B, 1, m.b0[1]); out(b.B, 2, m.b1[0]); out(b.B, 3, m.b1[1]);
+    out(b.C, 0, m.c0); out(b.C, 1, m.c1);
+    out(b.Q, 0, m.q0); out(b.Q, 1, m.q1);
+    out(b.x0, 0, 0.0); out(b.x0, 1, 0.0);
+    for (int c = 0; c < 2; ++c) { out(b.R, c, m.r[c]); out(b.lo, c, m.lo[c]); out(b.hi, c, m.hi[c]); }
+    for (int t = 0; t < b.H; ++t) {
+        out(b.targets, 2 * t, tg0); out(b.targets, 2 * t + 1, tg1);
+        out(b.controls, 2 * t, 0.0); out(b.controls, 2 * t + 1, 0.0);
+    }
+}
+
+__global__ __launch_bounds__(256) void compact_exact_scatter_kernel(cexact::Args a, CompactExactBatch b) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= b.count) return;
+    const int64_t k = b.index[j], ld = b.ld;
+    a.front[k] = b.u0[j];
+    a.rear[k] = b.u0[ld + j];
+    if (a.seq)
+        for (int c = 0; c < 2 * b.H; ++c) a.seq[(int64_t)c * a.ld_seq + k] = b.controls[(int64_t)c * ld + j];
+    if (a.status) a.status[k] = b.status[j];
+    if (a.res_in) a.res_in[k] = b.res_in[j];
+    if (a.res_out) a.res_out[k] = b.res_out[j];
+    if (a.fell_back) a.fell_back[k] = 1;
+}
+
+}  // namespace
+
+int rollout_grad_block(int64_t n);   // mpc_rollout_grad.hip: the largest of 256, 128, 64 that gives a block per CU
+
+bool compact_exact_in_registers(int H) { return H == 4 || H == 5; }
+
+// A lane's time is its own serial chain of rounds: polish_general's block
+hipError_t compact_exact(int H, const cexact::Args& a, void* ws, uint32_t* flags, hipStream_t s) {
+    if (a.n <= 0) return hipSuccess;
+    const int block = rollout_grad_block(a.n);
+    const unsigned grid = (unsigned)((a.n + block - 1) / block);
+    if (H == 4) hipLaunchKernelGGL(compact_exact_reg_kernel<4>, dim3(grid), dim3(block), 0, s, a, flags);
+    else if (H == 5) hipLaunchKernelGGL(compact_exact_reg_kernel<5>, dim3(grid), dim3(block), 0, s, a, flags);
+    else hipLaunchKernelGGL(compact_exact_ws_kernel, dim3(grid), dim3(block), 0, s, a, H, (double*)ws, flags);
+    return hipGetLastError();
+}
+
+// HOST arrays, on the calling thread: the same exact_instance() per instance
+uint32_t compact_exact_host(int H, const cexact::Args& a) {
+    std::vector<double> ws((size_t)cexact::kSlots * H);
+    uint32_t flags = 0;
+    for (int64_t k = 0; k < a.n; ++k) {
+        const uint32_t f = cexact::exact_instance<0>(a, H, k, ws.data(), 1);
+        flags |= a.raise_not_polished ? f : (f & ~0x8u);
+    }
+    return flags;
+}
+
+static hipError_t batch_launch(bool scatter, const cexact::Args& a, const CompactExactBatch& b, hipStream_t s) {
+    if (b.count <= 0) return hipSuccess;
+    const int block = 256;
+    const unsigned grid = (unsigned)((b.count + block - 1) / block);
+    if (scatter) hipLaunchKernelGGL(compact_exact_scatter_kernel, dim3(grid), dim3(block), 0, s, a, b);
+    else hipLaunchKernelGGL(compact_exact_gather_kernel, dim3(grid), dim3(block), 0, s, a, b);
+    return hipGetLastError();
+}
+
+hipError_t compact_exact_gather(const cexact::Args& a, const CompactExactBatch& b, hipStream_t s) {
+    return batch_launch(false, a, b, s);
+}
+
+hipError_t compact_exact_scatter(const cexact::Args& a, const CompactExactBatch& b, hipStream_t s) {
+    return batch_launch(true, a, b, s);
+}
+
+}  // namespace tpc

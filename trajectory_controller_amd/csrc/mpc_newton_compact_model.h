@@ -1,0 +1,165 @@
+// The exact compact solve (tpc_mpc_solve_batch_compact_exact, include/tpc_mpc.h): phase 1 of ONE instance, shared by
+// the gfx950 kernels (mpc_newton_compact.hip) and the host path of the same entry.  It is polish::polish_instance<2>
+// (mpc_polish_model.h) restated for the reference controller's model, started from U = 0:
+//   - the model comes from v and the call's parameters, in registers: A = [1, Tv; 0, 1], B = [0, Tv; Tv/l, -Tv/l],
+//     C = 0, x0 = 0, every target (dy, dphi) -- no model or target array is read;
+//   - the per-step values go through one pointer, ws[(q * H + t) * wn]: the handle's gradient workspace (run-time H),
+//     or, with a compile-time horizon HC, an array of the lane's own whose every index is then a constant, so that it
+//     lives in registers (a private array indexed by a run-time step lands in scratch).
+// The operation sequence is the general form's on the expanded values, operation for operation -- the "+ C" and the x0
+// terms included: fma(a, b, +0) is not a * b when the product is -0 -- so the result equals
+// tpc_mpc_polish_batch_general on the expanded arrays with zero controls bit for bit (tests/test_compact_exact_host.py).
+// Every fused operation is an explicit fma() and the unit is built with -ffp-contract=off, as mpc_polish_model.h.
+// The Riccati passes are grad::riccati_passes, as they are.
+#pragma once
+
+#include "mpc_polish_model.h"
+
+namespace tpc {
+namespace cexact {
+
+using grad::gabs;
+using grad::gfinite;
+using grad::gfma;
+using polish::clampd;
+
+// v, dy, dphi [n]; the outputs: front, rear [n], seq [H*2] rows ld_seq apart (may be null), and the optional rows of
+// the polish (status, residuals) and fell_back [n], which phase 1 clears
+struct Args {
+    int64_t n;
+    const double *v, *dy, *dphi;
+    double T, l, q0, q1, r[2], lo[2], hi[2];   // tpc_mpc_params: step_size, wheelbase, weights, bounds
+    double tol;
+    int32_t max_rounds;
+    int32_t raise_not_polished;   // FALLBACK_NONE: an unverified instance raises TPC_MPC_FLAG_NOT_POLISHED
+    double *front, *rear, *seq;
+    int64_t ld_seq;
+    int32_t* status;
+    double *res_in, *res_out;
+    int32_t* fell_back;
+    int32_t* fb_index;    // [n] the instances for the fallback, in no particular order; null: not collected
+    uint32_t* fb_count;   // how many
+};
+
+constexpr int kI = 2;
+constexpr int kSlots = polish::slots(kI);   // workspace doubles per step
+
+// the expanded model of one instance, as mpc_compact (autograd.py) builds it; fin / ok as grad::load_model has them
+TPC_GRAD_HD grad::Model build_model(const Args& a, double v) {
+    const double Tv = a.T * v, tvl = Tv / a.l;
+    grad::Model m;
+    m.a00 = 1.0; m.a01 = Tv; m.a10 = 0.0; m.a11 = 1.0;
+    m.c0 = 0.0; m.c1 = 0.0; m.q0 = a.q0; m.q1 = a.q1;
+    m.b0[0] = 0.0; m.b0[1] = Tv;
+    m.b1[0] = tvl; m.b1[1] = -tvl;
+    m.fin = gfinite(v) && gfinite(Tv) && gfinite(tvl) && gfinite(m.q0) && gfinite(m.q1);
+    m.ok = m.q0 >= 0.0 && m.q1 >= 0.0;
+#pragma unroll
+    for (int j = 0; j < kI; ++j) {
+        m.r[j] = a.r[j]; m.lo[j] = a.lo[j]; m.hi[j] = a.hi[j];
+        m.fin = m.fin && gfinite(m.r[j]) && m.lo[j] == m.lo[j] && m.hi[j] == m.hi[j];
+        m.ok = m.ok && m.r[j] > 0.0 && m.hi[j] >= m.lo[j];
+    }
+    return m;
+}
+
+// One instance.  HC > 0: the horizon, at compile time (Hrt is ignored); HC == 0: Hrt.  ws points at the instance's
+// first workspace element.  Returns its TPC_MPC_FLAG_* bits: 0x1 non-finite, 0x4 bad model (both: nothing run), 0x8
+// not verified; in all three cases the outputs are zeros with status -1 (residual_in keeps round 0's value when rounds
+// were run, as the polish reports it).
+template <int HC>
+TPC_GRAD_HD uint32_t exact_instance(const Args& a, int Hrt, int64_t k, double* ws, int64_t wn) {
+    constexpr int I = kI;
+    const int H = HC > 0 ? HC : Hrt;
+    auto slot = [&](int q, int t) -> double& { return ws[((int64_t)q * H + t) * wn]; };
+    const double tg0 = a.dy[k], tg1 = a.dphi[k];
+    const grad::Model m = build_model(a, a.v[k]);
+    const double xs0 = 0.0, xs1 = 0.0;
+    const bool fin = m.fin && gfinite(tg0) && gfinite(tg1);
+    constexpr int kU = 4 + I, kDf = 2 * I;   // first slot of the working copy / of df
+
+    auto finish = [&](int32_t status, double r_in, double r_out) {
+        if (a.status) a.status[k] = status;
+        if (a.res_in) a.res_in[k] = r_in;
+        if (a.res_out) a.res_out[k] = r_out;
+        if (a.fell_back) a.fell_back[k] = 0;
+        a.front[k] = status >= 0 ? slot(kU, 0) : 0.0;
+        a.rear[k] = status >= 0 ? slot(kU + 1, 0) : 0.0;
+        if (a.seq)
+            for (int t = 0; t < H; ++t)
+#pragma unroll
+                for (int j = 0; j < I; ++j)
+                    a.seq[(int64_t)(t * I + j) * a.ld_seq + k] = status >= 0 ? slot(kU + j, t) : 0.0;
+    };
+    const uint32_t bad = (fin ? 0u : 0x1u) | (m.ok ? 0u : 0x4u);
+    if (bad) {
+        finish(-1, 0.0, 0.0);
+        return bad;
+    }
+    for (int t = 0; t < H; ++t)
+#pragma unroll
+        for (int j = 0; j < I; ++j) slot(kU + j, t) = clampd(0.0, m.lo[j], m.hi[j]);
+
+    double res_in = 0.0, prev = 0.0;
+    bool inner = false;
+    for (int round = 0;; ++round) {
+        // ---- gradient, forward: x_{t+1}
+        double x0 = xs0, x1 = xs1;
+        for (int t = 0; t < H; ++t) {
+            double y0 = gfma(m.a00, x0, gfma(m.a01, x1, m.c0)), y1 = gfma(m.a10, x0, gfma(m.a11, x1, m.c1));
+#pragma unroll
+            for (int j = 0; j < I; ++j) {
+                const double u = slot(kU + j, t);
+                y0 = gfma(m.b0[j], u, y0);
+                y1 = gfma(m.b1[j], u, y1);
+            }
+            x0 = y0; x1 = y1;
+            slot(0, t) = x0; slot(1, t) = x1;
+        }
+        // ---- gradient, backward: costate, df, dlib's mask, the residual
+        double P0 = 0.0, P1 = 0.0, res = 0.0;
+        bool okdf = true;
+        for (int t = H - 1; t >= 0; --t) {
+            const double e0 = slot(0, t) - tg0, e1 = slot(1, t) - tg1;
+            const double p0 = gfma(m.a00, P0, gfma(m.a10, P1, m.q0 * e0)), p1 = gfma(m.a01, P0, gfma(m.a11, P1, m.q1 * e1));
+            P0 = p0; P1 = p1;
+#pragma unroll
+            for (int j = 0; j < I; ++j) {
+                const double u = slot(kU + j, t);
+                const double df = gfma(m.b0[j], p0, gfma(m.b1[j], p1, m.r[j] * u));
+                slot(kDf + j, t) = df;
+                okdf = okdf && gfinite(df);
+                const bool blocked = (u <= m.lo[j] && df > 0.0) || (u >= m.hi[j] && df < 0.0) || m.lo[j] == m.hi[j];
+                if (!blocked) res = gabs(df) > res ? gabs(df) : res;
+            }
+        }
+        if (round == 0) res_in = res;
+        if (!okdf) break;   // an intermediate overflowed: not verified
+        if (res <= a.tol) {
+            finish(round, res_in, res);
+            return 0u;
+        }
+        if (round >= a.max_rounds) break;
+        inner = !inner && round > 0 && !(res < prev);
+        prev = res;
+
+        // ---- w = H_FF^-1 df_F, then the clamped step
+        bool f2 = true;
+        double y0, y1, d0, d1;
+        grad::riccati_passes<I>(
+            m, H, xs0, xs1, [&](int t, int j) { return slot(kU + j, t); }, [&](int t, int j) { return slot(kDf + j, t); },
+            [&](int j, double u, double df) {
+                const bool blocked = (u <= m.lo[j] && df > 0.0) || (u >= m.hi[j] && df < 0.0) || m.lo[j] == m.hi[j];
+                return !blocked && !(inner && (u <= m.lo[j] || u >= m.hi[j]));
+            },
+            ws, wn, f2, y0, y1, d0, d1);
+        for (int t = 0; t < H; ++t)
+#pragma unroll
+            for (int j = 0; j < I; ++j) slot(kU + j, t) = clampd(slot(kU + j, t) - slot(4 + j, t), m.lo[j], m.hi[j]);
+    }
+    finish(-1, res_in, 0.0);
+    return 0x8u;
+}
+
+}  // namespace cexact
+}  // namespace tpc

@@ -24,6 +24,8 @@
 //   riccati_passes:           g = df read from slot 2 I + j (before the step's feed-forward is written there),
 //                             leaves w in slot 4 + j
 //   update:                   u in slot 4 + I + j, the working copy -- the caller's array is written on success only
+// The rounds below are restated for the compact model in mpc_newton_compact_model.h (exact_instance), which must stay
+// this function operation for operation: a change to the rounds is made in both (tests/test_compact_exact_host.py).
 #pragma once
 
 #include "mpc_grad_model.h"

@@ -10,6 +10,7 @@
 #include "mpc_grad_model.h"
 #include "mpc_polish_model.h"
 #include "mpc_rollout_newton.h"
+#include "mpc_newton_compact.h"
 #include "mpc_tangent_model.h"
 
 #include <cmath>
@@ -1896,6 +1897,176 @@ int tpc_mpc_rollout_newton(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_
                            uint32_t* flags_out, int mem, void* stream) {
     return rollout_newton_impl(h, p, io, steps, new_last_targets, q, fallback, controls_out, states_out, iters_out,
                                sequences_out, first_unverified, flags_out, mem, stream, nullptr);
+}
+
+// The exact compact solve (include/tpc_mpc.h): phase 1 is ONE launch, three rows in and two (+2H) out
+// (mpc_newton_compact.hip); with TPC_MPC_NEWTON_FALLBACK_SOLVE the instances it could not verify are gathered and
+// expanded to the general form on the device, run through tpc_mpc_solve_batch_general and tpc_mpc_polish_batch_general
+// and scattered back.  One 4-byte read-back (the fallback's count) sits between the phases; a host-only handle runs
+// phase 1 on the calling thread.  The Newton working set of tpc_mpc_rollout_newton holds the staging rows, the queue and
+// the compact batch.
+int tpc_mpc_solve_batch_compact_exact(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t n, const void* v,
+                                      const void* delta_y, const void* delta_phi, const tpc_mpc_polish* q,
+                                      int32_t fallback, void* steering_front, void* steering_rear, void* sequence_out,
+                                      int32_t* fell_back, uint32_t* flags_out, int mem, void* stream) {
+    return guarded(h, [&]() -> int {
+        int rc = check_common(h, p, true);
+        if (rc) return rc;
+        if (p->dtype != TPC_MPC_F64)
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "tpc_mpc_solve_batch_compact_exact is fp64 only: p->dtype must be TPC_MPC_F64");
+        rc = check_compact_model(h, p);
+        if (rc) return rc;
+        if (n < 0 || n > 0x7fffffffll) return fail(h, TPC_MPC_ERR_BAD_ARG, "need 0 <= n < 2^31");
+        if (mem != TPC_MPC_HOST && mem != TPC_MPC_DEVICE) return fail(h, TPC_MPC_ERR_BAD_ARG, "bad memory kind");
+        if (!q) return fail(h, TPC_MPC_ERR_BAD_ARG, "null polish struct");
+        if (!(q->tol > 0.0) || q->max_rounds < 0)
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "polish needs tol > 0 and max_rounds >= 0");
+        if (fallback != TPC_MPC_NEWTON_FALLBACK_SOLVE && fallback != TPC_MPC_NEWTON_FALLBACK_NONE)
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "unknown fallback %d", (int)fallback);
+        const bool solve = fallback == TPC_MPC_NEWTON_FALLBACK_SOLVE;
+        if (h->host_only && solve)
+            return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): the fallback solve runs on the device only; use TPC_MPC_NEWTON_FALLBACK_NONE");
+        if (h->host_only && mem == TPC_MPC_DEVICE)
+            return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): HOST memory only");
+        if (n == 0) { if (flags_out) *flags_out = 0; return TPC_MPC_OK; }
+        if (!v || !delta_y || !delta_phi || !steering_front || !steering_rear)
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "null batch pointer");
+        const int H = p->horizon;
+
+        cexact::Args a;
+        std::memset(&a, 0, sizeof(a));
+        a.n = n;
+        a.T = p->step_size; a.l = p->wheelbase; a.q0 = p->weight_y; a.q1 = p->weight_phi;
+        a.r[0] = p->weight_steering_front; a.r[1] = p->weight_steering_rear;
+        for (int j = 0; j < 2; ++j) { a.lo[j] = p->lower[j]; a.hi[j] = p->upper[j]; }
+        a.tol = q->tol; a.max_rounds = q->max_rounds;
+        a.raise_not_polished = solve ? 0 : 1;
+        a.ld_seq = n;
+
+        if (h->host_only) {   // on the calling thread, straight from and into the caller's arrays
+            a.v = (const double*)v; a.dy = (const double*)delta_y; a.dphi = (const double*)delta_phi;
+            a.front = (double*)steering_front; a.rear = (double*)steering_rear; a.seq = (double*)sequence_out;
+            a.status = q->status; a.res_in = (double*)q->residual_in; a.res_out = (double*)q->residual_out;
+            a.fell_back = fell_back;
+            const uint32_t f = compact_exact_host(H, a);
+            if (flags_out) *flags_out = f;
+            return TPC_MPC_OK;
+        }
+
+        HIP_TRY(h, hipSetDevice(h->device));
+        hipStream_t s = (hipStream_t)stream;
+        StreamOrderScope order(h, s);
+        rc = order.begin();
+        if (rc) return rc;
+        const bool host = mem == TPC_MPC_HOST;
+        // the working set: the queue and two words ([0] the fallback's count, [1] phase 1's flags), then for HOST
+        // arrays the staging rows, leading dimension ldw: v dy dphi | front rear seq[2H] res_in res_out | status fell_back
+        const int64_t ldw = (n + 63) / 64 * 64;
+        const int64_t o_words = ldw * 4, o_stage = o_words + 256;
+        const int64_t rows8 = 3 + 2 + (sequence_out ? 2 * H : 0) + (q->residual_in ? 1 : 0) + (q->residual_out ? 1 : 0);
+        const int64_t o_i32 = o_stage + rows8 * ldw * 8;
+        rc = ensure(h, &h->newton, &h->newton_bytes, host ? o_i32 + 2 * ldw * 4 : o_stage);
+        if (rc) return rc;
+        if (!compact_exact_in_registers(H)) {
+            rc = ensure(h, &h->grad_ws, &h->grad_ws_bytes, pad256(polish_scratch_bytes(2, H, n)));
+            if (rc) return rc;
+        }
+        char* w = (char*)h->newton;
+        int32_t* d_idx = (int32_t*)w;
+        uint32_t* d_words = (uint32_t*)(w + o_words);
+        HIP_TRY(h, hipMemsetAsync(d_words, 0, 8, s));
+        if (!host) {
+            a.v = (const double*)v; a.dy = (const double*)delta_y; a.dphi = (const double*)delta_phi;
+            a.front = (double*)steering_front; a.rear = (double*)steering_rear; a.seq = (double*)sequence_out;
+            a.status = q->status; a.res_in = (double*)q->residual_in; a.res_out = (double*)q->residual_out;
+            a.fell_back = fell_back;
+        } else {
+            int64_t r = 0;
+            auto row = [&](bool on, int64_t rows) -> double* {
+                double* at = on ? (double*)(w + o_stage + r * ldw * 8) : nullptr;
+                if (on) r += rows;
+                return at;
+            };
+            double *sv = row(true, 1), *sdy = row(true, 1), *sdphi = row(true, 1);
+            HIP_TRY(h, hipMemcpyAsync(sv, v, (size_t)n * 8, hipMemcpyHostToDevice, s));
+            HIP_TRY(h, hipMemcpyAsync(sdy, delta_y, (size_t)n * 8, hipMemcpyHostToDevice, s));
+            HIP_TRY(h, hipMemcpyAsync(sdphi, delta_phi, (size_t)n * 8, hipMemcpyHostToDevice, s));
+            a.v = sv; a.dy = sdy; a.dphi = sdphi;
+            a.front = row(true, 1); a.rear = row(true, 1);
+            a.seq = row(sequence_out != nullptr, 2 * H);
+            a.ld_seq = ldw;
+            a.res_in = row(q->residual_in != nullptr, 1); a.res_out = row(q->residual_out != nullptr, 1);
+            a.status = q->status ? (int32_t*)(w + o_i32) : nullptr;
+            a.fell_back = fell_back ? (int32_t*)(w + o_i32 + ldw * 4) : nullptr;
+        }
+        a.fb_index = solve ? d_idx : nullptr;
+        a.fb_count = d_words;
+        hipError_t e = compact_exact(H, a, h->grad_ws, d_words + 1, s);
+        if (e != hipSuccess) return hip_fail(h, e, "kernel launch");
+
+        uint32_t count = 0;
+        if (solve) {
+            HIP_TRY(h, hipMemcpyAsync(&count, d_words, sizeof(count), hipMemcpyDeviceToHost, s));
+            HIP_TRY(h, hipStreamSynchronize(s));
+        }
+        if (count > 0) {
+            // the compact batch, leading dimension ldc: the general form of the queued instances, then what the solve
+            // and the polish return for them
+            const int64_t cnt = count, ldc = (cnt + 63) / 64 * 64;
+            const int64_t rows_fb = 20 + 2 * H + 2 * H + 2 + 2;
+            rc = ensure(h, &h->newton_fb, &h->newton_fb_bytes, rows_fb * ldc * 8 + ldc * 4);
+            if (rc) return rc;
+            char* fb = (char*)h->newton_fb;
+            int64_t r = 0;
+            auto rowf = [&](int64_t rows) { double* at = (double*)(fb + r * ldc * 8); r += rows; return at; };
+            CompactExactBatch b;
+            std::memset(&b, 0, sizeof(b));
+            b.count = cnt; b.ld = ldc; b.index = d_idx; b.H = H;
+            b.A = rowf(4); b.B = rowf(4); b.C = rowf(2); b.Q = rowf(2); b.R = rowf(2); b.lo = rowf(2); b.hi = rowf(2);
+            b.x0 = rowf(2); b.targets = rowf(2 * H); b.controls = rowf(2 * H); b.u0 = rowf(2);
+            b.res_in = rowf(1); b.res_out = rowf(1);
+            b.status = (int32_t*)(fb + rows_fb * ldc * 8);
+            e = compact_exact_gather(a, b, s);
+            if (e != hipSuccess) return hip_fail(h, e, "gather launch");
+
+            tpc_mpc_general_io io2;
+            std::memset(&io2, 0, sizeof(io2));
+            io2.inputs = 2; io2.n = cnt; io2.ld = ldc;
+            io2.A = b.A; io2.B = b.B; io2.C = b.C; io2.Q = b.Q; io2.R = b.R; io2.lower = b.lo; io2.upper = b.hi;
+            io2.x0 = b.x0; io2.targets = b.targets; io2.controls_inout = b.controls; io2.u0 = b.u0;
+            tpc_mpc_polish q2 = *q;
+            q2.status = b.status; q2.residual_in = b.res_in; q2.residual_out = b.res_out;
+            // no flags_out: no synchronisation; each entry resets the handle's flag word, so the solve's flags join
+            // phase 1's before the polish runs, and all of them join the polish's below
+            rc = tpc_mpc_solve_batch_general(h, p, &io2, nullptr, TPC_MPC_DEVICE, stream);
+            if (rc) return rc;
+            e = rollout_newton_merge_flags(d_words + 1, h->ws_words + 1, s);
+            if (e != hipSuccess) return hip_fail(h, e, "flag merge launch");
+            rc = tpc_mpc_polish_batch_general(h, p, &io2, &q2, nullptr, TPC_MPC_DEVICE, stream);
+            if (rc) return rc;
+            e = compact_exact_scatter(a, b, s);
+            if (e != hipSuccess) return hip_fail(h, e, "scatter launch");
+        } else {
+            HIP_TRY(h, hipMemsetAsync(h->ws_words + 1, 0, sizeof(uint32_t), s));
+        }
+        e = rollout_newton_merge_flags(h->ws_words + 1, d_words + 1, s);
+        if (e != hipSuccess) return hip_fail(h, e, "flag merge launch");
+
+        if (host) {
+            HIP_TRY(h, hipMemcpyAsync(steering_front, a.front, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+            HIP_TRY(h, hipMemcpyAsync(steering_rear, a.rear, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+            if (sequence_out)
+                HIP_TRY(h, copy_rows(sequence_out, n * 8, a.seq, ldw * 8, n * 8, 2 * H, hipMemcpyDeviceToHost, s));
+            if (q->residual_in) HIP_TRY(h, hipMemcpyAsync(q->residual_in, a.res_in, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+            if (q->residual_out) HIP_TRY(h, hipMemcpyAsync(q->residual_out, a.res_out, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+            if (q->status) HIP_TRY(h, hipMemcpyAsync(q->status, a.status, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+            if (fell_back) HIP_TRY(h, hipMemcpyAsync(fell_back, a.fell_back, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(h, hipStreamSynchronize(s));
+        }
+        rc = order.end();
+        if (rc) return rc;
+        return finish_flags(h, flags_out, s);
+    });
 }
 
 // what the three plant entries check of a tpc_mpc_plant (after check_common and check_general_io)

@@ -205,6 +205,70 @@ class MpcSolver:
             self.last_flags = flags.value
         return (front, rear, iters) if want_iters else (front, rear)
 
+    def solve_batch_compact_exact(self, v, delta_y, delta_phi, tol: float = 1e-9, max_rounds: int = 16,
+                                  fallback: str = "solve", want_status: bool = True, want_sequence: bool = False,
+                                  want_residuals: bool = False, **over):
+        """n independent mpcControllerTobi calls answered with the verified optimum instead of dlib's eps-0.01 point
+        (tpc_mpc_solve_batch_compact_exact), fp64 only.
+
+        Every instance runs the polish's Newton rounds from U = 0 on the reference controller's model in one launch;
+        fallback="solve" then runs the first-order solve and the polish for the instances the rounds did not verify
+        (p's eps / max_iter / algo), fallback="none" returns (0, 0) with status -1 for them and is what a host-only
+        handle (device=None) serves.  Arrays as in solve_batch_compact (numpy: HOST memory, CUDA tensors: DEVICE memory
+        on the current stream).  Returns (front, rear[, sequence], status, fell_back[, residual_in, residual_out]):
+        sequence [2H, n] with want_sequence; status int32 [n] = the Newton rounds used or -1; fell_back int32 [n] = 1
+        where the solve ran (None with fallback="none"); the residuals with want_residuals.  Sets last_flags
+        (FLAG_NOT_POLISHED if an instance is left unverified, FLAG_NONFINITE for a NaN / Inf input).
+        want_status=False returns None for status and fell_back; with fallback="none" it also leaves last_flags at 0
+        and keeps a DEVICE call asynchronous (fallback="solve" synchronises between its phases anyway and always
+        reports the flags).  want_residuals is for checks: the polish's two residual rows.  max_rounds=16: from 8 to
+        16 halves the share that falls back, 32 gains little.
+        Not differentiable: mpc_compact takes per-instance weights, T, l and bounds that this entry cannot express;
+        mpc_compact(..., polish=True) stays the differentiable route."""
+        p = self._params(**over)
+        H = p.horizon
+        fb = capi.NEWTON_FALLBACKS[fallback]
+        if _is_torch(v):
+            import torch
+            n = v.numel()
+            for t in (v, delta_y, delta_phi):
+                if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == n):
+                    raise ValueError("device batch arrays must be contiguous fp64 CUDA tensors")
+
+            def new(dtype, rows=None):
+                t = torch.empty(n if rows is None else (rows, n),
+                                dtype=torch.float64 if dtype is np.float64 else torch.int32, device=v.device)
+                return t, t.data_ptr()
+            ptr = lambda t: t.data_ptr()
+            stream = C.c_void_p(torch.cuda.current_stream(v.device).cuda_stream)
+            mem = capi.DEVICE
+        else:
+            v, delta_y, delta_phi = (np.ascontiguousarray(a, dtype=np.float64) for a in (v, delta_y, delta_phi))
+            n = v.shape[0]
+
+            def new(dtype, rows=None):
+                a = np.empty(n if rows is None else (rows, n), dtype=dtype)
+                return a, a.ctypes.data
+            ptr = lambda a: a.ctypes.data
+            stream = None
+            mem = capi.HOST
+        front, fp = new(np.float64)
+        rear, rp = new(np.float64)
+        seq, sqp = new(np.float64, 2 * H) if want_sequence else (None, None)
+        status, sp = new(np.int32) if want_status else (None, None)
+        fell, fbp = new(np.int32) if want_status and fallback != "none" else (None, None)
+        rin, rip = new(np.float64) if want_residuals else (None, None)
+        rout, rop = new(np.float64) if want_residuals else (None, None)
+        q = capi.Polish(tol=float(tol), max_rounds=int(max_rounds), reserved=0, status=sp, residual_in=rip,
+                        residual_out=rop)
+        flags = C.c_uint32(0)
+        self._check(self._lib.tpc_mpc_solve_batch_compact_exact(
+            self._h, C.byref(p), n, ptr(v), ptr(delta_y), ptr(delta_phi), C.byref(q), fb, fp, rp, sqp, fbp,
+            C.byref(flags) if want_status or fallback != "none" else None, mem, stream))
+        self.last_flags = flags.value
+        out = (front, rear) + ((seq,) if want_sequence else ()) + (status, fell)
+        return out + ((rin, rout) if want_residuals else ())
+
     def solve_batch_compact_mixed(self, horizons, v, delta_y, delta_phi, want_iters: bool = False, **over):
         """Mixed-horizon batch (BASELINE config 5): instance k is solved with horizon horizons[k]
         (tpc_mpc_solve_batch_compact_mixed: binned by horizon on the device, one launch sequence per
