@@ -1,15 +1,19 @@
 """GPU tests of the exact compact solve (tpc_mpc_solve_batch_compact_exact, MpcSolver.solve_batch_compact_exact): the
-device against the host-only handle bit for bit through the register kernels (H = 4, 5) and the workspace kernel, the
-fallback against solve_batch_general + polish_batch_general on exactly the gathered instances bit for bit, the AUTO
-fallback against the LANE one, the other entries of the handle untouched by an exact call, and one full-size run."""
+device against the host-only handle bit for bit through the register kernels (H = 4, 5) and the workspace kernel under
+every controller model of VARIANTS, the fallback against solve_batch_general + polish_batch_general on exactly the
+gathered instances bit for bit (from the register kernels and under non-default models too), every subset of the
+optional outputs through the C entry, the AUTO fallback against the LANE one, the other entries of the handle untouched
+by an exact call, and one full-size run."""
+import ctypes as C
 import functools
+import itertools
 
 import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 
-from tests.model.compact_exact_common import N, NAMES, ROUNDS, TOL, bits, expand
+from tests.model.compact_exact_common import N, NAMES, ROUNDS, TOL, VARIANTS, bits, expand
 from trajectory_controller_amd import MpcSolver, capi
 from trajectory_controller_amd.synth import compact_inputs
 
@@ -46,9 +50,9 @@ def _inputs(H, n, bad=True):
 
 
 @functools.lru_cache(maxsize=None)
-def _host(H, n, rounds=ROUNDS):
+def _host(H, n, rounds=ROUNDS, variant="default"):
     v, dy, dphi, _ = _inputs(H, n)
-    with MpcSolver(horizon=H, device=None) as s:
+    with MpcSolver(horizon=H, device=None, **VARIANTS[variant]) as s:
         return _exact(s, v, dy, dphi, False, "none", rounds)
 
 
@@ -78,6 +82,25 @@ def test_device_equals_host_only_handle_bits(H, n, device):
     assert bool(flags & capi.FLAG_NONFINITE) == bool(invalid.any())
 
 
+# every model through the register kernels (H = 4, 5) and the workspace kernel (H = 7, 20): unequal bounds, a box that
+# excludes U = 0, a pinned input; and the horizons 1, 2 and 64 of the workspace kernel with the default model
+PER_MODEL = [(H, n, variant) for variant in VARIANTS for H in (4, 5, 7, 20) for n in (65, N)] + \
+    [(H, 65, "default") for H in (1, 2, 64)]
+
+
+@pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
+@pytest.mark.parametrize("H,n,variant", PER_MODEL)
+def test_device_equals_host_only_handle_bits_per_model(H, n, variant, device):
+    v, dy, dphi, invalid = _inputs(H, n)
+    want, wflags = _host(H, n, variant=variant)
+    with MpcSolver(horizon=H, device=0, **VARIANTS[variant]) as s:
+        got, flags = _exact(s, v, dy, dphi, device, "none")
+    print(f"H={H} n={n} {variant}: unverified {int((want[3] < 0).sum()) - int(invalid.sum())}, flags {flags:#x}")
+    _same(got, want)
+    assert flags == wflags
+    assert bool(flags & capi.FLAG_NONFINITE) == bool(invalid.any())
+
+
 # ---- 2. the fallback
 
 def _reference(s, H, v, dy, dphi, idx, device, rounds, **over):
@@ -99,9 +122,9 @@ def _reference(s, H, v, dy, dphi, idx, device, rounds, **over):
     return [u[0], u[1], u, _np(st), None, _np(rin), _np(rout)], f1 | f2
 
 
-def _check_fallback(H, n, device, rounds, algo="lane"):
-    v, dy, dphi, invalid = _inputs(H, n)
-    with MpcSolver(horizon=H, device=0, algo=algo) as s:
+def _check_fallback(H, n, device, rounds, algo="lane", variant="default", bad=True):
+    v, dy, dphi, invalid = _inputs(H, n, bad)
+    with MpcSolver(horizon=H, device=0, algo=algo, **VARIANTS[variant]) as s:
         none, nflags = _exact(s, v, dy, dphi, device, "none", rounds)
         got, flags = _exact(s, v, dy, dphi, device, "solve", rounds)
         fell = got[4]
@@ -113,7 +136,7 @@ def _check_fallback(H, n, device, rounds, algo="lane"):
         _same(got, none, cols=np.flatnonzero(fell == 0), skip=("fell_back",))
         expect = nflags & ~capi.FLAG_NOT_POLISHED
         if idx.size:
-            want, wflags = _reference(s, H, v, dy, dphi, idx, device, rounds)
+            want, wflags = _reference(s, H, v, dy, dphi, idx, device, rounds)      # the variant: the handle's params
             _same([a if a is None else a[..., idx] for a in got], want)
             expect |= wflags
         assert flags == expect
@@ -138,6 +161,88 @@ def test_nobody_falls_back_at_the_reference_horizon():
 def test_everybody_falls_back_without_rounds():
     got, flags, invalid = _check_fallback(10, 1000, True, 0)
     assert np.array_equal(got[4] == 1, ~invalid)
+
+
+# the host path leaves 58, 35, 167, 1, 631 and 282 of these batches unverified (without the two poisoned instances of
+# _inputs, which move a count by at most two): the queue fills from the register kernels, the gather kernel writes
+# unequal bounds and other weights, and (5, weights) is a batch of one through gather and scatter (one live lane)
+@pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
+@pytest.mark.parametrize("H,variant", [(4, "asymmetric"), (4, "offset"), (5, "asymmetric"), (5, "weights"),
+                                       (10, "asymmetric"), (20, "weights")])
+def test_fallback_from_the_register_kernels_and_under_other_models(H, variant, device):
+    got, flags, invalid = _check_fallback(H, N, device, ROUNDS, variant=variant)
+    count = int(got[4].sum())
+    assert count > 0
+    if (H, variant) != (5, "weights"):
+        assert count % 64 != 0          # the last wavefront of the gathered batch is partly live
+    left = (got[3] < 0) & ~invalid
+    assert not left[got[4] == 0].any()
+    assert bool(left.any()) == bool(flags & capi.FLAG_NOT_POLISHED)
+
+
+# max_rounds = 0 verifies nobody: the whole batch goes through a register kernel's queue, whatever order it comes out in
+@pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
+@pytest.mark.parametrize("H,n,variant", [(H, n, "default") for H in (4, 5) for n in (1, 64, 65, 1000)] +
+                         [(4, 65, "asymmetric"), (5, 65, "asymmetric")])
+def test_everybody_falls_back_from_a_register_kernel(H, n, variant, device):
+    got, flags, invalid = _check_fallback(H, n, device, 0, variant=variant, bad=False)
+    # _check_fallback has compared every instance with fell_back = 1 with _reference on exactly those: all of them
+    assert not invalid.any() and np.array_equal(got[4], np.ones(n, dtype=np.int32))
+
+
+# ---- 2b. every subset of the optional outputs, through the C entry
+
+OPTIONAL = ("sequence_out", "residual_in", "residual_out", "status", "fell_back")
+
+
+def _raw_exact(s, H, v, dy, dphi, device, fallback, present, sentinel=-777.0):
+    """tpc_mpc_solve_batch_compact_exact with exactly the optional outputs named in `present`, every given output filled
+    with a sentinel before the call: ({name: numpy array}, flags)"""
+    n = v.shape[0]
+    ins = [_up(a, device) for a in (v, dy, dphi)]
+    f64 = lambda *shape: _up(np.full(shape, sentinel), device)
+    i32 = lambda: _up(np.full(n, -7, dtype=np.int32), device)
+    out = dict(front=f64(n), rear=f64(n))
+    out.update({k: make() for k, make in (("sequence_out", lambda: f64(2 * H, n)), ("residual_in", lambda: f64(n)),
+                                          ("residual_out", lambda: f64(n)), ("status", i32), ("fell_back", i32))
+                if k in present})
+    ptr = lambda a: None if a is None else (a.data_ptr() if device else a.ctypes.data)
+    q = capi.Polish(tol=TOL, max_rounds=ROUNDS, reserved=0, status=ptr(out.get("status")),
+                    residual_in=ptr(out.get("residual_in")), residual_out=ptr(out.get("residual_out")))
+    flags = C.c_uint32(99)
+    rc = s._lib.tpc_mpc_solve_batch_compact_exact(
+        s._h, C.byref(s._params()), n, ptr(ins[0]), ptr(ins[1]), ptr(ins[2]), C.byref(q),
+        capi.NEWTON_FALLBACKS[fallback], ptr(out["front"]), ptr(out["rear"]), ptr(out.get("sequence_out")),
+        ptr(out.get("fell_back")), C.byref(flags), capi.DEVICE if device else capi.HOST, None)
+    assert rc == 0
+    if device:
+        torch.cuda.synchronize()
+    return {k: _np(a) for k, a in out.items()}, flags.value
+
+
+@pytest.mark.parametrize("fallback", ["solve", "none"])
+@pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
+@pytest.mark.parametrize("H", [5, 7])
+def test_every_subset_of_the_optional_outputs(H, device, fallback):
+    """The HOST staging packs its rows by which outputs are present and the scatter kernel writes what is present: the
+    outputs of each of the 32 subsets equal the all-present call's bits, and no given row is left unwritten."""
+    n = 65
+    v, dy, dphi, _ = _inputs(H, n)
+    with MpcSolver(horizon=H, device=0, algo="lane", **VARIANTS["asymmetric"]) as s:
+        full, fflags = _raw_exact(s, H, v, dy, dphi, device, fallback, OPTIONAL)
+        assert np.all(full["status"] != -7) and np.all(full["fell_back"] != -7)
+        assert not any(np.any(full[k] == -777.0) for k in full if k not in ("status", "fell_back"))
+        if fallback == "solve":
+            assert full["fell_back"].sum() > 0      # the scatter kernel ran
+        else:
+            assert not full["fell_back"].any() and (full["status"] < 0).sum() > 2
+        for r in range(len(OPTIONAL) + 1):
+            for present in itertools.combinations(OPTIONAL, r):
+                got, flags = _raw_exact(s, H, v, dy, dphi, device, fallback, present)
+                assert flags == fflags, present
+                assert set(got) == {"front", "rear"} | set(present)
+                for k, a in got.items():
+                    assert a.dtype == full[k].dtype and a.tobytes() == full[k].tobytes(), (present, k)
 
 
 def test_auto_fallback_agrees_with_the_lane_fallback():

@@ -22,21 +22,12 @@ import torch
 from oracle.bindings import Oracle
 from tests.model import mpc_grad_dense as dense
 from tests.model import mpc_polish_dense as pd
-from tests.model.compact_exact_common import N, NAMES, ROUNDS, TOL, bits, expand
+from tests.model.compact_exact_common import N, NAMES, ROUNDS, TOL, VARIANTS, bits, expand
 from trajectory_controller_amd import MpcSolver, capi
 from trajectory_controller_amd.synth import compact_inputs
 
 assert NAMES == dense.NAMES
 HS = (1, 4, 5, 7, 10, 20, 40, 64)
-AMAX = 22.0 * np.pi / 180.0
-VARIANTS = {
-    "default": {},
-    "weights": dict(weight_y=3.0, weight_phi=11.0, weight_steering_front=0.02, weight_steering_rear=0.7,
-                    step_size=0.05, wheelbase=0.3),
-    "asymmetric": dict(lower=(-0.05, -0.3), upper=(0.2, 0.01)),
-    "offset": dict(lower=(0.01, -0.3), upper=(0.2, -0.02)),       # U = 0 lies outside the box
-    "pinned": dict(lower=(-AMAX, 0.02), upper=(AMAX, 0.02)),      # the rear input pinned (lower == upper)
-}
 # unverified of 4096 after 16 rounds by tpc_mpc_polish_batch_general(controls = 0) before this entry existed
 PARENT_UNVERIFIED = {4: 0, 5: 0, 10: 38, 20: 125, 40: 189}
 ORACLE_STRIDE = {64: 128}      # H -> every how-manyth instance meets the oracle (default: every one)
