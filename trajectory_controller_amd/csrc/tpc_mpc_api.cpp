@@ -694,8 +694,10 @@ static void compact_args(tpc_mpc_context* h, const tpc_mpc_params* p, int64_t n,
 // prediction, not a decision: an instance it takes comes back with dlib's bits whether it capped or not, one it misses is
 // caught by the flag-driven second pass as before.  Horizons below 30 never get near the cap with dlib's defaults and
 // (and N = 30: lambda <= 1.1e6 at 4 m/s) are left alone: a presolve that finds nothing still costs GROUP its share of the chip.
+// No presolve when smo_iters >= max_iter: every instance then ends inside the coordinate-descent phase, where nothing is
+// queued and so nothing merged, while the second pass would still skip what the prediction names (mpc_lane.h, SUBSET 1).
 double presolve_lambda_impl(const tpc_mpc_params* p) {
-    if (p->horizon < 40 || p->max_iter < 2000) return 0.0;
+    if (p->horizon < 40 || p->max_iter < 2000 || p->smo_iters >= p->max_iter) return 0.0;
     const double t = (double)p->max_iter / 7.0;
     return t * t;
 }
