@@ -33,8 +33,8 @@ extern "C" {
 #endif
 
 #define TPC_MPC_ABI_VERSION 5   /* 5 = 4 + new symbols only (the split-named sharded entries; later additions, such as
-                                   tpc_mpc_solve_batch_general_backward, tpc_mpc_rollout_record / _backward / _polished / _newton and tpc_mpc_polish_batch_general,
-                                   are new symbols and structs only and keep 5);
+                                   tpc_mpc_solve_batch_general_backward, tpc_mpc_rollout_record / _backward / _polished / _newton, tpc_mpc_polish_batch_general
+                                   and tpc_mpc_solve_batch_compact_exact / _exact_backward, are new symbols and structs only and keep 5);
                                    4 broke 3: tpc_mpc_params.reserved became .options and must be zero-initialised */
 
 typedef struct tpc_mpc_context* tpc_mpc_handle;
@@ -516,6 +516,60 @@ int tpc_mpc_solve_batch_compact_exact(tpc_mpc_handle h, const tpc_mpc_params* p,
                                       const void* delta_y, const void* delta_phi, const tpc_mpc_polish* q,
                                       int32_t fallback, void* steering_front, void* steering_rear, void* sequence_out,
                                       int32_t* fell_back, uint32_t* flags_out, int mem, void* stream);
+
+/* The incoming gradient and the outputs of tpc_mpc_solve_batch_compact_exact_backward, fp64.  The ten shared
+ * parameters are indexed 0 weight_y, 1 weight_phi, 2 weight_steering_front, 3 weight_steering_rear, 4 step_size,
+ * 5 wheelbase, 6 lower[0], 7 lower[1], 8 upper[0], 9 upper[1]. */
+typedef struct tpc_mpc_compact_grad {
+    const void *grad_front, *grad_rear;   /* [n] dL/dsteering_front, dL/dsteering_rear; either may be NULL (zero) */
+    const void *grad_sequence;            /* optional [H*2], ld n: dL/dsequence_out; NULL (zero)                  */
+    void *dv, *ddelta_y, *ddelta_phi;     /* optional outputs [n]                                                 */
+    void *dparams_rows;                   /* optional output [10], ld n: per-instance dL/d(shared parameter)      */
+    void *dparams;                        /* optional output [10]: their sum over the batch                       */
+    void *kkt_residual;                   /* optional output [n], as tpc_mpc_general_grad                         */
+} tpc_mpc_compact_grad;
+
+/* No reference counterpart.  The backward pass of tpc_mpc_solve_batch_compact_exact: for n instances that share p's
+ * weights, step_size, wheelbase and bounds, the gradient of a loss L(steering_front, steering_rear, sequence_out) with
+ * respect to v, delta_y, delta_phi and those ten shared parameters, without the general form ever being written.
+ *   Definition.  Instance k has the expanded model of tpc_mpc_solve_batch_compact_exact (T = p->step_size,
+ *   l = p->wheelbase, Tv = T * v: A = [1, Tv; 0, 1], B = [0, Tv; Tv/l, -Tv/l], C = 0, x0 = 0, every target
+ *   (delta_y, delta_phi)).  Its incoming gradient is g(t, j) = grad_sequence[t*2+j], plus grad_front at (0, 0) and
+ *   grad_rear at (0, 1), added in the order grad_sequence + grad_front; an absent array counts as +0.0.  The adjoint
+ *   sweep of tpc_mpc_solve_batch_general_backward (csrc/mpc_grad_model.h, qp_step<2>, unchanged) runs on that model,
+ *   `sequence` and g; call its sums s (dA, dB, dQ, dR, dlower, dupper, kkt of that entry) and its dL/dtarget_t
+ *   (a_t, b_t), which arrive with t from H-1 down to 0.  Then, every operation rounded on its own:
+ *     S = s.A01 + s.B0[1]      D = s.B1[0] - s.B1[1]      Tv = T * v
+ *     dv         = T * S + (T / l) * D
+ *     ddelta_y   = ((0.0 + a_{H-1}) + a_{H-2}) + ... + a_0          ddelta_phi likewise with b_t
+ *     rows[0..3] = s.Q0, s.Q1, s.R[0], s.R[1]
+ *     rows[4]    = v * S + (v / l) * D                               (step_size)
+ *     rows[5]    = -((Tv / l) / l) * D                               (wheelbase)
+ *     rows[6..9] = s.lo[0], s.lo[1], s.hi[0], s.hi[1]
+ *     kkt_residual = s.kkt
+ *   These equal, bit for bit up to the sign of a zero, tpc_mpc_solve_batch_general_backward on the expanded arrays pushed
+ *   through the same lines.  dparams[c] is the sum of rows[c] over the contributing instances.
+ *   Excluded instances.  status != NULL && status[k] < 0 (nobody should differentiate the (0, 0) that stands in for an
+ *   unverified instance); a non-finite v, target, sequence, g or model value (TPC_MPC_FLAG_NONFINITE); a model that
+ *   breaks dlib's requires clause (TPC_MPC_FLAG_BAD_MODEL).  An excluded instance gets 0.0 in every per-instance output
+ *   and adds nothing to dparams; a negative status raises no flag of its own.
+ *   Method.  One lane per instance (csrc/mpc_compact_grad.hip): 3 + 2H doubles and the incoming gradient in, three
+ *   doubles out; the per-step values in the handle's gradient workspace, at horizons 4 and 5 in registers.  dparams
+ *   is summed without floating-point atomics: a fixed butterfly inside a wavefront, the block's wavefronts in order,
+ *   one partial row per block, one single-block launch over the blocks in a fixed order -- the same call on the same
+ *   data returns the same bytes every time.  The order depends on n; it is not the ascending-k order.
+ * p is validated as tpc_mpc_solve_batch_compact validates it.  v, delta_y, delta_phi [n] and sequence (SoA [H*2], leading
+ * dimension n, as sequence_out) are required; status (int32 [n]) is optional.  fp64 only, horizons 1..64.  A null g, a
+ * null sequence or a dtype other than TPC_MPC_F64 return TPC_MPC_ERR_BAD_ARG.  n == 0 returns TPC_MPC_OK with flags 0
+ * and writes zeros to dparams.  HOST arrays are staged; with DEVICE memory and flags_out == NULL the call is
+ * asynchronous on `stream`.  A host-only handle (TPC_MPC_DEVICE_NONE) runs HOST batches on the calling thread with the
+ * kernel's per-instance bits, its dparams summed in ascending k, and returns TPC_MPC_ERR_NO_DEVICE for DEVICE memory. */
+int tpc_mpc_solve_batch_compact_exact_backward(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t n, const void* v,
+                                               const void* delta_y, const void* delta_phi,
+                                               const void* sequence /* [H*2], ld n */,
+                                               const int32_t* status /* optional [n] */,
+                                               const tpc_mpc_compact_grad* g, uint32_t* flags_out, int mem,
+                                               void* stream);
 
 /* Inputs and outputs of tpc_mpc_rollout_backward, SoA with the io's leading dimension ld:
  *   sequences[steps*H*I]  the recorded sequences, as tpc_mpc_rollout_record returns them (required)

@@ -1,0 +1,256 @@
+"""GPU tests of the exact compact solve's backward pass (tpc_mpc_solve_batch_compact_exact_backward,
+MpcSolver.solve_batch_compact_exact_backward, mpc_compact_exact): the device against the host-only handle bit for bit
+through the register kernels (H = 4, 5) and the workspace kernel, the device's deterministic batch sum of the shared
+parameters' gradients, the handle's other entries untouched by a call, the autograd function against the raw entries,
+the gradients against the general-form route mpc_compact(..., polish=True), and one full-size run."""
+import functools
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+
+from tests.model import compact_grad_common as cg
+from tests.model.compact_grad_common import NAMES, VARIANTS, bits, expand
+from trajectory_controller_amd import COMPACT_PARAM_NAMES, MpcSolver, capi, mpc_compact, mpc_compact_exact
+from trajectory_controller_amd.synth import compact_inputs
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+TOL, ROUNDS = 1e-9, 16
+ALL = ("v", "delta_y", "delta_phi", "params", "params_rows", "kkt_residual")
+NS = (1, 63, 65, 300, 4096)   # a lone lane, a partial wavefront, one lane into the second, a partial block, many blocks
+
+
+def _up(a, device=True):
+    if a is None:
+        return None
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV) if device else np.ascontiguousarray(a)
+
+
+def _np(a):
+    return None if a is None else np.ascontiguousarray(a.cpu().numpy() if torch.is_tensor(a) else a)
+
+
+@functools.lru_cache(maxsize=None)
+def _case(H, n, variant="default"):
+    """inputs, the host-only handle's forward (sequence, status) and backward, shared by the tests (never modified).
+    From 63 instances on: one NaN speed (the forward gives it status -1 and a zero sequence) and one verified instance
+    whose status is set to -1."""
+    v, dy, dphi = (a.copy() for a in compact_inputs(H, n))
+    if n >= 63:
+        v[5] = np.nan
+    gf, gr, gs = cg.grad_in(H, n, 17 + H, sequence=True)
+    with MpcSolver(horizon=H, device=None, **VARIANTS[variant]) as s:
+        _, _, seq, st, _ = s.solve_batch_compact_exact(v, dy, dphi, tol=TOL, max_rounds=ROUNDS, fallback="none",
+                                                       want_sequence=True)
+        if n >= 63:
+            st = st.copy()
+            st[np.flatnonzero(st >= 0)[7]] = -1
+        want = s.solve_batch_compact_exact_backward(v, dy, dphi, seq, gf, gr, gs, status=st, want=ALL)
+        flags = s.last_flags
+    return dict(v=v, dy=dy, dphi=dphi, seq=seq, st=st, gf=gf, gr=gr, gs=gs, want=want, flags=flags)
+
+
+def _backward(s, c, device, want=ALL, status=True):
+    args = [_up(c[k], device) for k in ("v", "dy", "dphi", "seq", "gf", "gr", "gs")]
+    got = s.solve_batch_compact_exact_backward(*args, status=_up(c["st"], device) if status else None, want=want)
+    if device:
+        torch.cuda.synchronize()
+    return {k: _np(a) for k, a in got.items()}, s.last_flags
+
+
+# ---- 1. device against host: H = 4, 5 the register kernels, the others the workspace kernel
+
+@pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
+@pytest.mark.parametrize("H", [1, 4, 5, 7, 10, 20, 40, 64])
+def test_device_equals_host_only_handle_bits(H, device):
+    with MpcSolver(horizon=H, device=0) as s:
+        for n in NS:
+            c = _case(H, n)
+            got, flags = _backward(s, c, device)
+            for k in cg.PER_INSTANCE:
+                assert got[k].tobytes() == c["want"][k].tobytes(), (n, k)
+            assert flags == c["flags"] == (capi.FLAG_NONFINITE if n >= 63 else 0), n
+            excluded = c["st"] < 0
+            for k in cg.PER_INSTANCE:
+                assert not bits(got[k][..., excluded]).any(), (n, k)
+            assert np.all(np.abs(got["params"] - c["want"]["params"]) <= 2 * cg.fsum_bound(got["params_rows"])), n
+
+
+@pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
+@pytest.mark.parametrize("variant", [k for k in VARIANTS if k != "default"])
+@pytest.mark.parametrize("H", [4, 20])
+def test_device_equals_host_only_handle_bits_per_model(H, variant, device):
+    with MpcSolver(horizon=H, device=0, **VARIANTS[variant]) as s:
+        for n in (65, 300):
+            c = _case(H, n, variant)
+            got, flags = _backward(s, c, device)
+            for k in cg.PER_INSTANCE:
+                assert got[k].tobytes() == c["want"][k].tobytes(), (n, k)
+            assert flags == c["flags"]
+
+
+# ---- 2. dparams on the device: no floating-point atomics, a fixed order
+
+@pytest.mark.parametrize("H", [4, 20])
+def test_dparams_is_deterministic_and_within_the_bound_of_any_order(H):
+    with MpcSolver(horizon=H, device=0) as s:
+        for n in NS:     # n = 1 and n = 65: a block whose other wavefronts are empty
+            c = _case(H, n)
+            got, _ = _backward(s, c, True)
+            rows = got["params_rows"]
+            diff = np.abs(got["params"] - cg.fsum_rows(rows))
+            print(f"H={H} n={n}: max |dparams - fsum| / bound "
+                  f"{np.max(diff / np.maximum(cg.fsum_bound(rows), 1e-300)):.3f}")
+            assert np.all(diff <= cg.fsum_bound(rows)), (n, diff, cg.fsum_bound(rows))
+            again, _ = _backward(s, c, True)
+            assert again["params"].tobytes() == got["params"].tobytes(), n
+            with torch.cuda.stream(torch.cuda.Stream(device=DEV)):
+                other, _ = _backward(s, c, True)
+            assert other["params"].tobytes() == got["params"].tobytes(), n
+            alone, _ = _backward(s, c, True, want=("params",))       # the per-instance outputs not requested
+            assert set(alone) == {"params"} and alone["params"].tobytes() == got["params"].tobytes(), n
+            staged, _ = _backward(s, c, False, want=("params",))     # HOST arrays: the same launches
+            assert staged["params"].tobytes() == got["params"].tobytes(), n
+
+
+# ---- 3. the handle's other entries: the gradient workspace is shared
+
+def test_other_entries_return_the_same_bytes_around_a_backward_call():
+    H, n = 10, 300
+    c = _case(H, n)
+    tv, ty, tp = (_up(c[k]) for k in ("v", "dy", "dphi"))
+    th = expand(capi.default_params(H), H, *compact_inputs(H, n))
+    ins = [_up(th[k]) for k in NAMES]
+    g = _up(cg.expanded_gradient(H, n, c["gf"], c["gr"], c["gs"]))
+
+    def others(s):
+        out = [a for a in s.solve_batch_compact_exact(tv, ty, tp, tol=TOL, max_rounds=ROUNDS, want_sequence=True,
+                                                      want_residuals=True) if a is not None]
+        u = torch.zeros((2 * H, n), dtype=torch.float64, device=DEV)
+        out += [s.solve_batch_general(*ins, controls=u, inputs=2)]
+        out += list(s.polish_batch_general(*ins, u, tol=TOL, max_rounds=ROUNDS, inputs=2))
+        out += list(s.solve_batch_general_backward(*ins, u, g, inputs=2).values())
+        torch.cuda.synchronize()
+        return [_np(a).tobytes() for a in out]
+
+    with MpcSolver(horizon=H, device=0) as s:
+        before = others(s)
+        got, _ = _backward(s, c, True)
+        assert others(s) == before
+        again, _ = _backward(s, c, True)
+        for k in ALL:
+            assert again[k].tobytes() == got[k].tobytes(), k
+
+
+# ---- 4. autograd
+
+@pytest.mark.parametrize("where", ["cuda", "cpu"])
+@pytest.mark.parametrize("H", [4, 20])
+def test_autograd_equals_the_raw_entries(H, where):
+    n = 300
+    v, dy, dphi = compact_inputs(H, n)
+    rng = np.random.default_rng(4)
+    cf, cr = _up(rng.standard_normal(n)), _up(rng.standard_normal(n))
+    wdev = DEV if where == "cuda" else "cpu"
+    with MpcSolver(horizon=H, device=0) as s:
+        p = s.params
+        w0 = [p.weight_y, p.weight_phi, p.weight_steering_front, p.weight_steering_rear]
+        tv, ty, tp = (_up(a).requires_grad_() for a in (v, dy, dphi))
+        weights = torch.tensor(w0, dtype=torch.float64, device=wdev, requires_grad=True)
+        step = torch.tensor(p.step_size, dtype=torch.float64, device=wdev)      # given, requires no grad
+        lower = torch.tensor(list(p.lower), dtype=torch.float64, device=wdev, requires_grad=True)
+        front, rear = mpc_compact_exact(s, tv, ty, tp, weights=weights, step_size=step, lower=lower,
+                                        upper=tuple(p.upper), tol=TOL, max_rounds=ROUNDS)      # a plain tuple stays fp64
+        rf, rr, seq, st, _ = s.solve_batch_compact_exact(tv.detach(), ty.detach(), tp.detach(), tol=TOL,
+                                                         max_rounds=ROUNDS, want_sequence=True)
+        torch.cuda.synchronize()
+        assert _np(front.detach()).tobytes() == _np(rf).tobytes() and _np(rear.detach()).tobytes() == _np(rr).tobytes()
+        (cf * front + cr * rear).sum().backward()
+        raw = s.solve_batch_compact_exact_backward(tv.detach(), ty.detach(), tp.detach(), seq, cf, cr, status=st)
+        torch.cuda.synchronize()
+        for t, k in ((tv, "v"), (ty, "delta_y"), (tp, "delta_phi")):
+            assert _np(t.grad).tobytes() == _np(raw[k]).tobytes(), k
+        assert weights.grad.device.type == where and lower.grad.device.type == where
+        assert _np(weights.grad).tobytes() == _np(raw["params"][0:4]).tobytes()
+        assert _np(lower.grad).tobytes() == _np(raw["params"][6:8]).tobytes()
+        assert step.grad is None
+        # inputs that require no grad get None; with nothing to differentiate the backward entry is not called
+        tv2 = _up(v)
+        w2 = weights.detach().clone().requires_grad_()
+        front, rear = mpc_compact_exact(s, tv2, ty.detach(), tp.detach(), weights=w2, tol=TOL, max_rounds=ROUNDS)
+        (cf * front + cr * rear).sum().backward()
+        assert tv2.grad is None and _np(w2.grad).tobytes() == _np(raw["params"][0:4]).tobytes()
+
+
+# ---- 5. against the general-form route
+
+@pytest.mark.parametrize("H", [4, 20])
+def test_gradients_agree_with_mpc_compact_polished(H):
+    """Both routes take the same derivative (qp_step on the expanded model) at sequences that agree to rounding, so the
+    bound is the project's host-against-dense bound, 1e-8 norm-wise (test_host_backward_matches_dense_reference).  The
+    loss is a random linear one restricted to the instances both routes verify, so the summed weight gradients hold
+    the same instances on both sides."""
+    n = 4096
+    v, dy, dphi = compact_inputs(H, n)
+    rng = np.random.default_rng(8)
+    cf, cr = rng.standard_normal(n), rng.standard_normal(n)
+    with MpcSolver(horizon=H, device=0) as s:
+        p = s.params
+        w0 = [p.weight_y, p.weight_phi, p.weight_steering_front, p.weight_steering_rear]
+        # who the general-form route verifies: its own solve + polish, as mpc_general runs them
+        th = expand(p, H, v, dy, dphi)
+        ins = [_up(th[k]) for k in NAMES]
+        u = torch.zeros((2 * H, n), dtype=torch.float64, device=DEV)
+        s.solve_batch_general(*ins, controls=u, inputs=2)
+        _, pst, _, _ = s.polish_batch_general(*ins, u, tol=TOL, max_rounds=8, inputs=2)      # polish=True is (1e-9, 8)
+        _, _, est, _ = s.solve_batch_compact_exact(_up(v), _up(dy), _up(dphi), tol=TOL, max_rounds=ROUNDS)
+        both = (pst >= 0) & (est >= 0)
+        assert int(both.sum()) >= 0.95 * n
+        mf, mr = _up(cf) * both, _up(cr) * both
+        grads = {}
+        for route in ("exact", "general"):
+            tv, ty, tp = (_up(a).requires_grad_() for a in (v, dy, dphi))
+            w = torch.tensor(w0, dtype=torch.float64, device=DEV, requires_grad=True)
+            if route == "exact":
+                front, rear = mpc_compact_exact(s, tv, ty, tp, weights=w, tol=TOL, max_rounds=ROUNDS, fallback="solve")
+            else:
+                front, rear = mpc_compact(s, tv, ty, tp, w, step_size=p.step_size, wheelbase=p.wheelbase,
+                                          lower=tuple(p.lower), upper=tuple(p.upper), polish=True)
+            (mf * front + mr * rear).sum().backward()
+            torch.cuda.synchronize()
+            grads[route] = [_np(t.grad) for t in (tv, ty, tp, w)]
+    keep = _np(both)
+    worst = 0.0
+    for name, a, b in zip(("v", "delta_y", "delta_phi", "weights"), grads["exact"], grads["general"]):
+        if name != "weights":
+            a, b = a[keep], b[keep]
+        rel = np.linalg.norm(a - b) / np.linalg.norm(b)
+        print(f"H={H} d{name}: norm-wise relative difference {rel:.3e}")
+        worst = max(worst, rel)
+    print(f"H={H}: both verify {int(keep.sum())}/{n}, worst {worst:.3e}")
+    assert worst <= 1e-8
+
+
+# ---- 6. full size
+
+def test_full_size_call():
+    H, n = 20, 262144
+    v, dy, dphi = compact_inputs(H, n)
+    gf, gr, gs = cg.grad_in(H, n, 2, sequence=True)
+    with MpcSolver(horizon=H, device=0) as s:
+        tv, ty, tp = _up(v), _up(dy), _up(dphi)
+        _, _, seq, st, _ = s.solve_batch_compact_exact(tv, ty, tp, tol=TOL, max_rounds=ROUNDS, want_sequence=True)
+        fflags = s.last_flags
+        got = s.solve_batch_compact_exact_backward(tv, ty, tp, seq, _up(gf), _up(gr), _up(gs), status=st, want=ALL)
+        torch.cuda.synchronize()
+        flags = s.last_flags
+    print(f"262144 x N=20: forward flags {fflags:#x}, backward flags {flags:#x}, excluded {int((_np(st) < 0).sum())}, "
+          f"dparams {dict(zip(COMPACT_PARAM_NAMES, _np(got['params']).tolist()))}")
+    assert flags == fflags & capi.FLAG_NONFINITE
+    assert np.all(np.isfinite(_np(got["params"])))
+    for k in cg.PER_INSTANCE:
+        assert np.all(np.isfinite(_np(got[k]))), k
+    rows = _np(got["params_rows"])
+    assert np.all(np.abs(_np(got["params"]) - cg.fsum_rows(rows)) <= cg.fsum_bound(rows))

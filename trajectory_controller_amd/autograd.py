@@ -1,6 +1,7 @@
 """torch autograd over the batched general-form solve: `mpc_general` and the reference controller's `mpc_compact`,
 and over the closed loop: `mpc_rollout` (forward MpcSolver.rollout_record, or rollout_polished with polish=True;
-backward tpc_mpc_rollout_backward).
+backward tpc_mpc_rollout_backward); and `mpc_compact_exact`, the reference controller with shared parameters on the
+exact compact solve and its own backward kernel (no general form on either side).
 
 Forward is MpcSolver.solve_batch_general from a fresh controller (zero controls); backward is
 tpc_mpc_solve_batch_general_backward on torch's current stream (include/tpc_mpc.h gives the definition of the
@@ -259,3 +260,83 @@ def mpc_compact(solver, v, delta_y, delta_phi, weights, step_size=0.1, wheelbase
     u = mpc_general(solver, A, B, torch.zeros(2, n, **f64), w[0:2], w[2:4], rows(lower, 2), rows(upper, 2),
                     torch.zeros(2, n, **f64), targets, polish=polish, **over)
     return u[0], u[1]
+
+
+class _MpcCompactExact(torch.autograd.Function):
+    PARAMS = ("weights", "step_size", "wheelbase", "lower", "upper")
+    SLICES = {"weights": slice(0, 4), "step_size": 4, "wheelbase": 5, "lower": slice(6, 8), "upper": slice(8, 10)}
+
+    @staticmethod
+    def forward(ctx, solver, over, polish, v, delta_y, delta_phi, weights, step_size, wheelbase, lower, upper):
+        tol, rounds, fallback = polish
+        ins = [t.detach().contiguous() for t in (v, delta_y, delta_phi)]
+        front, rear, sequence, status, _ = solver.solve_batch_compact_exact(
+            *ins, tol=tol, max_rounds=rounds, fallback=fallback, want_sequence=True, **over)
+        ctx.solver, ctx.over = solver, over
+        # where each given parameter's gradient goes
+        ctx.like = [None if t is None else (t.device, t.dtype, t.shape)
+                    for t in (weights, step_size, wheelbase, lower, upper)]
+        ctx.save_for_backward(*ins, sequence, status)
+        return front, rear
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_front, grad_rear):
+        v, delta_y, delta_phi, sequence, status = ctx.saved_tensors
+        need = ctx.needs_input_grad[3:]
+        want = tuple(k for k, on in zip(("v", "delta_y", "delta_phi"), need[:3]) if on)
+        if any(need[3:]):
+            want += ("params",)
+        if not want:
+            return (None,) * 11
+        g = ctx.solver.solve_batch_compact_exact_backward(
+            v, delta_y, delta_phi, sequence, grad_front=grad_front.contiguous(), grad_rear=grad_rear.contiguous(),
+            status=status, want=want, want_flags=False, **ctx.over)
+        out = [g.get("v"), g.get("delta_y"), g.get("delta_phi")]
+        for name, like, on in zip(_MpcCompactExact.PARAMS, ctx.like, need[3:]):
+            if not on:
+                out.append(None)
+                continue
+            d = g["params"][_MpcCompactExact.SLICES[name]]
+            out.append(d.to(device=like[0], dtype=like[1]).reshape(like[2]))
+        return (None, None, None) + tuple(out)
+
+
+def mpc_compact_exact(solver, v, delta_y, delta_phi, weights=None, step_size=None, wheelbase=None, lower=None,
+                      upper=None, tol=1e-9, max_rounds=16, fallback="solve", **over):
+    """mpcControllerTobi for n instances that share ONE set of weights, T, l and bounds, answered with the verified
+    optimum and differentiable: returns (front, rear), each [n].
+
+    The forward is MpcSolver.solve_batch_compact_exact (three doubles in, two out per instance, the sequence and the
+    status kept); the backward is one call of tpc_mpc_solve_batch_compact_exact_backward on torch's current stream --
+    neither side materialises the general form.  v, delta_y, delta_phi are CUDA fp64 tensors [n].  The shared
+    parameters are tensors `weights` [4] (weight_y, weight_phi, weight_steering_front, weight_steering_rear),
+    `step_size` [], `wheelbase` [], `lower` [2] and `upper` [2], on any device; None takes the solver's own value
+    (with `over`'s overrides).  Their VALUES go into tpc_mpc_params by value: that is one small device-to-host read per
+    given parameter and call when they live on the GPU (keep them on the CPU to avoid it).  Gradients reach v,
+    delta_y, delta_phi and every given parameter that requires grad (the batch sum, reduced on the device in a fixed
+    order, sliced onto the parameter tensors); an instance left unverified (status -1, fallback="none" or a failed
+    fallback) or with non-finite data gets zero gradients and adds nothing to the parameters'.  Once-differentiable,
+    no forward mode.  mpc_compact remains the route for per-instance weights, T, l and bounds."""
+    for t in (v, delta_y, delta_phi):
+        if not (t.is_cuda and t.dtype == torch.float64):
+            raise ValueError("mpc_compact_exact takes CUDA fp64 tensors v, delta_y, delta_phi")
+    over = dict(over)
+    given = []
+    for name, t, shape in (("weights", weights, (4,)), ("step_size", step_size, ()), ("wheelbase", wheelbase, ()),
+                           ("lower", lower, (2,)), ("upper", upper, (2,))):
+        if t is None:
+            given.append(None)
+            continue
+        t = t if torch.is_tensor(t) else torch.as_tensor(t, dtype=torch.float64)
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} must have shape {list(shape)}")
+        val = t.detach().to(device="cpu", dtype=torch.float64).tolist()
+        if name == "weights":
+            over.update(weight_y=val[0], weight_phi=val[1], weight_steering_front=val[2],
+                        weight_steering_rear=val[3])
+        else:
+            over[name] = tuple(val) if shape else val
+        given.append(t)
+    return _MpcCompactExact.apply(solver, over, (float(tol), int(max_rounds), fallback), v, delta_y, delta_phi,
+                                  *given)

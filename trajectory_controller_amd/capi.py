@@ -46,7 +46,10 @@ EXPORTS = ("tpc_mpc_default_params", "tpc_mpc_create", "tpc_mpc_destroy", "tpc_m
            "tpc_mpc_polish_batch_general", "tpc_mpc_rollout_polished", "tpc_mpc_rollout_newton",
            "tpc_mpc_solve_batch_general_forward", "tpc_mpc_rollout_forward", "tpc_mpc_rollout_plant",
            "tpc_mpc_rollout_plant_backward", "tpc_mpc_rollout_plant_forward",
-           "tpc_mpc_solve_batch_compact_exact")
+           "tpc_mpc_solve_batch_compact_exact", "tpc_mpc_solve_batch_compact_exact_backward")
+# the shared parameters of tpc_mpc_solve_batch_compact_exact_backward, in the order of its dparams / dparams_rows
+COMPACT_PARAM_NAMES = ("weight_y", "weight_phi", "weight_steering_front", "weight_steering_rear", "step_size",
+                       "wheelbase", "lower[0]", "lower[1]", "upper[0]", "upper[1]")
 SPLIT_BLOCK, SPLIT_INTERLEAVED = 0, 1
 SPLITS = {"block": SPLIT_BLOCK, "interleaved": SPLIT_INTERLEAVED}
 
@@ -75,6 +78,13 @@ class GeneralGrad(C.Structure):
     _fields_ = [("controls", C.c_void_p), ("grad_controls", C.c_void_p), ("dA", C.c_void_p), ("dB", C.c_void_p),
                 ("dC", C.c_void_p), ("dQ", C.c_void_p), ("dR", C.c_void_p), ("dlower", C.c_void_p),
                 ("dupper", C.c_void_p), ("dx0", C.c_void_p), ("dtargets", C.c_void_p), ("kkt_residual", C.c_void_p)]
+
+
+class CompactGrad(C.Structure):
+    """struct tpc_mpc_compact_grad"""
+    _fields_ = [("grad_front", C.c_void_p), ("grad_rear", C.c_void_p), ("grad_sequence", C.c_void_p),
+                ("dv", C.c_void_p), ("ddelta_y", C.c_void_p), ("ddelta_phi", C.c_void_p),
+                ("dparams_rows", C.c_void_p), ("dparams", C.c_void_p), ("kkt_residual", C.c_void_p)]
 
 
 class Polish(C.Structure):
@@ -183,6 +193,8 @@ def load_library(path: str | None = None) -> C.CDLL:
                                            C.POINTER(Polish), C.c_int32, vp, vp, vp, vp, vp, u32p, C.c_int, vp]
     lib.tpc_mpc_solve_batch_compact_exact.argtypes = [vp, C.POINTER(Params), C.c_int64, vp, vp, vp, C.POINTER(Polish),
                                                       C.c_int32, vp, vp, vp, vp, u32p, C.c_int, vp]
+    lib.tpc_mpc_solve_batch_compact_exact_backward.argtypes = [vp, C.POINTER(Params), C.c_int64, vp, vp, vp, vp, vp,
+                                                               C.POINTER(CompactGrad), u32p, C.c_int, vp]
     lib.tpc_mpc_rollout_backward.argtypes = [vp, C.POINTER(Params), C.POINTER(GeneralIO), C.c_int32, vp,
                                              C.POINTER(RolloutGrad), u32p, C.c_int, vp]
     lib.tpc_mpc_solve_batch_general_forward.argtypes = [vp, C.POINTER(Params), C.POINTER(GeneralIO), vp,

@@ -11,6 +11,7 @@
 #include "mpc_polish_model.h"
 #include "mpc_rollout_newton.h"
 #include "mpc_newton_compact.h"
+#include "mpc_compact_grad.h"
 #include "mpc_tangent_model.h"
 
 #include <cmath>
@@ -2063,6 +2064,128 @@ int tpc_mpc_solve_batch_compact_exact(tpc_mpc_handle h, const tpc_mpc_params* p,
             if (q->residual_out) HIP_TRY(h, hipMemcpyAsync(q->residual_out, a.res_out, (size_t)n * 8, hipMemcpyDeviceToHost, s));
             if (q->status) HIP_TRY(h, hipMemcpyAsync(q->status, a.status, (size_t)n * 4, hipMemcpyDeviceToHost, s));
             if (fell_back) HIP_TRY(h, hipMemcpyAsync(fell_back, a.fell_back, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(h, hipStreamSynchronize(s));
+        }
+        rc = order.end();
+        if (rc) return rc;
+        return finish_flags(h, flags_out, s);
+    });
+}
+
+// The backward pass of the exact compact solve: one launch of the adjoint sweep on the model built from v
+// (mpc_compact_grad.hip), and with dparams one more, single-block launch that sums the blocks' partial rows.  The
+// per-step workspace (none at the register kernels' horizons) and the partial rows live in the gradient workspace; HOST
+// arrays are staged row by row, as tpc_mpc_solve_batch_compact_exact stages them.
+int tpc_mpc_solve_batch_compact_exact_backward(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t n, const void* v,
+                                               const void* delta_y, const void* delta_phi, const void* sequence,
+                                               const int32_t* status, const tpc_mpc_compact_grad* g,
+                                               uint32_t* flags_out, int mem, void* stream) {
+    return guarded(h, [&]() -> int {
+        int rc = check_common(h, p, true);
+        if (rc) return rc;
+        if (p->dtype != TPC_MPC_F64)
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "tpc_mpc_solve_batch_compact_exact_backward is fp64 only: p->dtype must be TPC_MPC_F64");
+        rc = check_compact_model(h, p);
+        if (rc) return rc;
+        if (n < 0 || n > 0x7fffffffll) return fail(h, TPC_MPC_ERR_BAD_ARG, "need 0 <= n < 2^31");
+        if (mem != TPC_MPC_HOST && mem != TPC_MPC_DEVICE) return fail(h, TPC_MPC_ERR_BAD_ARG, "bad memory kind");
+        if (!g) return fail(h, TPC_MPC_ERR_BAD_ARG, "null gradient struct");
+        if (h->host_only && mem == TPC_MPC_DEVICE)
+            return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): the backward pass takes HOST memory only");
+        const bool host = mem == TPC_MPC_HOST;
+        constexpr int kP = cgrad::kParams;
+        if (n == 0) {
+            if (g->dparams) {
+                if (host) {
+                    std::memset(g->dparams, 0, kP * 8);
+                } else {
+                    HIP_TRY(h, hipSetDevice(h->device));
+                    HIP_TRY(h, hipMemsetAsync(g->dparams, 0, kP * 8, (hipStream_t)stream));
+                }
+            }
+            if (flags_out) *flags_out = 0;
+            return TPC_MPC_OK;
+        }
+        if (!v || !delta_y || !delta_phi) return fail(h, TPC_MPC_ERR_BAD_ARG, "null batch pointer");
+        if (!sequence) return fail(h, TPC_MPC_ERR_BAD_ARG, "null sequence");
+        const int H = p->horizon;
+
+        cgrad::Args a;
+        std::memset(&a, 0, sizeof(a));
+        a.n = n; a.ld = n;
+        a.T = p->step_size; a.l = p->wheelbase; a.q0 = p->weight_y; a.q1 = p->weight_phi;
+        a.r[0] = p->weight_steering_front; a.r[1] = p->weight_steering_rear;
+        for (int j = 0; j < 2; ++j) { a.lo[j] = p->lower[j]; a.hi[j] = p->upper[j]; }
+        auto bind = [&]() {   // straight from and into the caller's arrays
+            a.v = (const double*)v; a.dy = (const double*)delta_y; a.dphi = (const double*)delta_phi;
+            a.seq = (const double*)sequence; a.status = status;
+            a.gf = (const double*)g->grad_front; a.gr = (const double*)g->grad_rear;
+            a.gs = (const double*)g->grad_sequence;
+            a.dv = (double*)g->dv; a.ddy = (double*)g->ddelta_y; a.ddphi = (double*)g->ddelta_phi;
+            a.rows = (double*)g->dparams_rows; a.kkt = (double*)g->kkt_residual;
+        };
+
+        if (h->host_only) {   // on the calling thread
+            bind();
+            const uint32_t f = compact_grad_host(H, a, (double*)g->dparams);
+            if (flags_out) *flags_out = f;
+            return TPC_MPC_OK;
+        }
+
+        HIP_TRY(h, hipSetDevice(h->device));
+        hipStream_t s = (hipStream_t)stream;
+        StreamOrderScope order(h, s);
+        rc = order.begin();
+        if (rc) return rc;
+        // the gradient workspace: the per-step slots, then the blocks' partial rows
+        const int64_t ws_b = pad256(compact_grad_scratch_bytes(H, n));
+        const int64_t part_b = g->dparams ? pad256(kP * compact_grad_blocks(n) * 8) : 0;
+        rc = ensure(h, &h->grad_ws, &h->grad_ws_bytes, ws_b + part_b);
+        if (rc) return rc;
+        double* partials = g->dparams ? (double*)((char*)h->grad_ws + ws_b) : nullptr;
+        double* d_dparams = (double*)g->dparams;
+
+        // HOST arrays: the rows in order, leading dimension ldw, each present one copied on its own (n elements)
+        const int64_t ldw = (n + 63) / 64 * 64;
+        const void* src[8] = {v, delta_y, delta_phi, sequence, g->grad_front, g->grad_rear, g->grad_sequence, status};
+        void* dst[6] = {g->dv, g->ddelta_y, g->ddelta_phi, g->dparams_rows, g->kkt_residual, g->dparams};
+        const int comps[14] = {1, 1, 1, 2 * H, 1, 1, 2 * H, 1, 1, 1, 1, kP, 1, 1};
+        int64_t off[14] = {0};
+        if (host) {
+            int64_t total = 0;
+            for (int c = 0; c < 14; ++c) {
+                const bool given = c < 8 ? src[c] != nullptr : dst[c - 8] != nullptr;
+                off[c] = total;
+                if (given) total += pad256((int64_t)comps[c] * ldw * 8);
+            }
+            rc = ensure(h, &h->stage, &h->stage_bytes, total);
+            if (rc) return rc;
+            char* b = (char*)h->stage;
+            for (int c = 0; c < 8; ++c) {
+                if (!src[c]) continue;
+                const int64_t es = c == 7 ? 4 : 8;   // status is int32
+                HIP_TRY(h, copy_rows(b + off[c], ldw * es, src[c], n * es, n * es, comps[c], hipMemcpyHostToDevice, s));
+            }
+            auto in = [&](int c) { return src[c] ? (const double*)(b + off[c]) : nullptr; };
+            auto out = [&](int c) { return dst[c] ? (double*)(b + off[8 + c]) : nullptr; };
+            a.ld = ldw;
+            a.v = in(0); a.dy = in(1); a.dphi = in(2); a.seq = in(3); a.gf = in(4); a.gr = in(5); a.gs = in(6);
+            a.status = status ? (const int32_t*)(b + off[7]) : nullptr;
+            a.dv = out(0); a.ddy = out(1); a.ddphi = out(2); a.rows = out(3); a.kkt = out(4);
+            d_dparams = out(5);
+        } else {
+            bind();
+        }
+        HIP_TRY(h, hipMemsetAsync(h->ws_words + 1, 0, sizeof(uint32_t), s));
+        hipError_t e = compact_grad(H, a, h->grad_ws, partials, d_dparams, h->ws_words + 1, s);
+        if (e != hipSuccess) return hip_fail(h, e, "kernel launch");
+        if (host) {
+            const char* b = (const char*)h->stage;
+            for (int c = 0; c < 5; ++c)
+                if (dst[c])
+                    HIP_TRY(h, copy_rows(dst[c], n * 8, b + off[8 + c], ldw * 8, n * 8, comps[8 + c],
+                                         hipMemcpyDeviceToHost, s));
+            if (dst[5]) HIP_TRY(h, hipMemcpyAsync(dst[5], d_dparams, kP * 8, hipMemcpyDeviceToHost, s));
             HIP_TRY(h, hipStreamSynchronize(s));
         }
         rc = order.end();

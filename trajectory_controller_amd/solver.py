@@ -17,6 +17,7 @@ import numpy as np
 from . import capi
 
 _NP = {capi.F64: np.float64, capi.F32: np.float32}
+COMPACT_PARAM_NAMES = capi.COMPACT_PARAM_NAMES   # the order of solve_batch_compact_exact_backward's "params"
 
 
 def _is_torch(x) -> bool:
@@ -223,8 +224,8 @@ class MpcSolver:
         and keeps a DEVICE call asynchronous (fallback="solve" synchronises between its phases anyway and always
         reports the flags).  want_residuals is for checks: the polish's two residual rows.  max_rounds=16: from 8 to
         16 halves the share that falls back, 32 gains little.
-        Not differentiable: mpc_compact takes per-instance weights, T, l and bounds that this entry cannot express;
-        mpc_compact(..., polish=True) stays the differentiable route."""
+        Its derivative is solve_batch_compact_exact_backward (autograd: mpc_compact_exact); mpc_compact takes
+        per-instance weights, T, l and bounds that this entry cannot express, and stays the route for those."""
         p = self._params(**over)
         H = p.horizon
         fb = capi.NEWTON_FALLBACKS[fallback]
@@ -268,6 +269,81 @@ class MpcSolver:
         self.last_flags = flags.value
         out = (front, rear) + ((seq,) if want_sequence else ()) + (status, fell)
         return out + ((rin, rout) if want_residuals else ())
+
+    COMPACT_GRAD_NAMES = ("v", "delta_y", "delta_phi", "params", "params_rows", "kkt_residual")
+
+    def solve_batch_compact_exact_backward(self, v, delta_y, delta_phi, sequence, grad_front=None, grad_rear=None,
+                                           grad_sequence=None, status=None,
+                                           want=("v", "delta_y", "delta_phi", "params"), want_flags: bool = True,
+                                           **over):
+        """Backward pass of solve_batch_compact_exact (tpc_mpc_solve_batch_compact_exact_backward), fp64 only.
+
+        Arrays as in solve_batch_compact_exact (numpy: HOST memory, CUDA tensors: DEVICE memory on the current stream):
+        v, delta_y, delta_phi [n], `sequence` [2H, n] as want_sequence returns it, `status` (int32 [n], optional: an
+        instance with a negative status is excluded).  The incoming gradient is grad_front, grad_rear [n] and
+        grad_sequence [2H, n], each optional (zero).  Returns a dict keyed by `want`: "v", "delta_y", "delta_phi" [n],
+        "params" [10] (the gradient of the shared parameters in the order of COMPACT_PARAM_NAMES, summed over the
+        batch on the device in a fixed order, the same bytes on every call), "params_rows" [10, n] (per instance) and
+        "kkt_residual" [n].  Excluded instances (negative status, non-finite data: last_flags) get zeros and add
+        nothing to "params"; want_flags=False leaves last_flags at 0 and keeps a DEVICE call asynchronous."""
+        p = self._params(**over)
+        H = p.horizon
+        unknown = set(want) - set(self.COMPACT_GRAD_NAMES)
+        if unknown:
+            raise ValueError(f"unknown gradient names {sorted(unknown)}")
+        if _is_torch(v):
+            import torch
+            n = v.numel()
+
+            def ptr(t, rows=None, dtype=torch.float64):
+                if t is None:
+                    return None
+                shape = (n,) if rows is None else (rows, n)
+                if not (t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape):
+                    raise ValueError(f"expected a contiguous {dtype} CUDA tensor {list(shape)}")
+                return t.data_ptr()
+
+            def new(shape):
+                t = torch.empty(shape, dtype=torch.float64, device=v.device)
+                return t, t.data_ptr()
+            i32 = torch.int32
+            stream = C.c_void_p(torch.cuda.current_stream(v.device).cuda_stream)
+            mem = capi.DEVICE
+        else:
+            v = np.ascontiguousarray(v, dtype=np.float64)
+            n = v.shape[0]
+            keep = []
+
+            def ptr(a, rows=None, dtype=np.float64):
+                if a is None:
+                    return None
+                a = np.ascontiguousarray(a, dtype=dtype)
+                if a.shape != ((n,) if rows is None else (rows, n)):
+                    raise ValueError(f"expected an array {[n] if rows is None else [rows, n]}")
+                keep.append(a)
+                return a.ctypes.data
+
+            def new(shape):
+                a = np.empty(shape, dtype=np.float64)
+                return a, a.ctypes.data
+            i32 = np.int32
+            stream = None
+            mem = capi.HOST
+        shapes = {"v": n, "delta_y": n, "delta_phi": n, "params": len(COMPACT_PARAM_NAMES),
+                  "params_rows": (len(COMPACT_PARAM_NAMES), n), "kkt_residual": n}
+        out, optr = {}, {}
+        for k in self.COMPACT_GRAD_NAMES:
+            out[k], optr[k] = new(shapes[k]) if k in want else (None, None)
+        g = capi.CompactGrad(grad_front=ptr(grad_front), grad_rear=ptr(grad_rear),
+                             grad_sequence=ptr(grad_sequence, 2 * H), dv=optr["v"], ddelta_y=optr["delta_y"],
+                             ddelta_phi=optr["delta_phi"], dparams_rows=optr["params_rows"], dparams=optr["params"],
+                             kkt_residual=optr["kkt_residual"])
+        flags = C.c_uint32(0)
+        self._check(self._lib.tpc_mpc_solve_batch_compact_exact_backward(
+            self._h, C.byref(p), n, ptr(v), ptr(delta_y), ptr(delta_phi), ptr(sequence, 2 * H),
+            ptr(status, dtype=i32), C.byref(g), C.byref(flags) if want_flags else None, mem, stream))
+        self.last_flags = flags.value
+        return {k: a for k, a in out.items() if a is not None}
 
     def solve_batch_compact_mixed(self, horizons, v, delta_y, delta_phi, want_iters: bool = False, **over):
         """Mixed-horizon batch (BASELINE config 5): instance k is solved with horizon horizons[k]
