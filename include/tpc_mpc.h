@@ -34,7 +34,7 @@ extern "C" {
 
 #define TPC_MPC_ABI_VERSION 5   /* 5 = 4 + new symbols only (the split-named sharded entries; later additions, such as
                                    tpc_mpc_solve_batch_general_backward, tpc_mpc_rollout_record / _backward / _polished / _newton, tpc_mpc_polish_batch_general
-                                   and tpc_mpc_solve_batch_compact_exact / _exact_backward, are new symbols and structs only and keep 5);
+                                   and tpc_mpc_solve_batch_compact_exact / _exact_backward / _exact_rows / _exact_rows_backward, are new symbols and structs only and keep 5);
                                    4 broke 3: tpc_mpc_params.reserved became .options and must be zero-initialised */
 
 typedef struct tpc_mpc_context* tpc_mpc_handle;
@@ -570,6 +570,48 @@ int tpc_mpc_solve_batch_compact_exact_backward(tpc_mpc_handle h, const tpc_mpc_p
                                                const int32_t* status /* optional [n] */,
                                                const tpc_mpc_compact_grad* g, uint32_t* flags_out, int mem,
                                                void* stream);
+
+/* No reference counterpart.  tpc_mpc_solve_batch_compact_exact and its backward pass with PER-INSTANCE weights,
+ * step_size, wheelbase and bounds: weights scheduled on speed, logs recorded with different wheelbases or cycle times,
+ * per-instance steering limits -- still without the general form being written for the instances that verify.
+ *   params_rows.  Required (NULL: TPC_MPC_ERR_BAD_ARG), SoA fp64 [10] with leading dimension n, in `mem` like every
+ *   other array: element (c, k) at base[c*n + k] is parameter c of instance k, c in the order of tpc_mpc_compact_grad
+ *   (0 weight_y, 1 weight_phi, 2 weight_steering_front, 3 weight_steering_rear, 4 step_size, 5 wheelbase, 6 lower[0],
+ *   7 lower[1], 8 upper[0], 9 upper[1]).  HOST rows are staged with v.
+ *   p gives the horizon, dtype, eps / max_iter / smo_iters / algo / options only; its ten model fields are neither read
+ *   nor validated.
+ *   Forward.  Instance k has the model of tpc_mpc_solve_batch_compact_exact built from v[k] and column k, by the same
+ *   rounded operations (Tv = T_k * v_k, Tv / l_k, its negation).  Phase 1 equals, bit for bit, what
+ *   tpc_mpc_polish_batch_general returns for the per-instance expanded arrays with zero controls; phase 2 gathers and
+ *   expands the unverified instances with their own ten values, and is what tpc_mpc_solve_batch_general and
+ *   tpc_mpc_polish_batch_general return for exactly those.  With every row constant along n, every output equals, bit
+ *   for bit, tpc_mpc_solve_batch_compact_exact called with those ten values in p.
+ *   Invalid instances are decided per instance.  TPC_MPC_FLAG_NONFINITE: a non-finite v, target, weight, step_size or
+ *   wheelbase, a NaN bound, a non-finite Tv or Tv / l (wheelbase == 0 lands here).  TPC_MPC_FLAG_BAD_MODEL: a negative
+ *   weight_y / weight_phi, a steering weight <= 0, upper < lower (a NaN weight or bound fails these comparisons too and
+ *   raises both flags, as it does in the general form).  Infinite bounds are legal.  Forward: (0, 0), a zero
+ *   sequence, status -1, zero residuals, not sent to the fallback, no TPC_MPC_FLAG_NOT_POLISHED of its own.  Backward:
+ *   excluded -- zeros in every per-instance output, nothing added to dparams.
+ *   Backward.  The definition of tpc_mpc_solve_batch_compact_exact_backward, line for line, with T, l and the model
+ *   from column k.  dparams_rows [10], ld n, is the gradient with respect to instance k's OWN ten parameters; dparams
+ *   [10] stays their column sum over the contributing instances, by the same fixed-order reduction -- the gradient of
+ *   a parameter the caller broadcast to every instance.  With constant rows every output equals the shared entry's bits.
+ * Everything else -- the argument checks, n == 0, the optional outputs, asynchronous DEVICE calls with flags_out == NULL,
+ * the host-only handle -- is as the two entries above have it.  Kernels: compact_exact_rows_* (csrc/mpc_newton_compact.hip)
+ * and compact_grad_rows_* (csrc/mpc_compact_grad.hip), one lane per instance, the ten values loaded once per lane. */
+int tpc_mpc_solve_batch_compact_exact_rows(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t n, const void* v,
+                                           const void* delta_y, const void* delta_phi,
+                                           const void* params_rows /* [10], ld n */, const tpc_mpc_polish* q,
+                                           int32_t fallback, void* steering_front, void* steering_rear,
+                                           void* sequence_out, int32_t* fell_back, uint32_t* flags_out, int mem,
+                                           void* stream);
+int tpc_mpc_solve_batch_compact_exact_rows_backward(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t n,
+                                                    const void* v, const void* delta_y, const void* delta_phi,
+                                                    const void* params_rows /* [10], ld n */,
+                                                    const void* sequence /* [H*2], ld n */,
+                                                    const int32_t* status /* optional [n] */,
+                                                    const tpc_mpc_compact_grad* g, uint32_t* flags_out, int mem,
+                                                    void* stream);
 
 /* Inputs and outputs of tpc_mpc_rollout_backward, SoA with the io's leading dimension ld:
  *   sequences[steps*H*I]  the recorded sequences, as tpc_mpc_rollout_record returns them (required)

@@ -1,7 +1,7 @@
 """torch autograd over the batched general-form solve: `mpc_general` and the reference controller's `mpc_compact`,
 and over the closed loop: `mpc_rollout` (forward MpcSolver.rollout_record, or rollout_polished with polish=True;
-backward tpc_mpc_rollout_backward); and `mpc_compact_exact`, the reference controller with shared parameters on the
-exact compact solve and its own backward kernel (no general form on either side).
+backward tpc_mpc_rollout_backward); and `mpc_compact_exact`, the reference controller with shared or per-instance
+parameters on the exact compact solve and its own backward kernel (no general form on either side).
 
 Forward is MpcSolver.solve_batch_general from a fresh controller (zero controls); backward is
 tpc_mpc_solve_batch_general_backward on torch's current stream (include/tpc_mpc.h gives the definition of the
@@ -302,10 +302,66 @@ class _MpcCompactExact(torch.autograd.Function):
         return (None, None, None) + tuple(out)
 
 
+class _MpcCompactExactRows(torch.autograd.Function):
+    """mpc_compact_exact with at least one per-instance parameter: the rows entries on a [10, n] device tensor"""
+
+    @staticmethod
+    def forward(ctx, solver, over, polish, defaults, v, delta_y, delta_phi, weights, step_size, wheelbase, lower,
+                upper):
+        tol, rounds, fallback = polish
+        ins = [t.detach().contiguous() for t in (v, delta_y, delta_phi)]
+        n = ins[0].numel()
+        # the ten rows, filled on the device by broadcasting: a given tensor as it is, the solver's value otherwise
+        rows = torch.empty(10, n, dtype=torch.float64, device=ins[0].device)
+        ctx.per_instance = []
+        for name, t in zip(_MpcCompactExact.PARAMS, (weights, step_size, wheelbase, lower, upper)):
+            sl = _MpcCompactExact.SLICES[name]
+            dst = rows[sl]
+            if t is None:
+                src = torch.tensor(defaults[name], dtype=torch.float64).to(rows.device, non_blocking=True)
+            else:
+                src = t.detach().to(device=rows.device, dtype=torch.float64)
+            per = t is not None and t.dim() == dst.dim()
+            ctx.per_instance.append(per)
+            dst.copy_(src if per else src.unsqueeze(-1))
+        front, rear, sequence, status, _ = solver.solve_batch_compact_exact(
+            *ins, tol=tol, max_rounds=rounds, fallback=fallback, want_sequence=True, params_rows=rows, **over)
+        ctx.solver, ctx.over = solver, over
+        ctx.like = [None if t is None else (t.device, t.dtype, t.shape)
+                    for t in (weights, step_size, wheelbase, lower, upper)]
+        ctx.save_for_backward(*ins, rows, sequence, status)
+        return front, rear
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_front, grad_rear):
+        v, delta_y, delta_phi, rows, sequence, status = ctx.saved_tensors
+        need = ctx.needs_input_grad[4:]
+        want = tuple(k for k, on in zip(("v", "delta_y", "delta_phi"), need[:3]) if on)
+        if any(on and not per for on, per in zip(need[3:], ctx.per_instance)):
+            want += ("params",)
+        if any(on and per for on, per in zip(need[3:], ctx.per_instance)):
+            want += ("params_rows",)
+        if not want:
+            return (None,) * 12
+        g = ctx.solver.solve_batch_compact_exact_backward(
+            v, delta_y, delta_phi, sequence, grad_front=grad_front.contiguous(), grad_rear=grad_rear.contiguous(),
+            status=status, want=want, want_flags=False, params_rows=rows, **ctx.over)
+        out = [g.get("v"), g.get("delta_y"), g.get("delta_phi")]
+        for name, like, on, per in zip(_MpcCompactExact.PARAMS, ctx.like, need[3:], ctx.per_instance):
+            if not on:
+                out.append(None)
+                continue
+            # a per-instance parameter: its own rows; a shared one: the batch sum, as it was broadcast to everyone
+            d = g["params_rows" if per else "params"][_MpcCompactExact.SLICES[name]]
+            out.append(d.to(device=like[0], dtype=like[1]).reshape(like[2]))
+        return (None, None, None, None) + tuple(out)
+
+
 def mpc_compact_exact(solver, v, delta_y, delta_phi, weights=None, step_size=None, wheelbase=None, lower=None,
                       upper=None, tol=1e-9, max_rounds=16, fallback="solve", **over):
-    """mpcControllerTobi for n instances that share ONE set of weights, T, l and bounds, answered with the verified
-    optimum and differentiable: returns (front, rear), each [n].
+    """mpcControllerTobi for n instances, answered with the verified optimum and differentiable: returns
+    (front, rear), each [n].  The weights, T, l and bounds are shared by the batch or given per instance.
 
     The forward is MpcSolver.solve_batch_compact_exact (three doubles in, two out per instance, the sequence and the
     status kept); the backward is one call of tpc_mpc_solve_batch_compact_exact_backward on torch's current stream --
@@ -317,14 +373,42 @@ def mpc_compact_exact(solver, v, delta_y, delta_phi, weights=None, step_size=Non
     delta_y, delta_phi and every given parameter that requires grad (the batch sum, reduced on the device in a fixed
     order, sliced onto the parameter tensors); an instance left unverified (status -1, fallback="none" or a failed
     fallback) or with non-finite data gets zero gradients and adds nothing to the parameters'.  Once-differentiable,
-    no forward mode.  mpc_compact remains the route for per-instance weights, T, l and bounds."""
+    no forward mode.
+
+    Per-instance parameters: any of them may carry a trailing n -- `weights` [4, n], `step_size` [n], `wheelbase` [n],
+    `lower` / `upper` [2, n], CUDA fp64 -- for weights scheduled on speed, logs with different wheelbases or cycle
+    times, per-instance steering limits.  The call then goes through the rows entries
+    (tpc_mpc_solve_batch_compact_exact_rows and its backward): a [10, n] tensor is filled on the device by broadcasting
+    (a shared tensor as it is, None from the solver's parameters; no device-to-host read), a per-instance parameter's
+    gradient is its own rows, a shared one's the batch sum.  An instance whose own column is invalid (a negative
+    weight, upper < lower, a zero wheelbase) returns (0, 0) and gets zero gradients.  With no per-instance parameter
+    the call is exactly the shared one above."""
     for t in (v, delta_y, delta_phi):
         if not (t.is_cuda and t.dtype == torch.float64):
             raise ValueError("mpc_compact_exact takes CUDA fp64 tensors v, delta_y, delta_phi")
+    specs = (("weights", weights, (4,)), ("step_size", step_size, ()), ("wheelbase", wheelbase, ()),
+             ("lower", lower, (2,)), ("upper", upper, (2,)))
+    n = v.numel()
+    # `weights` [4] at n == 4 is the shared shape: only a tensor one dimension longer than the shared shape is rows
+    if any(torch.is_tensor(t) and t.dim() == len(shape) + 1 for _, t, shape in specs):
+        given = []
+        for name, t, shape in specs:
+            if t is not None:
+                t = t if torch.is_tensor(t) else torch.as_tensor(t, dtype=torch.float64)
+                if tuple(t.shape) == shape + (n,):
+                    if not (t.is_cuda and t.dtype == torch.float64):
+                        raise ValueError(f"per-instance {name} must be a CUDA fp64 tensor")
+                elif tuple(t.shape) != shape:
+                    raise ValueError(f"{name} must have shape {list(shape)} or {list(shape + (n,))}")
+            given.append(t)
+        p = solver._params(**over)
+        defaults = {"weights": [p.weight_y, p.weight_phi, p.weight_steering_front, p.weight_steering_rear],
+                    "step_size": p.step_size, "wheelbase": p.wheelbase, "lower": list(p.lower), "upper": list(p.upper)}
+        return _MpcCompactExactRows.apply(solver, dict(over), (float(tol), int(max_rounds), fallback), defaults, v,
+                                          delta_y, delta_phi, *given)
     over = dict(over)
     given = []
-    for name, t, shape in (("weights", weights, (4,)), ("step_size", step_size, ()), ("wheelbase", wheelbase, ()),
-                           ("lower", lower, (2,)), ("upper", upper, (2,))):
+    for name, t, shape in specs:
         if t is None:
             given.append(None)
             continue

@@ -47,13 +47,13 @@ __device__ __forceinline__ void block_partials(double (&row)[kP], double* partia
 }
 
 // partials == null: no reduction, a lane past the batch leaves at once
-template <int HC>
+template <int HC, bool ROWS = false>
 __device__ __forceinline__ void lane_body(const cgrad::Args& a, int H, double* ws, int64_t wn, uint32_t* flags,
                                           double* partials) {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     double row[kP];
     if (k < a.n) {
-        const uint32_t f = cgrad::compact_grad_instance<HC>(a, H, k, ws, wn, row);
+        const uint32_t f = cgrad::compact_grad_instance<HC, ROWS>(a, H, k, ws, wn, row);
         if (f) atomicOr(flags, f);
     } else {
         if (!partials) return;
@@ -73,6 +73,20 @@ template <int HC>
 __global__ __launch_bounds__(256) void compact_grad_reg_kernel(cgrad::Args a, uint32_t* flags, double* partials) {
     double regs[cgrad::kSlots * HC];   // every index into it is a constant once the horizon's loops are unrolled
     lane_body<HC>(a, HC, regs, 1, flags, partials);
+}
+
+// ... and the same two shapes for tpc_mpc_solve_batch_compact_exact_rows_backward: the lane loads its instance's ten
+// model values from a.params, and its row is the gradient with respect to them
+__global__ __launch_bounds__(256) void compact_grad_rows_ws_kernel(cgrad::Args a, int H, double* ws, uint32_t* flags,
+                                                                   double* partials) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    lane_body<0, true>(a, H, ws + (k < a.n ? k : 0), a.n, flags, partials);
+}
+
+template <int HC>
+__global__ __launch_bounds__(256) void compact_grad_rows_reg_kernel(cgrad::Args a, uint32_t* flags, double* partials) {
+    double regs[cgrad::kSlots * HC];
+    lane_body<HC, true>(a, HC, regs, 1, flags, partials);
 }
 
 // one block: dparams[c] = the sum of partials[c * blocks + b] over b, in an order that depends on `blocks` alone
@@ -116,7 +130,11 @@ hipError_t compact_grad(int H, const cgrad::Args& a, void* ws, double* partials,
     const int block = rollout_grad_block(a.n);
     const unsigned grid = (unsigned)compact_grad_blocks(a.n);
     double* part = dparams ? partials : nullptr;
-    if (H == 4) hipLaunchKernelGGL(compact_grad_reg_kernel<4>, dim3(grid), dim3(block), 0, s, a, flags, part);
+    if (a.params) {
+        if (H == 4) hipLaunchKernelGGL(compact_grad_rows_reg_kernel<4>, dim3(grid), dim3(block), 0, s, a, flags, part);
+        else if (H == 5) hipLaunchKernelGGL(compact_grad_rows_reg_kernel<5>, dim3(grid), dim3(block), 0, s, a, flags, part);
+        else hipLaunchKernelGGL(compact_grad_rows_ws_kernel, dim3(grid), dim3(block), 0, s, a, H, (double*)ws, flags, part);
+    } else if (H == 4) hipLaunchKernelGGL(compact_grad_reg_kernel<4>, dim3(grid), dim3(block), 0, s, a, flags, part);
     else if (H == 5) hipLaunchKernelGGL(compact_grad_reg_kernel<5>, dim3(grid), dim3(block), 0, s, a, flags, part);
     else hipLaunchKernelGGL(compact_grad_ws_kernel, dim3(grid), dim3(block), 0, s, a, H, (double*)ws, flags, part);
     hipError_t e = hipGetLastError();
@@ -132,7 +150,8 @@ uint32_t compact_grad_host(int H, const cgrad::Args& a, double* dparams) {
     uint32_t flags = 0;
     for (int64_t k = 0; k < a.n; ++k) {
         double row[kP];
-        flags |= cgrad::compact_grad_instance<0>(a, H, k, ws.data(), 1, row);
+        flags |= a.params ? cgrad::compact_grad_instance<0, true>(a, H, k, ws.data(), 1, row)
+                          : cgrad::compact_grad_instance<0>(a, H, k, ws.data(), 1, row);
         for (int c = 0; c < kP; ++c) sum[c] = sum[c] + row[c];
     }
     if (dparams)

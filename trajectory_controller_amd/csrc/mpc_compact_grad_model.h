@@ -34,6 +34,8 @@ struct Args {
     const int32_t* status;
     const double *gf, *gr, *gs;
     double T, l, q0, q1, r[2], lo[2], hi[2];   // tpc_mpc_params: step_size, wheelbase, weights, bounds
+    const double* params;   // the rows entry: [10] rows ld apart, instance k's own ten values in column k, in the order
+                            // of kParams; the ten fields above are unused
     double *dv, *ddy, *ddphi, *rows, *kkt;
 };
 
@@ -41,7 +43,8 @@ struct Args {
 // first workspace element.  Writes the instance's outputs and leaves its ten shared-parameter gradients in row (zeros
 // for an excluded instance).  Returns its TPC_MPC_FLAG_* bits (0x1 non-finite, 0x4 bad model); a negative status
 // excludes the instance without a flag of its own.
-template <int HC>
+// ROWS: the model, T and l are instance k's own (a.params), and row is the gradient with respect to them.
+template <int HC, bool ROWS = false>
 TPC_GRAD_HD uint32_t compact_grad_instance(const Args& a, int Hrt, int64_t k, double* ws, int64_t wn,
                                            double (&row)[kParams]) {
     constexpr int I = kI;
@@ -49,9 +52,15 @@ TPC_GRAD_HD uint32_t compact_grad_instance(const Args& a, int Hrt, int64_t k, do
     const int64_t ld = a.ld;
     const double v = a.v[k], tg0 = a.dy[k], tg1 = a.dphi[k];
     cexact::Args ma = {};
-    ma.T = a.T; ma.l = a.l; ma.q0 = a.q0; ma.q1 = a.q1;
+    if (ROWS) {
+        ma.params = a.params; ma.ld_params = ld;
+        ma = cexact::instance_params<true>(ma, k);
+    } else {
+        ma.T = a.T; ma.l = a.l; ma.q0 = a.q0; ma.q1 = a.q1;
 #pragma unroll
-    for (int j = 0; j < I; ++j) { ma.r[j] = a.r[j]; ma.lo[j] = a.lo[j]; ma.hi[j] = a.hi[j]; }
+        for (int j = 0; j < I; ++j) { ma.r[j] = a.r[j]; ma.lo[j] = a.lo[j]; ma.hi[j] = a.hi[j]; }
+    }
+    const double T = ma.T, l = ma.l;
     const grad::Model m = cexact::build_model(ma, v);
     const double gf = a.gf ? a.gf[k] : 0.0, gr = a.gr ? a.gr[k] : 0.0;
 
@@ -65,17 +74,17 @@ TPC_GRAD_HD uint32_t compact_grad_instance(const Args& a, int Hrt, int64_t k, do
                          },
                          [&](int, int c) { return c == 0 ? tg0 : tg1; },
                          [&](int, double v0, double v1) { sa = sa + v0; sb = sb + v1; }, ws, wn, s, dx00, dx01) &&
-                     m.fin;
+                     m.fin && (!ROWS || (gfinite(T) && gfinite(l)));   // as cexact::exact_instance decides it
 
     const uint32_t flags = (fin ? 0u : 0x1u) | (m.ok ? 0u : 0x4u);
     const bool zero = flags != 0u || (a.status && a.status[k] < 0);
 
     // the chain rule of build_model
-    const double S = s.A01 + s.B0[1], D = s.B1[0] - s.B1[1], Tv = a.T * v;
-    const double dv = a.T * S + (a.T / a.l) * D;
+    const double S = s.A01 + s.B0[1], D = s.B1[0] - s.B1[1], Tv = T * v;
+    const double dv = T * S + (T / l) * D;
     row[0] = s.Q0; row[1] = s.Q1; row[2] = s.R[0]; row[3] = s.R[1];
-    row[4] = v * S + (v / a.l) * D;
-    row[5] = -((Tv / a.l) / a.l) * D;
+    row[4] = v * S + (v / l) * D;
+    row[5] = -((Tv / l) / l) * D;
     row[6] = s.lo[0]; row[7] = s.lo[1]; row[8] = s.hi[0]; row[9] = s.hi[1];
 #pragma unroll
     for (int c = 0; c < kParams; ++c) row[c] = zero ? 0.0 : row[c];

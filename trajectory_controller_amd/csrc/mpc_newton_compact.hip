@@ -6,6 +6,9 @@
 //   compact_exact_reg_kernel<HC>   the reference's horizons 4 and 5: the horizon at compile time, every loop over it
 //                                  unrolled, the per-step values in an array of the lane's own that the compiler keeps
 //                                  in registers -- no workspace memory is touched
+// compact_exact_rows_ws_kernel and compact_exact_rows_reg_kernel<HC> are the same two for
+// tpc_mpc_solve_batch_compact_exact_rows: each lane loads the ten model values of its own instance (Args::params) where
+// the kernels above read the call's from the kernel arguments.
 // The instances phase 1 could not verify are collected for the fallback (one atomicAdd per wavefront, as
 // mpc_rollout_newton.hip); gather-expand writes their general form into a compact batch for tpc_mpc_solve_batch_general
 // and tpc_mpc_polish_batch_general, scatter brings the results back.  Explicit fma() only (-ffp-contract=off): device and
@@ -50,11 +53,30 @@ __global__ __launch_bounds__(256) void compact_exact_reg_kernel(cexact::Args a, 
     exact_finish(a, k, f, flags);
 }
 
+// ... and the same two shapes for the rows entry: the lane loads its instance's ten model values from a.params
+__global__ __launch_bounds__(256) void compact_exact_rows_ws_kernel(cexact::Args a, int H, double* ws, uint32_t* flags) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= a.n) return;
+    const uint32_t f = cexact::exact_instance<0, true>(a, H, k, ws + k, a.n);
+    exact_finish(a, k, f, flags);
+}
+
+template <int HC>
+__global__ __launch_bounds__(256) void compact_exact_rows_reg_kernel(cexact::Args a, uint32_t* flags) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= a.n) return;
+    double regs[cexact::kSlots * HC];
+    const uint32_t f = cexact::exact_instance<HC, true>(a, HC, k, regs, 1);
+    exact_finish(a, k, f, flags);
+}
+
 __global__ __launch_bounds__(256) void compact_exact_gather_kernel(cexact::Args a, CompactExactBatch b) {
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= b.count) return;
     const int64_t k = b.index[j], ld = b.ld;
-    const grad::Model m = cexact::build_model(a, a.v[k]);
+    // a.params != null (uniform over the launch): the rows entry, the instance's own ten values
+    const grad::Model m = a.params ? cexact::build_model(cexact::instance_params<true>(a, k), a.v[k])
+                                   : cexact::build_model(a, a.v[k]);
     const double tg0 = a.dy[k], tg1 = a.dphi[k];
     auto out = [&](double* base, int c, double x) { base[(int64_t)c * ld + j] = x; };
     out(b.A, 0, m.a00); out(b.A, 1, m.a01); out(b.A, 2, m.a10); out(b.A, 3, m.a11);
@@ -94,6 +116,12 @@ hipError_t compact_exact(int H, const cexact::Args& a, void* ws, uint32_t* flags
     if (a.n <= 0) return hipSuccess;
     const int block = rollout_grad_block(a.n);
     const unsigned grid = (unsigned)((a.n + block - 1) / block);
+    if (a.params) {
+        if (H == 4) hipLaunchKernelGGL(compact_exact_rows_reg_kernel<4>, dim3(grid), dim3(block), 0, s, a, flags);
+        else if (H == 5) hipLaunchKernelGGL(compact_exact_rows_reg_kernel<5>, dim3(grid), dim3(block), 0, s, a, flags);
+        else hipLaunchKernelGGL(compact_exact_rows_ws_kernel, dim3(grid), dim3(block), 0, s, a, H, (double*)ws, flags);
+        return hipGetLastError();
+    }
     if (H == 4) hipLaunchKernelGGL(compact_exact_reg_kernel<4>, dim3(grid), dim3(block), 0, s, a, flags);
     else if (H == 5) hipLaunchKernelGGL(compact_exact_reg_kernel<5>, dim3(grid), dim3(block), 0, s, a, flags);
     else hipLaunchKernelGGL(compact_exact_ws_kernel, dim3(grid), dim3(block), 0, s, a, H, (double*)ws, flags);
@@ -105,7 +133,8 @@ uint32_t compact_exact_host(int H, const cexact::Args& a) {
     std::vector<double> ws((size_t)cexact::kSlots * H);
     uint32_t flags = 0;
     for (int64_t k = 0; k < a.n; ++k) {
-        const uint32_t f = cexact::exact_instance<0>(a, H, k, ws.data(), 1);
+        const uint32_t f = a.params ? cexact::exact_instance<0, true>(a, H, k, ws.data(), 1)
+                                    : cexact::exact_instance<0>(a, H, k, ws.data(), 1);
         flags |= a.raise_not_polished ? f : (f & ~0x8u);
     }
     return flags;

@@ -29,6 +29,8 @@ struct Args {
     int64_t n;
     const double *v, *dy, *dphi;
     double T, l, q0, q1, r[2], lo[2], hi[2];   // tpc_mpc_params: step_size, wheelbase, weights, bounds
+    const double* params;   // the rows entries: [10] rows ld_params apart, the ten values of instance k in column k, in
+    int64_t ld_params;      // cgrad's order (q0 q1 r[0] r[1] T l lo[0] lo[1] hi[0] hi[1]); the ten fields above are unused
     double tol;
     int32_t max_rounds;
     int32_t raise_not_polished;   // FALLBACK_NONE: an unverified instance raises TPC_MPC_FLAG_NOT_POLISHED
@@ -43,6 +45,20 @@ struct Args {
 
 constexpr int kI = 2;
 constexpr int kSlots = polish::slots(kI);   // workspace doubles per step
+
+// The ten model values of instance k.  ROWS: column k of a.params, each loaded once; otherwise the call's own, from the
+// kernel arguments.  The return value is a's ten fields either way, so build_model serves both.
+template <bool ROWS>
+TPC_GRAD_HD Args instance_params(const Args& a, int64_t k) {
+    if (!ROWS) return a;
+    Args b = a;
+    const double* p = a.params + k;
+    const int64_t ld = a.ld_params;
+    b.q0 = p[0]; b.q1 = p[ld]; b.r[0] = p[2 * ld]; b.r[1] = p[3 * ld];
+    b.T = p[4 * ld]; b.l = p[5 * ld];
+    b.lo[0] = p[6 * ld]; b.lo[1] = p[7 * ld]; b.hi[0] = p[8 * ld]; b.hi[1] = p[9 * ld];
+    return b;
+}
 
 // the expanded model of one instance, as mpc_compact (autograd.py) builds it; fin / ok as grad::load_model has them
 TPC_GRAD_HD grad::Model build_model(const Args& a, double v) {
@@ -67,15 +83,18 @@ TPC_GRAD_HD grad::Model build_model(const Args& a, double v) {
 // first workspace element.  Returns its TPC_MPC_FLAG_* bits: 0x1 non-finite, 0x4 bad model (both: nothing run), 0x8
 // not verified; in all three cases the outputs are zeros with status -1 (residual_in keeps round 0's value when rounds
 // were run, as the polish reports it).
-template <int HC>
+template <int HC, bool ROWS = false>
 TPC_GRAD_HD uint32_t exact_instance(const Args& a, int Hrt, int64_t k, double* ws, int64_t wn) {
     constexpr int I = kI;
     const int H = HC > 0 ? HC : Hrt;
     auto slot = [&](int q, int t) -> double& { return ws[((int64_t)q * H + t) * wn]; };
     const double tg0 = a.dy[k], tg1 = a.dphi[k];
-    const grad::Model m = build_model(a, a.v[k]);
+    const Args pa = instance_params<ROWS>(a, k);
+    const grad::Model m = build_model(pa, a.v[k]);
     const double xs0 = 0.0, xs1 = 0.0;
-    const bool fin = m.fin && gfinite(tg0) && gfinite(tg1);
+    // the rows entries decide a non-finite T or l per instance (l = inf leaves Tv / l finite); the call's own are checked
+    // before the launch
+    const bool fin = m.fin && gfinite(tg0) && gfinite(tg1) && (!ROWS || (gfinite(pa.T) && gfinite(pa.l)));
     constexpr int kU = 4 + I, kDf = 2 * I;   // first slot of the working copy / of df
 
     auto finish = [&](int32_t status, double r_in, double r_out) {

@@ -1908,17 +1908,22 @@ int tpc_mpc_rollout_newton(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_
 // and scattered back.  One 4-byte read-back (the fallback's count) sits between the phases; a host-only handle runs
 // phase 1 on the calling thread.  The Newton working set of tpc_mpc_rollout_newton holds the staging rows, the queue and
 // the compact batch.
-int tpc_mpc_solve_batch_compact_exact(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t n, const void* v,
-                                      const void* delta_y, const void* delta_phi, const tpc_mpc_polish* q,
-                                      int32_t fallback, void* steering_front, void* steering_rear, void* sequence_out,
-                                      int32_t* fell_back, uint32_t* flags_out, int mem, void* stream) {
+// `rows`: tpc_mpc_solve_batch_compact_exact_rows -- the ten model values per instance from params_rows ([10], ld n, in
+// `mem` like v), p's own neither read nor checked; HOST rows are staged behind v, dy, dphi.
+static int compact_exact_impl(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t n, const void* v, const void* delta_y,
+                              const void* delta_phi, bool rows, const void* params_rows, const tpc_mpc_polish* q,
+                              int32_t fallback, void* steering_front, void* steering_rear, void* sequence_out,
+                              int32_t* fell_back, uint32_t* flags_out, int mem, void* stream) {
     return guarded(h, [&]() -> int {
         int rc = check_common(h, p, true);
         if (rc) return rc;
         if (p->dtype != TPC_MPC_F64)
-            return fail(h, TPC_MPC_ERR_BAD_ARG, "tpc_mpc_solve_batch_compact_exact is fp64 only: p->dtype must be TPC_MPC_F64");
-        rc = check_compact_model(h, p);
-        if (rc) return rc;
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "%s is fp64 only: p->dtype must be TPC_MPC_F64",
+                        rows ? "tpc_mpc_solve_batch_compact_exact_rows" : "tpc_mpc_solve_batch_compact_exact");
+        if (!rows) {
+            rc = check_compact_model(h, p);
+            if (rc) return rc;
+        }
         if (n < 0 || n > 0x7fffffffll) return fail(h, TPC_MPC_ERR_BAD_ARG, "need 0 <= n < 2^31");
         if (mem != TPC_MPC_HOST && mem != TPC_MPC_DEVICE) return fail(h, TPC_MPC_ERR_BAD_ARG, "bad memory kind");
         if (!q) return fail(h, TPC_MPC_ERR_BAD_ARG, "null polish struct");
@@ -1934,14 +1939,20 @@ int tpc_mpc_solve_batch_compact_exact(tpc_mpc_handle h, const tpc_mpc_params* p,
         if (n == 0) { if (flags_out) *flags_out = 0; return TPC_MPC_OK; }
         if (!v || !delta_y || !delta_phi || !steering_front || !steering_rear)
             return fail(h, TPC_MPC_ERR_BAD_ARG, "null batch pointer");
+        if (rows && !params_rows) return fail(h, TPC_MPC_ERR_BAD_ARG, "null params_rows");
         const int H = p->horizon;
+        constexpr int kP = cgrad::kParams;
 
         cexact::Args a;
         std::memset(&a, 0, sizeof(a));
         a.n = n;
-        a.T = p->step_size; a.l = p->wheelbase; a.q0 = p->weight_y; a.q1 = p->weight_phi;
-        a.r[0] = p->weight_steering_front; a.r[1] = p->weight_steering_rear;
-        for (int j = 0; j < 2; ++j) { a.lo[j] = p->lower[j]; a.hi[j] = p->upper[j]; }
+        if (!rows) {
+            a.T = p->step_size; a.l = p->wheelbase; a.q0 = p->weight_y; a.q1 = p->weight_phi;
+            a.r[0] = p->weight_steering_front; a.r[1] = p->weight_steering_rear;
+            for (int j = 0; j < 2; ++j) { a.lo[j] = p->lower[j]; a.hi[j] = p->upper[j]; }
+        }
+        a.params = rows ? (const double*)params_rows : nullptr;
+        a.ld_params = n;
         a.tol = q->tol; a.max_rounds = q->max_rounds;
         a.raise_not_polished = solve ? 0 : 1;
         a.ld_seq = n;
@@ -1963,10 +1974,11 @@ int tpc_mpc_solve_batch_compact_exact(tpc_mpc_handle h, const tpc_mpc_params* p,
         if (rc) return rc;
         const bool host = mem == TPC_MPC_HOST;
         // the working set: the queue and two words ([0] the fallback's count, [1] phase 1's flags), then for HOST
-        // arrays the staging rows, leading dimension ldw: v dy dphi | front rear seq[2H] res_in res_out | status fell_back
+        // arrays the staging rows, leading dimension ldw: v dy dphi params[10] | front rear seq[2H] res_in res_out |
+        // status fell_back
         const int64_t ldw = (n + 63) / 64 * 64;
         const int64_t o_words = ldw * 4, o_stage = o_words + 256;
-        const int64_t rows8 = 3 + 2 + (sequence_out ? 2 * H : 0) + (q->residual_in ? 1 : 0) + (q->residual_out ? 1 : 0);
+        const int64_t rows8 = 3 + (rows ? kP : 0) + 2 + (sequence_out ? 2 * H : 0) + (q->residual_in ? 1 : 0) + (q->residual_out ? 1 : 0);
         const int64_t o_i32 = o_stage + rows8 * ldw * 8;
         rc = ensure(h, &h->newton, &h->newton_bytes, host ? o_i32 + 2 * ldw * 4 : o_stage);
         if (rc) return rc;
@@ -1995,6 +2007,11 @@ int tpc_mpc_solve_batch_compact_exact(tpc_mpc_handle h, const tpc_mpc_params* p,
             HIP_TRY(h, hipMemcpyAsync(sdy, delta_y, (size_t)n * 8, hipMemcpyHostToDevice, s));
             HIP_TRY(h, hipMemcpyAsync(sdphi, delta_phi, (size_t)n * 8, hipMemcpyHostToDevice, s));
             a.v = sv; a.dy = sdy; a.dphi = sdphi;
+            if (rows) {
+                double* sp = row(true, kP);
+                HIP_TRY(h, copy_rows(sp, ldw * 8, params_rows, n * 8, n * 8, kP, hipMemcpyHostToDevice, s));
+                a.params = sp; a.ld_params = ldw;
+            }
             a.front = row(true, 1); a.rear = row(true, 1);
             a.seq = row(sequence_out != nullptr, 2 * H);
             a.ld_seq = ldw;
@@ -2072,21 +2089,43 @@ int tpc_mpc_solve_batch_compact_exact(tpc_mpc_handle h, const tpc_mpc_params* p,
     });
 }
 
+int tpc_mpc_solve_batch_compact_exact(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t n, const void* v,
+                                      const void* delta_y, const void* delta_phi, const tpc_mpc_polish* q,
+                                      int32_t fallback, void* steering_front, void* steering_rear, void* sequence_out,
+                                      int32_t* fell_back, uint32_t* flags_out, int mem, void* stream) {
+    return compact_exact_impl(h, p, n, v, delta_y, delta_phi, false, nullptr, q, fallback, steering_front, steering_rear,
+                              sequence_out, fell_back, flags_out, mem, stream);
+}
+
+int tpc_mpc_solve_batch_compact_exact_rows(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t n, const void* v,
+                                           const void* delta_y, const void* delta_phi, const void* params_rows,
+                                           const tpc_mpc_polish* q, int32_t fallback, void* steering_front,
+                                           void* steering_rear, void* sequence_out, int32_t* fell_back,
+                                           uint32_t* flags_out, int mem, void* stream) {
+    return compact_exact_impl(h, p, n, v, delta_y, delta_phi, true, params_rows, q, fallback, steering_front,
+                              steering_rear, sequence_out, fell_back, flags_out, mem, stream);
+}
+
 // The backward pass of the exact compact solve: one launch of the adjoint sweep on the model built from v
 // (mpc_compact_grad.hip), and with dparams one more, single-block launch that sums the blocks' partial rows.  The
 // per-step workspace (none at the register kernels' horizons) and the partial rows live in the gradient workspace; HOST
 // arrays are staged row by row, as tpc_mpc_solve_batch_compact_exact stages them.
-int tpc_mpc_solve_batch_compact_exact_backward(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t n, const void* v,
-                                               const void* delta_y, const void* delta_phi, const void* sequence,
-                                               const int32_t* status, const tpc_mpc_compact_grad* g,
-                                               uint32_t* flags_out, int mem, void* stream) {
+// `rows`: tpc_mpc_solve_batch_compact_exact_rows_backward, as compact_exact_impl takes params_rows.
+static int compact_exact_backward_impl(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t n, const void* v,
+                                       const void* delta_y, const void* delta_phi, bool rows, const void* params_rows,
+                                       const void* sequence, const int32_t* status, const tpc_mpc_compact_grad* g,
+                                       uint32_t* flags_out, int mem, void* stream) {
     return guarded(h, [&]() -> int {
         int rc = check_common(h, p, true);
         if (rc) return rc;
         if (p->dtype != TPC_MPC_F64)
-            return fail(h, TPC_MPC_ERR_BAD_ARG, "tpc_mpc_solve_batch_compact_exact_backward is fp64 only: p->dtype must be TPC_MPC_F64");
-        rc = check_compact_model(h, p);
-        if (rc) return rc;
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "%s is fp64 only: p->dtype must be TPC_MPC_F64",
+                        rows ? "tpc_mpc_solve_batch_compact_exact_rows_backward"
+                             : "tpc_mpc_solve_batch_compact_exact_backward");
+        if (!rows) {
+            rc = check_compact_model(h, p);
+            if (rc) return rc;
+        }
         if (n < 0 || n > 0x7fffffffll) return fail(h, TPC_MPC_ERR_BAD_ARG, "need 0 <= n < 2^31");
         if (mem != TPC_MPC_HOST && mem != TPC_MPC_DEVICE) return fail(h, TPC_MPC_ERR_BAD_ARG, "bad memory kind");
         if (!g) return fail(h, TPC_MPC_ERR_BAD_ARG, "null gradient struct");
@@ -2108,15 +2147,19 @@ int tpc_mpc_solve_batch_compact_exact_backward(tpc_mpc_handle h, const tpc_mpc_p
         }
         if (!v || !delta_y || !delta_phi) return fail(h, TPC_MPC_ERR_BAD_ARG, "null batch pointer");
         if (!sequence) return fail(h, TPC_MPC_ERR_BAD_ARG, "null sequence");
+        if (rows && !params_rows) return fail(h, TPC_MPC_ERR_BAD_ARG, "null params_rows");
         const int H = p->horizon;
 
         cgrad::Args a;
         std::memset(&a, 0, sizeof(a));
         a.n = n; a.ld = n;
-        a.T = p->step_size; a.l = p->wheelbase; a.q0 = p->weight_y; a.q1 = p->weight_phi;
-        a.r[0] = p->weight_steering_front; a.r[1] = p->weight_steering_rear;
-        for (int j = 0; j < 2; ++j) { a.lo[j] = p->lower[j]; a.hi[j] = p->upper[j]; }
+        if (!rows) {
+            a.T = p->step_size; a.l = p->wheelbase; a.q0 = p->weight_y; a.q1 = p->weight_phi;
+            a.r[0] = p->weight_steering_front; a.r[1] = p->weight_steering_rear;
+            for (int j = 0; j < 2; ++j) { a.lo[j] = p->lower[j]; a.hi[j] = p->upper[j]; }
+        }
         auto bind = [&]() {   // straight from and into the caller's arrays
+            a.params = rows ? (const double*)params_rows : nullptr;
             a.v = (const double*)v; a.dy = (const double*)delta_y; a.dphi = (const double*)delta_phi;
             a.seq = (const double*)sequence; a.status = status;
             a.gf = (const double*)g->grad_front; a.gr = (const double*)g->grad_rear;
@@ -2152,7 +2195,7 @@ int tpc_mpc_solve_batch_compact_exact_backward(tpc_mpc_handle h, const tpc_mpc_p
         const int comps[14] = {1, 1, 1, 2 * H, 1, 1, 2 * H, 1, 1, 1, 1, kP, 1, 1};
         int64_t off[14] = {0};
         if (host) {
-            int64_t total = 0;
+            int64_t total = rows ? pad256((int64_t)kP * ldw * 8) : 0;   // params_rows first, when there are any
             for (int c = 0; c < 14; ++c) {
                 const bool given = c < 8 ? src[c] != nullptr : dst[c - 8] != nullptr;
                 off[c] = total;
@@ -2161,6 +2204,10 @@ int tpc_mpc_solve_batch_compact_exact_backward(tpc_mpc_handle h, const tpc_mpc_p
             rc = ensure(h, &h->stage, &h->stage_bytes, total);
             if (rc) return rc;
             char* b = (char*)h->stage;
+            if (rows) {
+                HIP_TRY(h, copy_rows(b, ldw * 8, params_rows, n * 8, n * 8, kP, hipMemcpyHostToDevice, s));
+                a.params = (const double*)b;
+            }
             for (int c = 0; c < 8; ++c) {
                 if (!src[c]) continue;
                 const int64_t es = c == 7 ? 4 : 8;   // status is int32
@@ -2192,6 +2239,23 @@ int tpc_mpc_solve_batch_compact_exact_backward(tpc_mpc_handle h, const tpc_mpc_p
         if (rc) return rc;
         return finish_flags(h, flags_out, s);
     });
+}
+
+int tpc_mpc_solve_batch_compact_exact_backward(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t n, const void* v,
+                                               const void* delta_y, const void* delta_phi, const void* sequence,
+                                               const int32_t* status, const tpc_mpc_compact_grad* g,
+                                               uint32_t* flags_out, int mem, void* stream) {
+    return compact_exact_backward_impl(h, p, n, v, delta_y, delta_phi, false, nullptr, sequence, status, g, flags_out,
+                                       mem, stream);
+}
+
+int tpc_mpc_solve_batch_compact_exact_rows_backward(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t n,
+                                                    const void* v, const void* delta_y, const void* delta_phi,
+                                                    const void* params_rows, const void* sequence,
+                                                    const int32_t* status, const tpc_mpc_compact_grad* g,
+                                                    uint32_t* flags_out, int mem, void* stream) {
+    return compact_exact_backward_impl(h, p, n, v, delta_y, delta_phi, true, params_rows, sequence, status, g,
+                                       flags_out, mem, stream);
 }
 
 // what the three plant entries check of a tpc_mpc_plant (after check_common and check_general_io)

@@ -208,7 +208,7 @@ class MpcSolver:
 
     def solve_batch_compact_exact(self, v, delta_y, delta_phi, tol: float = 1e-9, max_rounds: int = 16,
                                   fallback: str = "solve", want_status: bool = True, want_sequence: bool = False,
-                                  want_residuals: bool = False, **over):
+                                  want_residuals: bool = False, params_rows=None, **over):
         """n independent mpcControllerTobi calls answered with the verified optimum instead of dlib's eps-0.01 point
         (tpc_mpc_solve_batch_compact_exact), fp64 only.
 
@@ -224,17 +224,26 @@ class MpcSolver:
         and keeps a DEVICE call asynchronous (fallback="solve" synchronises between its phases anyway and always
         reports the flags).  want_residuals is for checks: the polish's two residual rows.  max_rounds=16: from 8 to
         16 halves the share that falls back, 32 gains little.
-        Its derivative is solve_batch_compact_exact_backward (autograd: mpc_compact_exact); mpc_compact takes
-        per-instance weights, T, l and bounds that this entry cannot express, and stays the route for those."""
+        params_rows ([10, n] fp64, numpy or a contiguous CUDA tensor like v; rows in the order of
+        COMPACT_PARAM_NAMES) gives every instance its own weights, step_size, wheelbase and bounds
+        (tpc_mpc_solve_batch_compact_exact_rows): the solver's ten model values are then not read, an instance with an
+        invalid column returns (0, 0) with status -1 and raises FLAG_NONFINITE or FLAG_BAD_MODEL, and the fallback
+        expands the unverified instances with their own values.  None is the shared entry.
+        Its derivative is solve_batch_compact_exact_backward (autograd: mpc_compact_exact)."""
         p = self._params(**over)
         H = p.horizon
         fb = capi.NEWTON_FALLBACKS[fallback]
+        rows_shape = (len(COMPACT_PARAM_NAMES), v.numel() if _is_torch(v) else np.shape(v)[0])
         if _is_torch(v):
             import torch
             n = v.numel()
             for t in (v, delta_y, delta_phi):
                 if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == n):
                     raise ValueError("device batch arrays must be contiguous fp64 CUDA tensors")
+            if params_rows is not None and not (
+                    _is_torch(params_rows) and params_rows.is_cuda and params_rows.dtype == torch.float64
+                    and params_rows.is_contiguous() and tuple(params_rows.shape) == rows_shape):
+                raise ValueError(f"params_rows must be a contiguous fp64 CUDA tensor {list(rows_shape)}")
 
             def new(dtype, rows=None):
                 t = torch.empty(n if rows is None else (rows, n),
@@ -246,6 +255,10 @@ class MpcSolver:
         else:
             v, delta_y, delta_phi = (np.ascontiguousarray(a, dtype=np.float64) for a in (v, delta_y, delta_phi))
             n = v.shape[0]
+            if params_rows is not None:
+                params_rows = np.ascontiguousarray(params_rows, dtype=np.float64)
+                if params_rows.shape != rows_shape:
+                    raise ValueError(f"params_rows must be an array {list(rows_shape)}")
 
             def new(dtype, rows=None):
                 a = np.empty(n if rows is None else (rows, n), dtype=dtype)
@@ -263,9 +276,15 @@ class MpcSolver:
         q = capi.Polish(tol=float(tol), max_rounds=int(max_rounds), reserved=0, status=sp, residual_in=rip,
                         residual_out=rop)
         flags = C.c_uint32(0)
-        self._check(self._lib.tpc_mpc_solve_batch_compact_exact(
-            self._h, C.byref(p), n, ptr(v), ptr(delta_y), ptr(delta_phi), C.byref(q), fb, fp, rp, sqp, fbp,
-            C.byref(flags) if want_status or fallback != "none" else None, mem, stream))
+        fp_flags = C.byref(flags) if want_status or fallback != "none" else None
+        if params_rows is None:
+            self._check(self._lib.tpc_mpc_solve_batch_compact_exact(
+                self._h, C.byref(p), n, ptr(v), ptr(delta_y), ptr(delta_phi), C.byref(q), fb, fp, rp, sqp, fbp,
+                fp_flags, mem, stream))
+        else:
+            self._check(self._lib.tpc_mpc_solve_batch_compact_exact_rows(
+                self._h, C.byref(p), n, ptr(v), ptr(delta_y), ptr(delta_phi), ptr(params_rows), C.byref(q), fb, fp,
+                rp, sqp, fbp, fp_flags, mem, stream))
         self.last_flags = flags.value
         out = (front, rear) + ((seq,) if want_sequence else ()) + (status, fell)
         return out + ((rin, rout) if want_residuals else ())
@@ -275,7 +294,7 @@ class MpcSolver:
     def solve_batch_compact_exact_backward(self, v, delta_y, delta_phi, sequence, grad_front=None, grad_rear=None,
                                            grad_sequence=None, status=None,
                                            want=("v", "delta_y", "delta_phi", "params"), want_flags: bool = True,
-                                           **over):
+                                           params_rows=None, **over):
         """Backward pass of solve_batch_compact_exact (tpc_mpc_solve_batch_compact_exact_backward), fp64 only.
 
         Arrays as in solve_batch_compact_exact (numpy: HOST memory, CUDA tensors: DEVICE memory on the current stream):
@@ -285,7 +304,9 @@ class MpcSolver:
         "params" [10] (the gradient of the shared parameters in the order of COMPACT_PARAM_NAMES, summed over the
         batch on the device in a fixed order, the same bytes on every call), "params_rows" [10, n] (per instance) and
         "kkt_residual" [n].  Excluded instances (negative status, non-finite data: last_flags) get zeros and add
-        nothing to "params"; want_flags=False leaves last_flags at 0 and keeps a DEVICE call asynchronous."""
+        nothing to "params"; want_flags=False leaves last_flags at 0 and keeps a DEVICE call asynchronous.
+        With params_rows ([10, n], as solve_batch_compact_exact takes it: tpc_mpc_solve_batch_compact_exact_rows_backward)
+        "params_rows" is the gradient with respect to each instance's own ten parameters and "params" their sum."""
         p = self._params(**over)
         H = p.horizon
         unknown = set(want) - set(self.COMPACT_GRAD_NAMES)
@@ -339,9 +360,15 @@ class MpcSolver:
                              ddelta_phi=optr["delta_phi"], dparams_rows=optr["params_rows"], dparams=optr["params"],
                              kkt_residual=optr["kkt_residual"])
         flags = C.c_uint32(0)
-        self._check(self._lib.tpc_mpc_solve_batch_compact_exact_backward(
-            self._h, C.byref(p), n, ptr(v), ptr(delta_y), ptr(delta_phi), ptr(sequence, 2 * H),
-            ptr(status, dtype=i32), C.byref(g), C.byref(flags) if want_flags else None, mem, stream))
+        if params_rows is None:
+            self._check(self._lib.tpc_mpc_solve_batch_compact_exact_backward(
+                self._h, C.byref(p), n, ptr(v), ptr(delta_y), ptr(delta_phi), ptr(sequence, 2 * H),
+                ptr(status, dtype=i32), C.byref(g), C.byref(flags) if want_flags else None, mem, stream))
+        else:
+            self._check(self._lib.tpc_mpc_solve_batch_compact_exact_rows_backward(
+                self._h, C.byref(p), n, ptr(v), ptr(delta_y), ptr(delta_phi),
+                ptr(params_rows, len(COMPACT_PARAM_NAMES)), ptr(sequence, 2 * H), ptr(status, dtype=i32), C.byref(g),
+                C.byref(flags) if want_flags else None, mem, stream))
         self.last_flags = flags.value
         return {k: a for k, a in out.items() if a is not None}
 
