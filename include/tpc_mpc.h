@@ -34,7 +34,7 @@ extern "C" {
 
 #define TPC_MPC_ABI_VERSION 5   /* 5 = 4 + new symbols only (the split-named sharded entries; later additions, such as
                                    tpc_mpc_solve_batch_general_backward, tpc_mpc_rollout_record / _backward / _polished / _newton, tpc_mpc_polish_batch_general
-                                   and tpc_mpc_solve_batch_compact_exact / _exact_backward / _exact_rows / _exact_rows_backward, are new symbols and structs only and keep 5);
+                                   and tpc_mpc_solve_batch_compact_exact / _exact_backward / _exact_rows / _exact_rows_backward / _exact_from, are new symbols and structs only and keep 5);
                                    4 broke 3: tpc_mpc_params.reserved became .options and must be zero-initialised */
 
 typedef struct tpc_mpc_context* tpc_mpc_handle;
@@ -612,6 +612,40 @@ int tpc_mpc_solve_batch_compact_exact_rows_backward(tpc_mpc_handle h, const tpc_
                                                     const int32_t* status /* optional [n] */,
                                                     const tpc_mpc_compact_grad* g, uint32_t* flags_out, int mem,
                                                     void* stream);
+
+/* No reference counterpart.  tpc_mpc_solve_batch_compact_exact / _exact_rows WARM-STARTED: the Newton rounds of phase 1
+ * begin at a sequence the caller gives per instance -- in a fitting loop, the instance's own optimum from the previous
+ * optimiser step (the sequence_out of that call) -- not at U = 0.  Near the optimum one round verifies where the cold
+ * start needs two or three, and most of the instances the cold start sends to the fallback verify in phase 1.
+ *   params_rows.  Optional, [10] with leading dimension n as tpc_mpc_solve_batch_compact_exact_rows takes it.  NULL: p's
+ *   ten values, and every rule below is tpc_mpc_solve_batch_compact_exact's; given: the rows entry's (p's ten model
+ *   fields neither read nor validated, invalid columns decided per instance).
+ *   start.  Required (NULL: TPC_MPC_ERR_BAD_ARG), SoA fp64 [H*2] with leading dimension n, in `mem` like every other
+ *   array: element (t*2+j, k) at base[(t*2+j)*n + k], the layout of sequence_out.  HOST rows are staged with v.
+ *   Phase 1.  Instance k runs the parents' rounds with ONE change: the working copy begins at
+ *   clamp(start[(t*2+j)*n + k], lower[j], upper[j]) where the parents begin at clamp(0.0, lower[j], upper[j]).  For an
+ *   instance whose start is finite in every component, steering_front / steering_rear, sequence_out, status and both
+ *   residuals equal, bit for bit, what tpc_mpc_polish_batch_general returns for the (per-instance) expanded arrays with
+ *   controls = start; residual_in is the residual at the clamped start.
+ *   No start.  An instance with a NaN or an Inf in ANY component of its start column is that instance of the cold
+ *   entry, bit for bit: it starts from clamp(0.0, ..) in every component and raises no flag.  This is how a caller
+ *   says "I have no start for this one"; a column of zeros gives the same result.
+ *   Phase 2, the flags, invalid instances (their start is not read), the optional outputs, n == 0, the argument errors,
+ *   asynchronous DEVICE calls with flags_out == NULL and the host-only handle are the parents'.  The fallback solves
+ *   cold, as the parents' does: an instance that falls back returns what tpc_mpc_solve_batch_general and
+ *   tpc_mpc_polish_batch_general return for it, whatever its start was.  Under TPC_MPC_NEWTON_FALLBACK_NONE an
+ *   unverified instance returns (0, 0), a zero sequence and status -1, so the next call finds a column of zeros there.
+ *   Aliasing.  sequence_out == start is allowed (update the stored sequences in place): a lane reads its whole column
+ *   before its first write.  No other overlap of an input with an output is.
+ * Kernels: compact_exact_warm_* (csrc/mpc_newton_compact.hip), launched as the parents' -- one lane per instance, the
+ * start loaded once; at horizons 4 and 5 the per-step values stay in registers. */
+int tpc_mpc_solve_batch_compact_exact_from(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t n, const void* v,
+                                           const void* delta_y, const void* delta_phi,
+                                           const void* params_rows /* optional [10], ld n */,
+                                           const void* start /* [H*2], ld n */, const tpc_mpc_polish* q,
+                                           int32_t fallback, void* steering_front, void* steering_rear,
+                                           void* sequence_out, int32_t* fell_back, uint32_t* flags_out, int mem,
+                                           void* stream);
 
 /* Inputs and outputs of tpc_mpc_rollout_backward, SoA with the io's leading dimension ld:
  *   sequences[steps*H*I]  the recorded sequences, as tpc_mpc_rollout_record returns them (required)

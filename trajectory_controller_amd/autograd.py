@@ -262,16 +262,46 @@ def mpc_compact(solver, v, delta_y, delta_phi, weights, step_size=0.1, wheelbase
     return u[0], u[1]
 
 
+class CompactWarmStart:
+    """What mpc_compact_exact(..., warm=) carries from one call to the next: the sequence the last forward returned
+    ([2H, n], detached), which the next forward hands to the Newton rounds as their start
+    (tpc_mpc_solve_batch_compact_exact_from).  One holder per logged batch: the columns are the instances' own optima of
+    the previous optimiser step.  The first call, or a call whose n, H or device differs from the stored sequence's,
+    is a cold call.  reset() forgets the sequence."""
+
+    def __init__(self):
+        self.sequence = None
+
+    def reset(self):
+        self.sequence = None
+
+    def start_for(self, H, like):
+        s = self.sequence
+        if s is None or tuple(s.shape) != (2 * H, like.numel()) or s.device != like.device:
+            return None
+        return s
+
+
+def _warm_forward(solver, warm, ins, over, **kw):
+    """solve_batch_compact_exact from the holder's sequence (warm None: the cold call), which then takes the returned
+    one -- a new tensor every call, so the sequence an earlier forward saved for its backward is never written"""
+    start = None if warm is None else warm.start_for(solver._params(**over).horizon, ins[0])
+    out = solver.solve_batch_compact_exact(*ins, want_sequence=True, start=start, **kw, **over)
+    if warm is not None:
+        warm.sequence = out[2].detach()
+    return out
+
+
 class _MpcCompactExact(torch.autograd.Function):
-    PARAMS = ("weights", "step_size", "wheelbase", "lower", "upper")
+    PARAMS =("weights", "step_size", "wheelbase", "lower", "upper")
     SLICES = {"weights": slice(0, 4), "step_size": 4, "wheelbase": 5, "lower": slice(6, 8), "upper": slice(8, 10)}
 
     @staticmethod
     def forward(ctx, solver, over, polish, v, delta_y, delta_phi, weights, step_size, wheelbase, lower, upper):
-        tol, rounds, fallback = polish
+        tol, rounds, fallback, warm = polish
         ins = [t.detach().contiguous() for t in (v, delta_y, delta_phi)]
-        front, rear, sequence, status, _ = solver.solve_batch_compact_exact(
-            *ins, tol=tol, max_rounds=rounds, fallback=fallback, want_sequence=True, **over)
+        front, rear, sequence, status, _ = _warm_forward(solver, warm, ins, over, tol=tol, max_rounds=rounds,
+                                                         fallback=fallback)
         ctx.solver, ctx.over = solver, over
         # where each given parameter's gradient goes
         ctx.like = [None if t is None else (t.device, t.dtype, t.shape)
@@ -308,7 +338,7 @@ class _MpcCompactExactRows(torch.autograd.Function):
     @staticmethod
     def forward(ctx, solver, over, polish, defaults, v, delta_y, delta_phi, weights, step_size, wheelbase, lower,
                 upper):
-        tol, rounds, fallback = polish
+        tol, rounds, fallback, warm = polish
         ins = [t.detach().contiguous() for t in (v, delta_y, delta_phi)]
         n = ins[0].numel()
         # the ten rows, filled on the device by broadcasting: a given tensor as it is, the solver's value otherwise
@@ -324,8 +354,8 @@ class _MpcCompactExactRows(torch.autograd.Function):
             per = t is not None and t.dim() == dst.dim()
             ctx.per_instance.append(per)
             dst.copy_(src if per else src.unsqueeze(-1))
-        front, rear, sequence, status, _ = solver.solve_batch_compact_exact(
-            *ins, tol=tol, max_rounds=rounds, fallback=fallback, want_sequence=True, params_rows=rows, **over)
+        front, rear, sequence, status, _ = _warm_forward(solver, warm, ins, over, tol=tol, max_rounds=rounds,
+                                                         fallback=fallback, params_rows=rows)
         ctx.solver, ctx.over = solver, over
         ctx.like = [None if t is None else (t.device, t.dtype, t.shape)
                     for t in (weights, step_size, wheelbase, lower, upper)]
@@ -359,7 +389,7 @@ class _MpcCompactExactRows(torch.autograd.Function):
 
 
 def mpc_compact_exact(solver, v, delta_y, delta_phi, weights=None, step_size=None, wheelbase=None, lower=None,
-                      upper=None, tol=1e-9, max_rounds=16, fallback="solve", **over):
+                      upper=None, tol=1e-9, max_rounds=16, fallback="solve", warm=None, **over):
     """mpcControllerTobi for n instances, answered with the verified optimum and differentiable: returns
     (front, rear), each [n].  The weights, T, l and bounds are shared by the batch or given per instance.
 
@@ -382,7 +412,15 @@ def mpc_compact_exact(solver, v, delta_y, delta_phi, weights=None, step_size=Non
     (a shared tensor as it is, None from the solver's parameters; no device-to-host read), a per-instance parameter's
     gradient is its own rows, a shared one's the batch sum.  An instance whose own column is invalid (a negative
     weight, upper < lower, a zero wheelbase) returns (0, 0) and gets zero gradients.  With no per-instance parameter
-    the call is exactly the shared one above."""
+    the call is exactly the shared one above.
+
+    warm: a CompactWarmStart, kept by the caller across the steps of a fitting loop over the same batch.  The forward
+    hands the holder's sequence -- the previous call's optimum, detached -- to the Newton rounds as their start
+    (tpc_mpc_solve_batch_compact_exact_from) and then stores the sequence it returns; the first call, or a changed n or
+    horizon, is a cold call.  The backward is unchanged: it differentiates at the returned sequence, which is the same
+    optimum to rounding.  Shared and per-instance parameters alike.  None is the call above."""
+    if warm is not None and not isinstance(warm, CompactWarmStart):
+        raise ValueError("warm must be a CompactWarmStart")
     for t in (v, delta_y, delta_phi):
         if not (t.is_cuda and t.dtype == torch.float64):
             raise ValueError("mpc_compact_exact takes CUDA fp64 tensors v, delta_y, delta_phi")
@@ -404,7 +442,7 @@ def mpc_compact_exact(solver, v, delta_y, delta_phi, weights=None, step_size=Non
         p = solver._params(**over)
         defaults = {"weights": [p.weight_y, p.weight_phi, p.weight_steering_front, p.weight_steering_rear],
                     "step_size": p.step_size, "wheelbase": p.wheelbase, "lower": list(p.lower), "upper": list(p.upper)}
-        return _MpcCompactExactRows.apply(solver, dict(over), (float(tol), int(max_rounds), fallback), defaults, v,
+        return _MpcCompactExactRows.apply(solver, dict(over), (float(tol), int(max_rounds), fallback, warm), defaults, v,
                                           delta_y, delta_phi, *given)
     over = dict(over)
     given = []
@@ -422,5 +460,5 @@ def mpc_compact_exact(solver, v, delta_y, delta_phi, weights=None, step_size=Non
         else:
             over[name] = tuple(val) if shape else val
         given.append(t)
-    return _MpcCompactExact.apply(solver, over, (float(tol), int(max_rounds), fallback), v, delta_y, delta_phi,
+    return _MpcCompactExact.apply(solver, over, (float(tol), int(max_rounds), fallback, warm), v, delta_y, delta_phi,
                                   *given)

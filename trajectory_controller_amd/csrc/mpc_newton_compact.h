@@ -21,7 +21,8 @@ struct CompactExactBatch {
 
 // true: a kernel with the horizon at compile time and the per-step values in registers serves H
 bool compact_exact_in_registers(int H);
-// phase 1 on DEVICE arrays; ws holds polish_scratch_bytes(2, H, n) (not touched when compact_exact_in_registers(H))
+// phase 1 on DEVICE arrays; ws holds polish_scratch_bytes(2, H, n) (not touched when compact_exact_in_registers(H));
+// a.start != null: the warm kernels (tpc_mpc_solve_batch_compact_exact_from), here and in compact_exact_host
 hipError_t compact_exact(int H, const cexact::Args& a, void* ws, uint32_t* flags, hipStream_t s);
 // ... and on the calling thread; returns the OR of the flags
 uint32_t compact_exact_host(int H, const cexact::Args& a);

@@ -9,6 +9,8 @@
 // compact_exact_rows_ws_kernel and compact_exact_rows_reg_kernel<HC> are the same two for
 // tpc_mpc_solve_batch_compact_exact_rows: each lane loads the ten model values of its own instance (Args::params) where
 // the kernels above read the call's from the kernel arguments.
+// compact_exact_warm_* are the same four for tpc_mpc_solve_batch_compact_exact_from: the lane starts from its column of
+// Args::start (one pass: load, clamp, track finiteness; a non-finite column is rewritten with the cold start).
 // The instances phase 1 could not verify are collected for the fallback (one atomicAdd per wavefront, as
 // mpc_rollout_newton.hip); gather-expand writes their general form into a compact batch for tpc_mpc_solve_batch_general
 // and tpc_mpc_polish_batch_general, scatter brings the results back.  Explicit fma() only (-ffp-contract=off): device and
@@ -70,6 +72,41 @@ __global__ __launch_bounds__(256) void compact_exact_rows_reg_kernel(cexact::Arg
     exact_finish(a, k, f, flags);
 }
 
+// tpc_mpc_solve_batch_compact_exact_from: the four shapes above with the working copy started from column k of a.start
+// (exact_instance's WARM) -- kernels of their own, so that the parents' code objects stay as they are
+__global__ __launch_bounds__(256) void compact_exact_warm_ws_kernel(cexact::Args a, int H, double* ws, uint32_t* flags) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= a.n) return;
+    const uint32_t f = cexact::exact_instance<0, false, true>(a, H, k, ws + k, a.n);
+    exact_finish(a, k, f, flags);
+}
+
+template <int HC>
+__global__ __launch_bounds__(256) void compact_exact_warm_reg_kernel(cexact::Args a, uint32_t* flags) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= a.n) return;
+    double regs[cexact::kSlots * HC];
+    const uint32_t f = cexact::exact_instance<HC, false, true>(a, HC, k, regs, 1);
+    exact_finish(a, k, f, flags);
+}
+
+__global__ __launch_bounds__(256) void compact_exact_warm_rows_ws_kernel(cexact::Args a, int H, double* ws,
+                                                                         uint32_t* flags) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= a.n) return;
+    const uint32_t f = cexact::exact_instance<0, true, true>(a, H, k, ws + k, a.n);
+    exact_finish(a, k, f, flags);
+}
+
+template <int HC>
+__global__ __launch_bounds__(256) void compact_exact_warm_rows_reg_kernel(cexact::Args a, uint32_t* flags) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= a.n) return;
+    double regs[cexact::kSlots * HC];
+    const uint32_t f = cexact::exact_instance<HC, true, true>(a, HC, k, regs, 1);
+    exact_finish(a, k, f, flags);
+}
+
 __global__ __launch_bounds__(256) void compact_exact_gather_kernel(cexact::Args a, CompactExactBatch b) {
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= b.count) return;
@@ -116,6 +153,18 @@ hipError_t compact_exact(int H, const cexact::Args& a, void* ws, uint32_t* flags
     if (a.n <= 0) return hipSuccess;
     const int block = rollout_grad_block(a.n);
     const unsigned grid = (unsigned)((a.n + block - 1) / block);
+    if (a.start) {   // the warm entry: the same launch shape on the warm kernels
+        if (a.params) {
+            if (H == 4) hipLaunchKernelGGL(compact_exact_warm_rows_reg_kernel<4>, dim3(grid), dim3(block), 0, s, a, flags);
+            else if (H == 5) hipLaunchKernelGGL(compact_exact_warm_rows_reg_kernel<5>, dim3(grid), dim3(block), 0, s, a, flags);
+            else hipLaunchKernelGGL(compact_exact_warm_rows_ws_kernel, dim3(grid), dim3(block), 0, s, a, H, (double*)ws, flags);
+        } else {
+            if (H == 4) hipLaunchKernelGGL(compact_exact_warm_reg_kernel<4>, dim3(grid), dim3(block), 0, s, a, flags);
+            else if (H == 5) hipLaunchKernelGGL(compact_exact_warm_reg_kernel<5>, dim3(grid), dim3(block), 0, s, a, flags);
+            else hipLaunchKernelGGL(compact_exact_warm_ws_kernel, dim3(grid), dim3(block), 0, s, a, H, (double*)ws, flags);
+        }
+        return hipGetLastError();
+    }
     if (a.params) {
         if (H == 4) hipLaunchKernelGGL(compact_exact_rows_reg_kernel<4>, dim3(grid), dim3(block), 0, s, a, flags);
         else if (H == 5) hipLaunchKernelGGL(compact_exact_rows_reg_kernel<5>, dim3(grid), dim3(block), 0, s, a, flags);
@@ -133,8 +182,10 @@ uint32_t compact_exact_host(int H, const cexact::Args& a) {
     std::vector<double> ws((size_t)cexact::kSlots * H);
     uint32_t flags = 0;
     for (int64_t k = 0; k < a.n; ++k) {
-        const uint32_t f = a.params ? cexact::exact_instance<0, true>(a, H, k, ws.data(), 1)
-                                    : cexact::exact_instance<0>(a, H, k, ws.data(), 1);
+        const uint32_t f = a.start ? (a.params ? cexact::exact_instance<0, true, true>(a, H, k, ws.data(), 1)
+                                               : cexact::exact_instance<0, false, true>(a, H, k, ws.data(), 1))
+                           : a.params ? cexact::exact_instance<0, true>(a, H, k, ws.data(), 1)
+                                      : cexact::exact_instance<0>(a, H, k, ws.data(), 1);
         flags |= a.raise_not_polished ? f : (f & ~0x8u);
     }
     return flags;

@@ -41,6 +41,8 @@ struct Args {
     int32_t* fell_back;
     int32_t* fb_index;    // [n] the instances for the fallback, in no particular order; null: not collected
     uint32_t* fb_count;   // how many
+    const double* start;  // the warm entry (exact_instance<.., WARM = true>): [H*2] rows ld_start apart, the start of
+    int64_t ld_start;     // instance k in column k; may be seq (a lane reads its column before its first write)
 };
 
 constexpr int kI = 2;
@@ -83,7 +85,10 @@ TPC_GRAD_HD grad::Model build_model(const Args& a, double v) {
 // first workspace element.  Returns its TPC_MPC_FLAG_* bits: 0x1 non-finite, 0x4 bad model (both: nothing run), 0x8
 // not verified; in all three cases the outputs are zeros with status -1 (residual_in keeps round 0's value when rounds
 // were run, as the polish reports it).
-template <int HC, bool ROWS = false>
+// WARM (tpc_mpc_solve_batch_compact_exact_from): the working copy starts at the clamped column k of a.start where the
+// parents start at clampd(0.0, ..); a column with a non-finite component means "no start" and is the parents' start in
+// every component.  WARM = false compiles to the parents' code: a.start is not read.
+template <int HC, bool ROWS = false, bool WARM = false>
 TPC_GRAD_HD uint32_t exact_instance(const Args& a, int Hrt, int64_t k, double* ws, int64_t wn) {
     constexpr int I = kI;
     const int H = HC > 0 ? HC : Hrt;
@@ -115,9 +120,26 @@ TPC_GRAD_HD uint32_t exact_instance(const Args& a, int Hrt, int64_t k, double* w
         finish(-1, 0.0, 0.0);
         return bad;
     }
-    for (int t = 0; t < H; ++t)
+    if (WARM) {
+        // one pass over the column: clamp into the slots and track finiteness of what was loaded (the clamp would hide
+        // an Inf); the slots are rewritten only for a column that was not finite
+        bool have = true;
+        for (int t = 0; t < H; ++t)
 #pragma unroll
-        for (int j = 0; j < I; ++j) slot(kU + j, t) = clampd(0.0, m.lo[j], m.hi[j]);
+            for (int j = 0; j < I; ++j) {
+                const double s = a.start[(int64_t)(t * I + j) * a.ld_start + k];
+                have = have && gfinite(s);
+                slot(kU + j, t) = clampd(s, m.lo[j], m.hi[j]);
+            }
+        if (!have)
+            for (int t = 0; t < H; ++t)
+#pragma unroll
+                for (int j = 0; j < I; ++j) slot(kU + j, t) = clampd(0.0, m.lo[j], m.hi[j]);
+    } else {
+        for (int t = 0; t < H; ++t)
+#pragma unroll
+            for (int j = 0; j < I; ++j) slot(kU + j, t) = clampd(0.0, m.lo[j], m.hi[j]);
+    }
 
     double res_in = 0.0, prev = 0.0;
     bool inner = false;

@@ -1910,8 +1910,11 @@ int tpc_mpc_rollout_newton(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_
 // the compact batch.
 // `rows`: tpc_mpc_solve_batch_compact_exact_rows -- the ten model values per instance from params_rows ([10], ld n, in
 // `mem` like v), p's own neither read nor checked; HOST rows are staged behind v, dy, dphi.
+// `warm`: tpc_mpc_solve_batch_compact_exact_from -- phase 1 starts from `start` ([H*2], ld n, in `mem`; HOST rows are
+// staged behind the others) on the warm kernels; everything after phase 1 is the same code.
 static int compact_exact_impl(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t n, const void* v, const void* delta_y,
-                              const void* delta_phi, bool rows, const void* params_rows, const tpc_mpc_polish* q,
+                              const void* delta_phi, bool rows, const void* params_rows, bool warm, const void* start,
+                              const tpc_mpc_polish* q,
                               int32_t fallback, void* steering_front, void* steering_rear, void* sequence_out,
                               int32_t* fell_back, uint32_t* flags_out, int mem, void* stream) {
     return guarded(h, [&]() -> int {
@@ -1919,7 +1922,9 @@ static int compact_exact_impl(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t
         if (rc) return rc;
         if (p->dtype != TPC_MPC_F64)
             return fail(h, TPC_MPC_ERR_BAD_ARG, "%s is fp64 only: p->dtype must be TPC_MPC_F64",
-                        rows ? "tpc_mpc_solve_batch_compact_exact_rows" : "tpc_mpc_solve_batch_compact_exact");
+                        warm   ? "tpc_mpc_solve_batch_compact_exact_from"
+                        : rows ? "tpc_mpc_solve_batch_compact_exact_rows"
+                               : "tpc_mpc_solve_batch_compact_exact");
         if (!rows) {
             rc = check_compact_model(h, p);
             if (rc) return rc;
@@ -1940,6 +1945,7 @@ static int compact_exact_impl(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t
         if (!v || !delta_y || !delta_phi || !steering_front || !steering_rear)
             return fail(h, TPC_MPC_ERR_BAD_ARG, "null batch pointer");
         if (rows && !params_rows) return fail(h, TPC_MPC_ERR_BAD_ARG, "null params_rows");
+        if (warm && !start) return fail(h, TPC_MPC_ERR_BAD_ARG, "null start");
         const int H = p->horizon;
         constexpr int kP = cgrad::kParams;
 
@@ -1956,6 +1962,8 @@ static int compact_exact_impl(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t
         a.tol = q->tol; a.max_rounds = q->max_rounds;
         a.raise_not_polished = solve ? 0 : 1;
         a.ld_seq = n;
+        a.start = warm ? (const double*)start : nullptr;
+        a.ld_start = n;
 
         if (h->host_only) {   // on the calling thread, straight from and into the caller's arrays
             a.v = (const double*)v; a.dy = (const double*)delta_y; a.dphi = (const double*)delta_phi;
@@ -1974,11 +1982,11 @@ static int compact_exact_impl(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t
         if (rc) return rc;
         const bool host = mem == TPC_MPC_HOST;
         // the working set: the queue and two words ([0] the fallback's count, [1] phase 1's flags), then for HOST
-        // arrays the staging rows, leading dimension ldw: v dy dphi params[10] | front rear seq[2H] res_in res_out |
-        // status fell_back
+        // arrays the staging rows, leading dimension ldw: v dy dphi params[10] start[2H] | front rear seq[2H] res_in
+        // res_out | status fell_back
         const int64_t ldw = (n + 63) / 64 * 64;
         const int64_t o_words = ldw * 4, o_stage = o_words + 256;
-        const int64_t rows8 = 3 + (rows ? kP : 0) + 2 + (sequence_out ? 2 * H : 0) + (q->residual_in ? 1 : 0) + (q->residual_out ? 1 : 0);
+        const int64_t rows8 = 3 + (rows ? kP : 0) + (warm ? 2 * H : 0) + 2 + (sequence_out ? 2 * H : 0) + (q->residual_in ? 1 : 0) + (q->residual_out ? 1 : 0);
         const int64_t o_i32 = o_stage + rows8 * ldw * 8;
         rc = ensure(h, &h->newton, &h->newton_bytes, host ? o_i32 + 2 * ldw * 4 : o_stage);
         if (rc) return rc;
@@ -2011,6 +2019,11 @@ static int compact_exact_impl(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t
                 double* sp = row(true, kP);
                 HIP_TRY(h, copy_rows(sp, ldw * 8, params_rows, n * 8, n * 8, kP, hipMemcpyHostToDevice, s));
                 a.params = sp; a.ld_params = ldw;
+            }
+            if (warm) {
+                double* ss = row(true, 2 * H);
+                HIP_TRY(h, copy_rows(ss, ldw * 8, start, n * 8, n * 8, 2 * H, hipMemcpyHostToDevice, s));
+                a.start = ss; a.ld_start = ldw;
             }
             a.front = row(true, 1); a.rear = row(true, 1);
             a.seq = row(sequence_out != nullptr, 2 * H);
@@ -2093,8 +2106,8 @@ int tpc_mpc_solve_batch_compact_exact(tpc_mpc_handle h, const tpc_mpc_params* p,
                                       const void* delta_y, const void* delta_phi, const tpc_mpc_polish* q,
                                       int32_t fallback, void* steering_front, void* steering_rear, void* sequence_out,
                                       int32_t* fell_back, uint32_t* flags_out, int mem, void* stream) {
-    return compact_exact_impl(h, p, n, v, delta_y, delta_phi, false, nullptr, q, fallback, steering_front, steering_rear,
-                              sequence_out, fell_back, flags_out, mem, stream);
+    return compact_exact_impl(h, p, n, v, delta_y, delta_phi, false, nullptr, false, nullptr, q, fallback,
+                              steering_front, steering_rear, sequence_out, fell_back, flags_out, mem, stream);
 }
 
 int tpc_mpc_solve_batch_compact_exact_rows(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t n, const void* v,
@@ -2102,8 +2115,17 @@ int tpc_mpc_solve_batch_compact_exact_rows(tpc_mpc_handle h, const tpc_mpc_param
                                            const tpc_mpc_polish* q, int32_t fallback, void* steering_front,
                                            void* steering_rear, void* sequence_out, int32_t* fell_back,
                                            uint32_t* flags_out, int mem, void* stream) {
-    return compact_exact_impl(h, p, n, v, delta_y, delta_phi, true, params_rows, q, fallback, steering_front,
-                              steering_rear, sequence_out, fell_back, flags_out, mem, stream);
+    return compact_exact_impl(h, p, n, v, delta_y, delta_phi, true, params_rows, false, nullptr, q, fallback,
+                              steering_front, steering_rear, sequence_out, fell_back, flags_out, mem, stream);
+}
+
+int tpc_mpc_solve_batch_compact_exact_from(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t n, const void* v,
+                                           const void* delta_y, const void* delta_phi, const void* params_rows,
+                                           const void* start, const tpc_mpc_polish* q, int32_t fallback,
+                                           void* steering_front, void* steering_rear, void* sequence_out,
+                                           int32_t* fell_back, uint32_t* flags_out, int mem, void* stream) {
+    return compact_exact_impl(h, p, n, v, delta_y, delta_phi, params_rows != nullptr, params_rows, true, start, q,
+                              fallback, steering_front, steering_rear, sequence_out, fell_back, flags_out, mem, stream);
 }
 
 // The backward pass of the exact compact solve: one launch of the adjoint sweep on the model built from v

@@ -208,7 +208,7 @@ class MpcSolver:
 
     def solve_batch_compact_exact(self, v, delta_y, delta_phi, tol: float = 1e-9, max_rounds: int = 16,
                                   fallback: str = "solve", want_status: bool = True, want_sequence: bool = False,
-                                  want_residuals: bool = False, params_rows=None, **over):
+                                  want_residuals: bool = False, params_rows=None, start=None, **over):
         """n independent mpcControllerTobi calls answered with the verified optimum instead of dlib's eps-0.01 point
         (tpc_mpc_solve_batch_compact_exact), fp64 only.
 
@@ -229,6 +229,11 @@ class MpcSolver:
         (tpc_mpc_solve_batch_compact_exact_rows): the solver's ten model values are then not read, an instance with an
         invalid column returns (0, 0) with status -1 and raises FLAG_NONFINITE or FLAG_BAD_MODEL, and the fallback
         expands the unverified instances with their own values.  None is the shared entry.
+        start ([2H, n] fp64, numpy or a contiguous CUDA tensor like v; the layout of `sequence`) warm-starts the Newton
+        rounds (tpc_mpc_solve_batch_compact_exact_from, with or without params_rows): instance k begins at its column,
+        clamped to its bounds -- in a fitting loop, the `sequence` the previous step returned.  A column with a NaN or
+        an Inf means "no start for this one" and is the cold start, as a column of zeros is; the fallback stays cold.
+        None is the cold call above.
         Its derivative is solve_batch_compact_exact_backward (autograd: mpc_compact_exact)."""
         p = self._params(**over)
         H = p.horizon
@@ -244,6 +249,10 @@ class MpcSolver:
                     _is_torch(params_rows) and params_rows.is_cuda and params_rows.dtype == torch.float64
                     and params_rows.is_contiguous() and tuple(params_rows.shape) == rows_shape):
                 raise ValueError(f"params_rows must be a contiguous fp64 CUDA tensor {list(rows_shape)}")
+            if start is not None and not (
+                    _is_torch(start) and start.is_cuda and start.dtype == torch.float64 and start.is_contiguous()
+                    and tuple(start.shape) == (2 * H, n)):
+                raise ValueError(f"start must be a contiguous fp64 CUDA tensor {[2 * H, n]}")
 
             def new(dtype, rows=None):
                 t = torch.empty(n if rows is None else (rows, n),
@@ -259,6 +268,10 @@ class MpcSolver:
                 params_rows = np.ascontiguousarray(params_rows, dtype=np.float64)
                 if params_rows.shape != rows_shape:
                     raise ValueError(f"params_rows must be an array {list(rows_shape)}")
+            if start is not None:
+                start = np.ascontiguousarray(start, dtype=np.float64)
+                if start.shape != (2 * H, n):
+                    raise ValueError(f"start must be an array {[2 * H, n]}")
 
             def new(dtype, rows=None):
                 a = np.empty(n if rows is None else (rows, n), dtype=dtype)
@@ -277,7 +290,12 @@ class MpcSolver:
                         residual_out=rop)
         flags = C.c_uint32(0)
         fp_flags = C.byref(flags) if want_status or fallback != "none" else None
-        if params_rows is None:
+        if start is not None:
+            self._check(self._lib.tpc_mpc_solve_batch_compact_exact_from(
+                self._h, C.byref(p), n, ptr(v), ptr(delta_y), ptr(delta_phi),
+                None if params_rows is None else ptr(params_rows), ptr(start), C.byref(q), fb, fp, rp, sqp, fbp,
+                fp_flags, mem, stream))
+        elif params_rows is None:
             self._check(self._lib.tpc_mpc_solve_batch_compact_exact(
                 self._h, C.byref(p), n, ptr(v), ptr(delta_y), ptr(delta_phi), C.byref(q), fb, fp, rp, sqp, fbp,
                 fp_flags, mem, stream))
