@@ -161,6 +161,38 @@ def test_rollout_shard_of_wider_batch(torch_cuda, mem):
         assert np.array_equal(a, _soa(g[k])), k
 
 
+@pytest.mark.parametrize("I,H", [(2, 7), (1, 3)])
+def test_rollout_record_fp32_host_shard_of_wider_batch(torch_cuda, I, H):
+    """fp32, HOST memory: tpc_mpc_rollout_record on columns [k0, k0+n) of wider arrays (4-byte elements through the
+    staging copies: new_last_targets in; controls, states, iters and sequences out) equals the same instances passed
+    contiguously bit for bit, and nothing outside the shard's columns is written."""
+    from trajectory_controller_amd import capi
+    from trajectory_controller_amd.synth import general_inputs
+    n, ld, k0, steps = 70, 200, 37, 3
+    g = general_inputs(H, ld, I=I, first=3)
+    rng = np.random.default_rng(1)
+    nlt = _soa(g["targets"][:, -1:, :] + rng.uniform(-0.05, 0.05, size=(ld, steps, 2))).astype(np.float32)
+    arrays = [_soa(g[k]).astype(np.float32) for k in GEN_NAMES]
+    sl = slice(k0, k0 + n)
+    with _solver(H, "lane", dtype="f32") as s:
+        want = s.rollout_record(steps, *[np.ascontiguousarray(a[:, sl]) for a in arrays],
+                                new_last_targets=np.ascontiguousarray(nlt[:, sl]), inputs=I, want_iters=True)
+        outs = [np.full((steps * I, ld), SENT, np.float32), np.full((steps * 2, ld), SENT, np.float32),
+                np.full((steps * H * I, ld), SENT, np.float32), np.full((steps, ld), -5, dtype=np.int32)]
+        base = lambda a: a.ctypes.data + k0 * 4
+        io = capi.GeneralIO(inputs=I, n=n, ld=ld, A=base(arrays[0]), B=base(arrays[1]), C=base(arrays[2]),
+                            Q=base(arrays[3]), R=base(arrays[4]), lower=base(arrays[5]), upper=base(arrays[6]),
+                            x0=base(arrays[7]), targets=base(arrays[8]), controls_inout=None, v_inout=None, u0=None,
+                            iters=None)
+        flags = C.c_uint32(0)
+        s._check(s._lib.tpc_mpc_rollout_record(s._h, C.byref(s.params), C.byref(io), steps, base(nlt), base(outs[0]),
+                                               base(outs[1]), base(outs[3]), base(outs[2]), C.byref(flags), capi.HOST,
+                                               None))
+    for got, ref, pad in zip(outs, want, (SENT, SENT, SENT, -5)):
+        assert got[:, sl].tobytes() == ref.tobytes()
+        assert np.all(got[:, :k0] == pad) and np.all(got[:, k0 + n:] == pad)
+
+
 def test_allocation_failure_is_a_status_code(torch_cuda):
     """A reservation no GPU can satisfy (about 0.8 TB of scratch) comes back as TPC_MPC_ERR_ALLOC, and
     the handle keeps working."""

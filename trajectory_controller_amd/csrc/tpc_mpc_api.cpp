@@ -450,6 +450,34 @@ int check_general_io(tpc_mpc_context* h, const tpc_mpc_general_io* io, int mem) 
     return TPC_MPC_OK;
 }
 
+// Checks that several general-form entries make.  Each entry calls them where its own checks need them: the order in
+// which an entry's checks fire is part of its behaviour (a host-only handle reports argument errors before NO_DEVICE).
+// The model's nine arrays (`also`: whether the entry's own required array is there as well)
+int check_model(tpc_mpc_context* h, const tpc_mpc_general_io* io, bool also = true) {
+    if (!io->A || !io->B || !io->C || !io->Q || !io->R || !io->lower || !io->upper || !io->x0 || !io->targets || !also)
+        return fail(h, TPC_MPC_ERR_BAD_ARG, "null batch pointer");
+    return TPC_MPC_OK;
+}
+int check_polish(tpc_mpc_context* h, const tpc_mpc_polish* q) {
+    if (!q) return fail(h, TPC_MPC_ERR_BAD_ARG, "null polish struct");
+    if (!(q->tol > 0.0) || q->max_rounds < 0)
+        return fail(h, TPC_MPC_ERR_BAD_ARG, "polish needs tol > 0 and max_rounds >= 0");
+    return TPC_MPC_OK;
+}
+int check_steps(tpc_mpc_context* h, int32_t steps) {
+    if (steps < 0 || steps > (1 << 24)) return fail(h, TPC_MPC_ERR_BAD_ARG, "need 0 <= steps <= 2^24");
+    return TPC_MPC_OK;
+}
+int check_fallback(tpc_mpc_context* h, int32_t fallback) {
+    if (fallback != TPC_MPC_NEWTON_FALLBACK_SOLVE && fallback != TPC_MPC_NEWTON_FALLBACK_NONE)
+        return fail(h, TPC_MPC_ERR_BAD_ARG, "unknown fallback %d", (int)fallback);
+    return TPC_MPC_OK;
+}
+// (what an entry named `entry` returns for p->dtype != TPC_MPC_F64)
+int fp64_only(tpc_mpc_context* h, const char* entry) {
+    return fail(h, TPC_MPC_ERR_BAD_ARG, "%s is fp64 only: p->dtype must be TPC_MPC_F64", entry);
+}
+
 }  // namespace
 
 namespace tpc {
@@ -668,9 +696,7 @@ int general_launch(tpc_mpc_context* h, const tpc_mpc_params* p, const tpc_mpc_ge
 int check_general_device_io(tpc_mpc_context* h, const tpc_mpc_general_io* io) {
     int rc = check_general_io(h, io, TPC_MPC_DEVICE);
     if (rc) return rc;
-    if (io->n > 0 && (!io->A || !io->B || !io->C || !io->Q || !io->R || !io->lower || !io->upper || !io->x0 || !io->targets || !io->u0))
-        return fail(h, TPC_MPC_ERR_BAD_ARG, "null batch pointer");
-    return TPC_MPC_OK;
+    return io->n > 0 ? check_model(h, io, io->u0 != nullptr) : TPC_MPC_OK;
 }
 
 static void compact_args(tpc_mpc_context* h, const tpc_mpc_params* p, int64_t n, const void* v, const void* dy, const void* dphi,
@@ -832,14 +858,24 @@ int compact_launch(tpc_mpc_context* h, const tpc_mpc_params* p, int64_t n, const
 
 namespace {
 
-// What the two forward-mode entries share after their argument checks: nin input arrays (a null one is not staged) of
-// rows[c] component rows and nout output arrays of rows[nin + c], run by `run(ld, in, out, s, host_flags)` -- on the
-// calling thread for a host-only handle (host_flags != null), else as a launch on s after HOST arrays were staged with
-// the leading dimension lds.  Staging, stream and flag behaviour are tpc_mpc_rollout_backward's.
-template <class Run>
-int forward_run(tpc_mpc_context* h, const tpc_mpc_general_io* io, int mem, void* stream, uint32_t* flags_out,
-                int64_t ws_bytes, const void* const* src, void* const* dst, const int64_t* rows, int nin, int nout,
-                Run run, const int64_t* src_ld = nullptr) {   // src_ld[c]: leading dimension of src[c] where not io->ld (0: io->ld)
+// What only some users of staged_run need of their arrays in the caller's memory; each table may be null
+struct StagedExtra {
+    const int64_t* src_ld = nullptr;   // [NIn] leading dimension of src[c] where not io->ld (0: io->ld)
+    const int64_t* dst_ld = nullptr;   // [NOut] ... and of dst[c]
+    const int* width = nullptr;        // [NIn + NOut] bytes per element where not 8 (0: 8)
+    int inout = -1;                    // src[inout] is written too: its staged copy always goes back to it
+};
+
+// What the one-launch general-form entries share after their argument checks: NIn input arrays (a null one is not
+// staged) of rows[c] component rows and NOut output arrays of rows[NIn + c], run by `run(ld, in, out, s, host_flags)` --
+// on the calling thread for a host-only handle (host_flags != null), else as a launch on s: on the caller's own DEVICE
+// arrays and io->ld, or after HOST arrays were staged in h->stage with the leading dimension lds.  On the stream: the
+// gradient workspace grown to ws_bytes, the staging copies, the flag word zeroed, the launch, the copies back and a
+// synchronise (HOST only), the stream order's event, the flags.
+template <int NIn, int NOut, class Run>
+int staged_run(tpc_mpc_context* h, const tpc_mpc_general_io* io, int mem, void* stream, uint32_t* flags_out,
+               int64_t ws_bytes, const void* const (&src)[NIn], void* const (&dst)[NOut],
+               const int64_t (&rows)[NIn + NOut], Run run, const StagedExtra& x = StagedExtra()) {
     const int64_t n = io->n;
     if (h->host_only) {   // on the calling thread, straight from and into the caller's arrays
         uint32_t f = 0;
@@ -855,44 +891,60 @@ int forward_run(tpc_mpc_context* h, const tpc_mpc_general_io* io, int mem, void*
     rc = ensure(h, &h->grad_ws, &h->grad_ws_bytes, pad256(ws_bytes));
     if (rc) return rc;
     const int64_t lds = (n + 63) / 64 * 64;
-    std::vector<int64_t> off(nin + nout, 0);
-    std::vector<const void*> sin(src, src + nin);
-    std::vector<void*> sout(dst, dst + nout);
+    const void* sin[NIn];
+    void* sout[NOut];
+    for (int c = 0; c < NIn; ++c) sin[c] = src[c];
+    for (int c = 0; c < NOut; ++c) sout[c] = dst[c];
     int64_t ld = io->ld;
-    if (mem == TPC_MPC_HOST) {
+    const bool host = mem == TPC_MPC_HOST;
+    auto width = [&](int c) -> int64_t { return x.width && x.width[c] ? x.width[c] : 8; };
+    auto ld_of = [&](const int64_t* lds_given, int c) { return lds_given && lds_given[c] ? lds_given[c] : io->ld; };
+    if (host) {
         // HOST arrays: every component row copied on its own (n elements, never ld); only the arrays given are staged
-        int64_t total = 0;
-        for (int c = 0; c < nin + nout; ++c) {
-            const bool given = c < nin ? src[c] != nullptr : dst[c - nin] != nullptr;
+        int64_t off[NIn + NOut], total = 0;
+        for (int c = 0; c < NIn + NOut; ++c) {
+            const bool given = c < NIn ? src[c] != nullptr : dst[c - NIn] != nullptr;
             off[c] = total;
-            if (given) total += pad256(rows[c] * lds * 8);
+            if (given) total += pad256(rows[c] * lds * width(c));
         }
         rc = ensure(h, &h->stage, &h->stage_bytes, total);
         if (rc) return rc;
         char* b = (char*)h->stage;
-        for (int c = 0; c < nin; ++c) {
-            sin[c] = src[c] ? b + off[c] : nullptr;
-            if (src[c])
-                HIP_TRY(h, copy_rows(b + off[c], lds * 8, src[c], (src_ld && src_ld[c] ? src_ld[c] : io->ld) * 8, n * 8,
-                                     rows[c], hipMemcpyHostToDevice, s));
+        for (int c = 0; c < NIn; ++c) {
+            if (!src[c]) continue;
+            sin[c] = b + off[c];
+            HIP_TRY(h, copy_rows(b + off[c], lds * width(c), src[c], ld_of(x.src_ld, c) * width(c), n * width(c), rows[c],
+                                 hipMemcpyHostToDevice, s));
         }
-        for (int c = 0; c < nout; ++c) sout[c] = dst[c] ? b + off[nin + c] : nullptr;
+        for (int c = 0; c < NOut; ++c)
+            if (dst[c]) sout[c] = b + off[NIn + c];
         ld = lds;
     }
     HIP_TRY(h, hipMemsetAsync(h->ws_words + 1, 0, sizeof(uint32_t), s));
-    hipError_t e = run(ld, sin.data(), sout.data(), s, (uint32_t*)nullptr);
+    hipError_t e = run(ld, sin, sout, s, (uint32_t*)nullptr);
     if (e != hipSuccess) return hip_fail(h, e, "kernel launch");
-    if (mem == TPC_MPC_HOST) {
-        const char* b = (const char*)h->stage;
-        for (int c = 0; c < nout; ++c)
+    if (host) {
+        if (x.inout >= 0) {
+            const int c = x.inout;
+            HIP_TRY(h, copy_rows(const_cast<void*>(src[c]), ld_of(x.src_ld, c) * width(c), sin[c], lds * width(c),
+                                 n * width(c), rows[c], hipMemcpyDeviceToHost, s));
+        }
+        for (int c = 0; c < NOut; ++c)
             if (dst[c])
-                HIP_TRY(h, copy_rows(dst[c], io->ld * 8, b + off[nin + c], lds * 8, n * 8, rows[nin + c],
-                                     hipMemcpyDeviceToHost, s));
+                HIP_TRY(h, copy_rows(dst[c], ld_of(x.dst_ld, c) * width(NIn + c), sout[c], lds * width(NIn + c),
+                                     n * width(NIn + c), rows[NIn + c], hipMemcpyDeviceToHost, s));
         HIP_TRY(h, hipStreamSynchronize(s));
     }
     rc = order.end();
     if (rc) return rc;
     return finish_flags(h, flags_out, s);
+}
+
+// the model's nine arrays, in[0..8] in the io's order, into the Args of a gradient, polish or tangent kernel
+template <class Args> void bind_model(Args* a, const void* const* in) {
+    a->A = (const double*)in[0]; a->B = (const double*)in[1]; a->C = (const double*)in[2];
+    a->Q = (const double*)in[3]; a->R = (const double*)in[4]; a->lo = (const double*)in[5];
+    a->hi = (const double*)in[6]; a->x0 = (const double*)in[7]; a->targets = (const double*)in[8];
 }
 
 // the ten tangent arrays of a tpc_mpc_tangents in Dirs' order, from in[0..9]
@@ -903,6 +955,70 @@ tangent::Dirs bind_dirs(const void* const* in) {
     d.thi = (const double*)in[6]; d.tx0 = (const double*)in[7]; d.ttargets = (const double*)in[8];
     d.tnlt = (const double*)in[9];
     return d;
+}
+
+// The per-step arrays of the closed loops (rollout_impl, rollout_newton_impl): new_last_targets and the plant's
+// disturbance in, seven outputs; a null one is not there.  The kernels take the caller's DEVICE arrays as they are.
+// HOST arrays go through h->stage: stage_steps gives every array that is there a slot with the leading dimension ldw
+// (n rounded up to a wavefront) and copies the inputs in, unstage_steps copies the outputs back -- n elements per row,
+// so a caller's ld > n (a shard of a wider batch) is neither over-read nor over-written.
+enum { kStepCtrl, kStepStates, kStepIters, kStepSeq, kStepStatus, kStepRin, kStepRout, kStepOuts };
+struct StepArrays {
+    const void* in[2];      // new_last_targets [steps*2] (ld_nlt), disturbance [steps*2] (ld_d)
+    void* out[kStepOuts];   // (ld_out)
+    int64_t ld_nlt, ld_d, ld_out;
+    int64_t rows[2 + kStepOuts], width[2 + kStepOuts];   // component rows and bytes per element: in, then out
+};
+// the caller's arrays; es: bytes per element of the loop's arithmetic (iters and status are int32, the residuals fp64
+// whatever it is); q null: a loop without the polish's outputs
+StepArrays step_arrays(const tpc_mpc_general_io* io, int H, int64_t S, int64_t es, const void* new_last_targets,
+                       const tpc_mpc_plant* plant, void* controls_out, void* states_out, int32_t* iters_out,
+                       void* sequences_out, const tpc_mpc_polish* q) {
+    const int64_t I = io->inputs;
+    const void* dist = plant ? plant->disturbance : nullptr;
+    return StepArrays{{new_last_targets, dist},
+                      {controls_out, states_out, iters_out, sequences_out, q ? q->status : nullptr,
+                       q ? q->residual_in : nullptr, q ? q->residual_out : nullptr},
+                      io->ld, dist ? plant->ld_d : 0, io->ld,
+                      {2 * S, 2 * S, S * I, 2 * S, S, S * H * I, S, S, S},
+                      {es, es, es, es, 4, es, 4, 8, 8}};
+}
+// *d: what the kernels take for the caller's g
+int stage_steps(tpc_mpc_context* h, const StepArrays& g, bool host, int64_t n, hipStream_t s, StepArrays* d) {
+    *d = g;
+    if (!host) return TPC_MPC_OK;
+    const int64_t ldw = (n + 63) / 64 * 64;
+    int64_t off[2 + kStepOuts], total = 0;
+    for (int c = 0; c < 2 + kStepOuts; ++c) {
+        off[c] = total;
+        if (c < 2 ? g.in[c] != nullptr : g.out[c - 2] != nullptr) total += pad256(g.rows[c] * ldw * g.width[c]);
+    }
+    int rc = ensure(h, &h->stage, &h->stage_bytes, total);
+    if (rc) return rc;
+    char* b = (char*)h->stage;
+    const int64_t in_ld[2] = {g.ld_nlt, g.ld_d};
+    for (int c = 0; c < 2; ++c) {
+        if (!g.in[c]) continue;
+        const int64_t w = g.width[c];
+        HIP_TRY(h, copy_rows(b + off[c], ldw * w, g.in[c], in_ld[c] * w, n * w, g.rows[c], hipMemcpyHostToDevice, s));
+        d->in[c] = b + off[c];
+    }
+    for (int c = 0; c < kStepOuts; ++c)
+        if (g.out[c]) d->out[c] = b + off[2 + c];
+    d->ld_nlt = d->ld_out = ldw;
+    if (g.in[1]) d->ld_d = ldw;
+    return TPC_MPC_OK;
+}
+// HOST arrays only: the staged outputs d back into the caller's g, and the wait for them
+int unstage_steps(tpc_mpc_context* h, const StepArrays& g, const StepArrays& d, int64_t n, hipStream_t s) {
+    for (int c = 0; c < kStepOuts; ++c) {
+        const int64_t w = g.width[2 + c];
+        if (g.out[c])
+            HIP_TRY(h, copy_rows(g.out[c], g.ld_out * w, d.out[c], d.ld_out * w, n * w, g.rows[2 + c],
+                                 hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return TPC_MPC_OK;
 }
 
 }  // namespace
@@ -1123,9 +1239,8 @@ int tpc_mpc_solve_batch_general(tpc_mpc_handle h, const tpc_mpc_params* p,
         rc = check_general_io(h, io, mem);
         if (rc) return rc;
         if (io->n == 0) { if (flags_out) *flags_out = 0; return TPC_MPC_OK; }
-        if (!io->A || !io->B || !io->C || !io->Q || !io->R || !io->lower || !io->upper || !io->x0 ||
-            !io->targets || !io->u0)
-            return fail(h, TPC_MPC_ERR_BAD_ARG, "null batch pointer");
+        rc = check_model(h, io, io->u0 != nullptr);
+        if (rc) return rc;
         HIP_TRY(h, hipSetDevice(h->device));
         hipStream_t s = (hipStream_t)stream;
         const int64_t es = (int64_t)esize(p->dtype);
@@ -1221,16 +1336,15 @@ int tpc_mpc_solve_batch_general_backward(tpc_mpc_handle h, const tpc_mpc_params*
     return guarded(h, [&]() -> int {
         int rc = check_common(h, p, true);
         if (rc) return rc;
-        if (p->dtype != TPC_MPC_F64)
-            return fail(h, TPC_MPC_ERR_BAD_ARG, "tpc_mpc_solve_batch_general_backward is fp64 only: p->dtype must be TPC_MPC_F64");
+        if (p->dtype != TPC_MPC_F64) return fp64_only(h, "tpc_mpc_solve_batch_general_backward");
         rc = check_general_io(h, io, mem);
         if (rc) return rc;
         if (!g) return fail(h, TPC_MPC_ERR_BAD_ARG, "null gradient struct");
         if (h->host_only && mem == TPC_MPC_DEVICE)
             return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): the backward pass takes HOST memory only");
         if (io->n == 0) { if (flags_out) *flags_out = 0; return TPC_MPC_OK; }
-        if (!io->A || !io->B || !io->C || !io->Q || !io->R || !io->lower || !io->upper || !io->x0 || !io->targets)
-            return fail(h, TPC_MPC_ERR_BAD_ARG, "null batch pointer");
+        rc = check_model(h, io);
+        if (rc) return rc;
         if (!g->controls || !g->grad_controls) return fail(h, TPC_MPC_ERR_BAD_ARG, "null controls / grad_controls");
         const int I = io->inputs, H = p->horizon;
         const int64_t n = io->n;
@@ -1238,70 +1352,22 @@ int tpc_mpc_solve_batch_general_backward(tpc_mpc_handle h, const tpc_mpc_params*
         const void* src[11] = {io->A, io->B, io->C, io->Q, io->R, io->lower, io->upper, io->x0, io->targets,
                                g->controls, g->grad_controls};
         void* dst[10] = {g->dA, g->dB, g->dC, g->dQ, g->dR, g->dlower, g->dupper, g->dx0, g->dtargets, g->kkt_residual};
-        const int comps[21] = {4, 2 * I, 2, 2, I, I, I, 2, 2 * H, H * I, H * I,
-                               4, 2 * I, 2, 2, I, I, I, 2, 2 * H, 1};
-        auto bind = [](grad::Args* a, const void* const* in, void* const* out) {
-            a->A = (const double*)in[0]; a->B = (const double*)in[1]; a->C = (const double*)in[2];
-            a->Q = (const double*)in[3]; a->R = (const double*)in[4]; a->lo = (const double*)in[5];
-            a->hi = (const double*)in[6]; a->x0 = (const double*)in[7]; a->targets = (const double*)in[8];
-            a->u = (const double*)in[9]; a->g = (const double*)in[10];
-            a->dA = (double*)out[0]; a->dB = (double*)out[1]; a->dC = (double*)out[2]; a->dQ = (double*)out[3];
-            a->dR = (double*)out[4]; a->dlo = (double*)out[5]; a->dhi = (double*)out[6]; a->dx0 = (double*)out[7];
-            a->dtargets = (double*)out[8]; a->kkt = (double*)out[9];
-        };
-        grad::Args a;
-        std::memset(&a, 0, sizeof(a));
-        a.n = n;
-        if (h->host_only) {   // on the calling thread, straight from and into the caller's arrays
-            a.ld = io->ld;
-            bind(&a, src, dst);
-            const uint32_t f = grad_general_host(I, H, a);
-            if (flags_out) *flags_out = f;
-            return TPC_MPC_OK;
-        }
-        HIP_TRY(h, hipSetDevice(h->device));
-        hipStream_t s = (hipStream_t)stream;
-        StreamOrderScope order(h, s);
-        rc = order.begin();
-        if (rc) return rc;
-        rc = ensure(h, &h->grad_ws, &h->grad_ws_bytes, pad256(grad_scratch_bytes(I, H, n)));
-        if (rc) return rc;
-        const int64_t lds = (n + 63) / 64 * 64;
-        int64_t off[21] = {0};
-        if (mem == TPC_MPC_DEVICE) {
-            a.ld = io->ld;
-            bind(&a, src, dst);
-        } else {
-            // HOST arrays: every component row copied on its own (n elements, never ld), as tpc_mpc_solve_batch_general
-            int64_t total = 0;
-            for (int c = 0; c < 21; ++c) { off[c] = total; total += pad256((int64_t)comps[c] * lds * 8); }
-            rc = ensure(h, &h->stage, &h->stage_bytes, total);
-            if (rc) return rc;
-            char* b = (char*)h->stage;
-            const void* sin[11];
-            void* sout[10];
-            for (int c = 0; c < 11; ++c) {
-                HIP_TRY(h, copy_rows(b + off[c], lds * 8, src[c], io->ld * 8, n * 8, comps[c], hipMemcpyHostToDevice, s));
-                sin[c] = b + off[c];
-            }
-            for (int c = 0; c < 10; ++c) sout[c] = dst[c] ? b + off[11 + c] : nullptr;
-            a.ld = lds;
-            bind(&a, sin, sout);
-        }
-        HIP_TRY(h, hipMemsetAsync(h->ws_words + 1, 0, sizeof(uint32_t), s));
-        hipError_t e = grad_general(I, H, a, h->grad_ws, h->ws_words + 1, s);
-        if (e != hipSuccess) return hip_fail(h, e, "kernel launch");
-        if (mem == TPC_MPC_HOST) {
-            const char* b = (const char*)h->stage;
-            for (int c = 0; c < 10; ++c)
-                if (dst[c])
-                    HIP_TRY(h, copy_rows(dst[c], io->ld * 8, b + off[11 + c], lds * 8, n * 8, comps[11 + c],
-                                         hipMemcpyDeviceToHost, s));
-            HIP_TRY(h, hipStreamSynchronize(s));
-        }
-        rc = order.end();
-        if (rc) return rc;
-        return finish_flags(h, flags_out, s);
+        const int64_t rows[21] = {4, 2 * I, 2, 2, I, I, I, 2, 2 * H, H * I, H * I,
+                                  4, 2 * I, 2, 2, I, I, I, 2, 2 * H, 1};
+        return staged_run(h, io, mem, stream, flags_out, grad_scratch_bytes(I, H, n), src, dst, rows,
+                          [&](int64_t ld, const void* const* in, void* const* out, hipStream_t s, uint32_t* hf) {
+                              grad::Args a;
+                              std::memset(&a, 0, sizeof(a));
+                              a.n = n; a.ld = ld;
+                              bind_model(&a, in);
+                              a.u = (const double*)in[9]; a.g = (const double*)in[10];
+                              a.dA = (double*)out[0]; a.dB = (double*)out[1]; a.dC = (double*)out[2];
+                              a.dQ = (double*)out[3]; a.dR = (double*)out[4]; a.dlo = (double*)out[5];
+                              a.dhi = (double*)out[6]; a.dx0 = (double*)out[7]; a.dtargets = (double*)out[8];
+                              a.kkt = (double*)out[9];
+                              if (hf) { *hf = grad_general_host(I, H, a); return hipSuccess; }
+                              return grad_general(I, H, a, h->grad_ws, h->ws_words + 1, s);
+                          });
     });
 }
 
@@ -1310,92 +1376,43 @@ int tpc_mpc_polish_batch_general(tpc_mpc_handle h, const tpc_mpc_params* p, cons
     return guarded(h, [&]() -> int {
         int rc = check_common(h, p, true);
         if (rc) return rc;
-        if (p->dtype != TPC_MPC_F64)
-            return fail(h, TPC_MPC_ERR_BAD_ARG, "tpc_mpc_polish_batch_general is fp64 only: p->dtype must be TPC_MPC_F64");
+        if (p->dtype != TPC_MPC_F64) return fp64_only(h, "tpc_mpc_polish_batch_general");
         rc = check_general_io(h, io, mem);
         if (rc) return rc;
-        if (!q) return fail(h, TPC_MPC_ERR_BAD_ARG, "null polish struct");
-        if (!(q->tol > 0.0) || q->max_rounds < 0)
-            return fail(h, TPC_MPC_ERR_BAD_ARG, "polish needs tol > 0 and max_rounds >= 0");
+        rc = check_polish(h, q);
+        if (rc) return rc;
         if (h->host_only && mem == TPC_MPC_DEVICE)
             return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): the polish takes HOST memory only");
         if (io->n == 0) { if (flags_out) *flags_out = 0; return TPC_MPC_OK; }
-        if (!io->A || !io->B || !io->C || !io->Q || !io->R || !io->lower || !io->upper || !io->x0 || !io->targets)
-            return fail(h, TPC_MPC_ERR_BAD_ARG, "null batch pointer");
+        rc = check_model(h, io);
+        if (rc) return rc;
         if (!io->controls_inout) return fail(h, TPC_MPC_ERR_BAD_ARG, "null controls_inout: the sequence to polish");
         const int I = io->inputs, H = p->horizon;
         const int64_t n = io->n;
-        // the arrays in order: 10 inputs (controls_inout is also the first output), then u0, the residuals (fp64) and
-        // the status (int32), with their component counts
+        // the arrays in order: 10 inputs (controls_inout is polished in place: in and out), then u0, the residuals
+        // (fp64) and the status (int32), with their component counts
         const void* src[10] = {io->A, io->B, io->C, io->Q, io->R, io->lower, io->upper, io->x0, io->targets,
                                io->controls_inout};
         void* dst[4] = {io->u0, q->residual_in, q->residual_out, q->status};
-        const int comps[14] = {4, 2 * I, 2, 2, I, I, I, 2, 2 * H, H * I, I, 1, 1, 1};
-        auto bind = [](polish::Args* a, const void* const* in, void* const* out) {
-            a->A = (const double*)in[0]; a->B = (const double*)in[1]; a->C = (const double*)in[2];
-            a->Q = (const double*)in[3]; a->R = (const double*)in[4]; a->lo = (const double*)in[5];
-            a->hi = (const double*)in[6]; a->x0 = (const double*)in[7]; a->targets = (const double*)in[8];
-            a->u = (double*)in[9];
-            a->u0 = (double*)out[0]; a->res_in = (double*)out[1]; a->res_out = (double*)out[2];
-            a->status = (int32_t*)out[3];
-        };
-        polish::Args a;
-        std::memset(&a, 0, sizeof(a));
-        a.n = n;
-        a.tol = q->tol;
-        a.max_rounds = q->max_rounds;
-        if (h->host_only) {   // on the calling thread, straight from and into the caller's arrays
-            a.ld = io->ld;
-            bind(&a, src, dst);
-            const uint32_t f = polish_general_host(I, H, a);
-            if (flags_out) *flags_out = f;
-            return TPC_MPC_OK;
-        }
-        HIP_TRY(h, hipSetDevice(h->device));
-        hipStream_t s = (hipStream_t)stream;
-        StreamOrderScope order(h, s);
-        rc = order.begin();
-        if (rc) return rc;
-        rc = ensure(h, &h->grad_ws, &h->grad_ws_bytes, pad256(polish_scratch_bytes(I, H, n)));
-        if (rc) return rc;
-        const int64_t lds = (n + 63) / 64 * 64;
-        int64_t off[14] = {0};
-        if (mem == TPC_MPC_DEVICE) {
-            a.ld = io->ld;
-            bind(&a, src, dst);
-        } else {
-            // HOST arrays: every component row copied on its own (n elements, never ld), as the backward entry
-            int64_t total = 0;
-            for (int c = 0; c < 14; ++c) { off[c] = total; total += pad256((int64_t)comps[c] * lds * 8); }
-            rc = ensure(h, &h->stage, &h->stage_bytes, total);
-            if (rc) return rc;
-            char* b = (char*)h->stage;
-            const void* sin[10];
-            void* sout[4];
-            for (int c = 0; c < 10; ++c) {
-                HIP_TRY(h, copy_rows(b + off[c], lds * 8, src[c], io->ld * 8, n * 8, comps[c], hipMemcpyHostToDevice, s));
-                sin[c] = b + off[c];
-            }
-            for (int c = 0; c < 4; ++c) sout[c] = dst[c] ? b + off[10 + c] : nullptr;
-            a.ld = lds;
-            bind(&a, sin, sout);
-        }
-        HIP_TRY(h, hipMemsetAsync(h->ws_words + 1, 0, sizeof(uint32_t), s));
-        hipError_t e = polish_general(I, H, a, h->grad_ws, h->ws_words + 1, s);
-        if (e != hipSuccess) return hip_fail(h, e, "kernel launch");
-        if (mem == TPC_MPC_HOST) {
-            const char* b = (const char*)h->stage;
-            HIP_TRY(h, copy_rows(io->controls_inout, io->ld * 8, b + off[9], lds * 8, n * 8, H * I, hipMemcpyDeviceToHost, s));
-            for (int c = 0; c < 3; ++c)
-                if (dst[c])
-                    HIP_TRY(h, copy_rows(dst[c], io->ld * 8, b + off[10 + c], lds * 8, n * 8, comps[10 + c],
-                                         hipMemcpyDeviceToHost, s));
-            if (q->status) HIP_TRY(h, hipMemcpyAsync(q->status, b + off[13], n * 4, hipMemcpyDeviceToHost, s));
-            HIP_TRY(h, hipStreamSynchronize(s));
-        }
-        rc = order.end();
-        if (rc) return rc;
-        return finish_flags(h, flags_out, s);
+        const int64_t rows[14] = {4, 2 * I, 2, 2, I, I, I, 2, 2 * H, H * I, I, 1, 1, 1};
+        int width[14] = {0};
+        width[13] = 4;
+        StagedExtra x;
+        x.width = width;
+        x.inout = 9;
+        return staged_run(h, io, mem, stream, flags_out, polish_scratch_bytes(I, H, n), src, dst, rows,
+                          [&](int64_t ld, const void* const* in, void* const* out, hipStream_t s, uint32_t* hf) {
+                              polish::Args a;
+                              std::memset(&a, 0, sizeof(a));
+                              a.n = n; a.ld = ld; a.tol = q->tol; a.max_rounds = q->max_rounds;
+                              bind_model(&a, in);
+                              a.u = (double*)in[9];
+                              a.u0 = (double*)out[0]; a.res_in = (double*)out[1]; a.res_out = (double*)out[2];
+                              a.status = (int32_t*)out[3];
+                              if (hf) { *hf = polish_general_host(I, H, a); return hipSuccess; }
+                              return polish_general(I, H, a, h->grad_ws, h->ws_words + 1, s);
+                          },
+                          x);
     });
 }
 
@@ -1412,20 +1429,17 @@ int rollout_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_genera
         // (plant: tpc_mpc_rollout_plant, which has checked the plant itself; null: the controller's model moves the state)
         int rc = check_common(h, p, polished || plant);
         if (rc) return rc;
-        if (polished && p->dtype != TPC_MPC_F64)
-            return fail(h, TPC_MPC_ERR_BAD_ARG, "tpc_mpc_rollout_polished is fp64 only: p->dtype must be TPC_MPC_F64");
+        if (polished && p->dtype != TPC_MPC_F64) return fp64_only(h, "tpc_mpc_rollout_polished");
         rc = check_general_io(h, io, mem);
         if (rc) return rc;
-        if (polished && !q) return fail(h, TPC_MPC_ERR_BAD_ARG, "null polish struct");
-        if (polished && (!(q->tol > 0.0) || q->max_rounds < 0))
-            return fail(h, TPC_MPC_ERR_BAD_ARG, "polish needs tol > 0 and max_rounds >= 0");
-        if (steps < 0 || steps > (1 << 24)) return fail(h, TPC_MPC_ERR_BAD_ARG, "need 0 <= steps <= 2^24");
+        if (polished) rc = check_polish(h, q);
+        if (!rc) rc = check_steps(h, steps);
+        if (rc) return rc;
         if (h->host_only)
             return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): the closed loops run on the device only");
         if (io->n == 0 || steps == 0) { if (flags_out) *flags_out = 0; return TPC_MPC_OK; }
-        if (!io->A || !io->B || !io->C || !io->Q || !io->R || !io->lower || !io->upper || !io->x0 ||
-            !io->targets || !controls_out)
-            return fail(h, TPC_MPC_ERR_BAD_ARG, "null batch pointer");
+        rc = check_model(h, io, controls_out != nullptr);
+        if (rc) return rc;
         if (record && !sequences_out) return fail(h, TPC_MPC_ERR_BAD_ARG, "null sequences_out");
         HIP_TRY(h, hipSetDevice(h->device));
         hipStream_t s = (hipStream_t)stream;
@@ -1453,12 +1467,11 @@ int rollout_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_genera
         int64_t off[12], total = 0;
         for (int c = 0; c < 12; ++c) { off[c] = total; total += pad256((int64_t)comps[c] * ldw * es); }
         const int64_t o_iters = total; total += pad256(ldw * 4);
-        // ... and the plant's arrays and (HOST memory) the disturbance, behind everything the parent loop has
-        const bool plant_abc = plant && plant->A, plant_d = plant && plant->disturbance;
+        // ... and the plant's arrays, behind everything the parent loop has
+        const bool plant_abc = plant && plant->A;
         const int64_t o_pa = total; if (plant_abc) total += pad256(4 * ldw * es);
         const int64_t o_pb = total; if (plant_abc) total += pad256(2 * I * ldw * es);
         const int64_t o_pc = total; if (plant_abc) total += pad256(2 * ldw * es);
-        const int64_t o_pd = total; if (plant_d && mem == TPC_MPC_HOST) total += pad256((int64_t)steps * 2 * ldw * es);
         rc = ensure(h, &h->roll, &h->roll_bytes, total);
         if (rc) return rc;
         if (polished) {
@@ -1470,40 +1483,12 @@ int rollout_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_genera
             if (src[c]) HIP_TRY(h, copy_rows(w + off[c], ldw * es, src[c], ld * es, n * es, comps[c], in_kind, s));
             else HIP_TRY(h, hipMemsetAsync(w + off[c], 0, (size_t)((int64_t)comps[c] * ldw * es), s));
         }
-        // HOST mode: new_last_targets in, and the three per-step outputs, go through the staging buffer
-        const void* d_nlt = new_last_targets;
-        int64_t ld_nlt = ld, ld_out = ld;
-        char *d_ctrl = (char*)controls_out, *d_states = (char*)states_out, *d_seq = (char*)sequences_out;
-        int32_t* d_iters = iters_out;
-        // ... and the polish's three per-step rows ([steps] rows like iters_out)
-        int32_t* d_status = polished ? q->status : nullptr;
-        char *d_rin = polished ? (char*)q->residual_in : nullptr, *d_rout = polished ? (char*)q->residual_out : nullptr;
-        if (host) {
-            const int64_t s_nlt = 0, s_ctrl = s_nlt + pad256((int64_t)steps * 2 * ldw * es);
-            const int64_t s_states = s_ctrl + pad256((int64_t)steps * I * ldw * es);
-            const int64_t s_iters = s_states + pad256((int64_t)steps * 2 * ldw * es);
-            const int64_t s_seq = s_iters + pad256((int64_t)steps * ldw * 4);
-            const int64_t s_status = s_seq + (sequences_out ? pad256((int64_t)steps * H * I * ldw * es) : 0);
-            const int64_t s_rin = s_status + (d_status ? pad256((int64_t)steps * ldw * 4) : 0);
-            const int64_t s_rout = s_rin + (d_rin ? pad256((int64_t)steps * ldw * 8) : 0);
-            const int64_t s_end = s_rout + (d_rout ? pad256((int64_t)steps * ldw * 8) : 0);
-            rc = ensure(h, &h->stage, &h->stage_bytes, s_end);
-            if (rc) return rc;
-            char* b = (char*)h->stage;
-            if (new_last_targets) {
-                HIP_TRY(h, copy_rows(b + s_nlt, ldw * es, new_last_targets, ld * es, n * es, (int64_t)steps * 2,
-                                     hipMemcpyHostToDevice, s));
-                d_nlt = b + s_nlt;
-            }
-            ld_nlt = ld_out = ldw;
-            d_ctrl = b + s_ctrl;
-            d_states = states_out ? b + s_states : nullptr;
-            d_iters = iters_out ? (int32_t*)(b + s_iters) : nullptr;
-            d_seq = sequences_out ? b + s_seq : nullptr;
-            if (d_status) d_status = (int32_t*)(b + s_status);
-            if (d_rin) d_rin = b + s_rin;
-            if (d_rout) d_rout = b + s_rout;
-        }
+        // the per-step arrays: the caller's (g), and what the kernels take for them (d)
+        const StepArrays g = step_arrays(io, H, steps, es, new_last_targets, plant, controls_out, states_out, iters_out,
+                                         sequences_out, polished ? q : nullptr);
+        StepArrays d;
+        rc = stage_steps(h, g, host, n, s, &d);
+        if (rc) return rc;
 
         GeneralArgs a;
         std::memset(&a, 0, sizeof(a));
@@ -1516,24 +1501,17 @@ int rollout_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_genera
 
         RolloutStepArgs r;
         std::memset(&r, 0, sizeof(r));
-        r.n = n; r.ld = ldw; r.ld_out = ld_out; r.ld_nlt = ld_nlt; r.I = I; r.H = H; r.steps = steps;
+        r.n = n; r.ld = ldw; r.ld_out = d.ld_out; r.ld_nlt = d.ld_nlt; r.I = I; r.H = H; r.steps = steps;
         r.A = a.A; r.B = a.B; r.C = a.C;
-        r.x = w + off[7]; r.targets = w + off[8]; r.controls = w + off[9]; r.new_last_targets = d_nlt;
-        r.controls_out = d_ctrl; r.states_out = d_states;
-        r.iters_step = a.iters; r.iters_out = d_iters; r.sequences_out = d_seq;
+        r.x = w + off[7]; r.targets = w + off[8]; r.controls = w + off[9]; r.new_last_targets = d.in[0];
+        r.controls_out = d.out[kStepCtrl]; r.states_out = d.out[kStepStates];
+        r.iters_step = a.iters; r.iters_out = (int32_t*)d.out[kStepIters]; r.sequences_out = d.out[kStepSeq];
+        r.disturbance = d.in[1]; r.ld_d = d.ld_d;
         if (plant_abc) {
             HIP_TRY(h, copy_rows(w + o_pa, ldw * es, plant->A, ld * es, n * es, 4, in_kind, s));
             HIP_TRY(h, copy_rows(w + o_pb, ldw * es, plant->B, ld * es, n * es, 2 * I, in_kind, s));
             HIP_TRY(h, copy_rows(w + o_pc, ldw * es, plant->C, ld * es, n * es, 2, in_kind, s));
             r.A = w + o_pa; r.B = w + o_pb; r.C = w + o_pc;
-        }
-        if (plant_d) {
-            r.disturbance = plant->disturbance; r.ld_d = plant->ld_d;
-            if (host) {
-                HIP_TRY(h, copy_rows(w + o_pd, ldw * es, plant->disturbance, plant->ld_d * es, n * es, (int64_t)steps * 2,
-                                     hipMemcpyHostToDevice, s));
-                r.disturbance = w + o_pd; r.ld_d = ldw;
-            }
         }
 
         polish::Args pa;
@@ -1555,9 +1533,10 @@ int rollout_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_genera
             if (e != hipSuccess) return hip_fail(h, e, "kernel launch");
             r.step = st;
             if (polished) {   // the step's rows of the polish outputs; the sequence is polished where the loop keeps it
-                pa.status = d_status ? d_status + (int64_t)st * ld_out : nullptr;
-                pa.res_in = d_rin ? (double*)d_rin + (int64_t)st * ld_out : nullptr;
-                pa.res_out = d_rout ? (double*)d_rout + (int64_t)st * ld_out : nullptr;
+                const int64_t at = (int64_t)st * d.ld_out;
+                pa.status = d.out[kStepStatus] ? (int32_t*)d.out[kStepStatus] + at : nullptr;
+                pa.res_in = d.out[kStepRin] ? (double*)d.out[kStepRin] + at : nullptr;
+                pa.res_out = d.out[kStepRout] ? (double*)d.out[kStepRout] + at : nullptr;
                 e = launch_rollout_polish_step(I, pa, r, h->grad_ws, h->ws_words + 1, s);
             } else {
                 e = launch_rollout_step(p->dtype, r, s);
@@ -1569,21 +1548,8 @@ int rollout_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_genera
             HIP_TRY(h, copy_rows(io->controls_inout, ld * es, w + off[9], ldw * es, n * es, H * I, out_kind, s));
         if (io->v_inout) HIP_TRY(h, copy_rows(io->v_inout, ld * es, w + off[10], ldw * es, n * es, H * I, out_kind, s));
         if (host) {
-            HIP_TRY(h, copy_rows(controls_out, ld * es, d_ctrl, ldw * es, n * es, (int64_t)steps * I, hipMemcpyDeviceToHost, s));
-            if (states_out)
-                HIP_TRY(h, copy_rows(states_out, ld * es, d_states, ldw * es, n * es, (int64_t)steps * 2, hipMemcpyDeviceToHost, s));
-            if (iters_out)
-                HIP_TRY(h, copy_rows(iters_out, ld * 4, d_iters, ldw * 4, n * 4, steps, hipMemcpyDeviceToHost, s));
-            if (sequences_out)
-                HIP_TRY(h, copy_rows(sequences_out, ld * es, d_seq, ldw * es, n * es, (int64_t)steps * H * I,
-                                     hipMemcpyDeviceToHost, s));
-            if (d_status)
-                HIP_TRY(h, copy_rows(q->status, ld * 4, d_status, ldw * 4, n * 4, steps, hipMemcpyDeviceToHost, s));
-            if (d_rin)
-                HIP_TRY(h, copy_rows(q->residual_in, ld * 8, d_rin, ldw * 8, n * 8, steps, hipMemcpyDeviceToHost, s));
-            if (d_rout)
-                HIP_TRY(h, copy_rows(q->residual_out, ld * 8, d_rout, ldw * 8, n * 8, steps, hipMemcpyDeviceToHost, s));
-            HIP_TRY(h, hipStreamSynchronize(s));
+            rc = unstage_steps(h, g, d, n, s);
+            if (rc) return rc;
         }
         rc = order.end();
         if (rc) return rc;
@@ -1630,25 +1596,20 @@ static int rollout_newton_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const 
     return guarded(h, [&]() -> int {
         int rc = check_common(h, p, true);
         if (rc) return rc;
-        if (p->dtype != TPC_MPC_F64)
-            return fail(h, TPC_MPC_ERR_BAD_ARG, "tpc_mpc_rollout_newton is fp64 only: p->dtype must be TPC_MPC_F64");
+        if (p->dtype != TPC_MPC_F64) return fp64_only(h, "tpc_mpc_rollout_newton");
         rc = check_general_io(h, io, mem);
+        if (!rc) rc = check_polish(h, q);
+        if (!rc) rc = check_fallback(h, fallback);
+        if (!rc) rc = check_steps(h, steps);
         if (rc) return rc;
-        if (!q) return fail(h, TPC_MPC_ERR_BAD_ARG, "null polish struct");
-        if (!(q->tol > 0.0) || q->max_rounds < 0)
-            return fail(h, TPC_MPC_ERR_BAD_ARG, "polish needs tol > 0 and max_rounds >= 0");
-        if (fallback != TPC_MPC_NEWTON_FALLBACK_SOLVE && fallback != TPC_MPC_NEWTON_FALLBACK_NONE)
-            return fail(h, TPC_MPC_ERR_BAD_ARG, "unknown fallback %d", (int)fallback);
-        if (steps < 0 || steps > (1 << 24)) return fail(h, TPC_MPC_ERR_BAD_ARG, "need 0 <= steps <= 2^24");
         const bool solve = fallback == TPC_MPC_NEWTON_FALLBACK_SOLVE;
         if (h->host_only && solve)
             return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): the fallback solve runs on the device only; use TPC_MPC_NEWTON_FALLBACK_NONE");
         if (h->host_only && mem == TPC_MPC_DEVICE)
             return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): HOST memory only");
         if (io->n == 0 || steps == 0) { if (flags_out) *flags_out = 0; return TPC_MPC_OK; }
-        if (!io->A || !io->B || !io->C || !io->Q || !io->R || !io->lower || !io->upper || !io->x0 ||
-            !io->targets || !controls_out)
-            return fail(h, TPC_MPC_ERR_BAD_ARG, "null batch pointer");
+        rc = check_model(h, io, controls_out != nullptr);
+        if (rc) return rc;
         const int I = io->inputs, H = p->horizon;
         const int64_t n = io->n, ld = io->ld;
         // the working set: a copy of the model, then x0, targets, controls and v AS GIVEN (what the fallback restarts
@@ -1738,46 +1699,17 @@ static int rollout_newton_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const 
         uint32_t* d_words = (uint32_t*)(w + o_words);   // [0] the fallback's count, [1] phase 1's flags
         HIP_TRY(h, hipMemsetAsync(d_words, 0, 8, s));
 
-        // HOST mode: new_last_targets in, and the per-step outputs, go through the staging buffer (as rollout_impl)
-        const void* d_nlt = new_last_targets;
-        int64_t ld_nlt = ld, ld_out = ld;
-        char *d_ctrl = (char*)controls_out, *d_states = (char*)states_out, *d_seq = (char*)sequences_out;
-        int32_t *d_iters = iters_out, *d_status = q->status;
-        char *d_rin = (char*)q->residual_in, *d_rout = (char*)q->residual_out;
-        const void* d_dist = plant_d ? plant->disturbance : nullptr;
-        int64_t ld_dist = plant_d ? plant->ld_d : 0;
-        if (host) {
-            const int64_t s_nlt = 0, s_ctrl = s_nlt + pad256((int64_t)steps * 2 * ldw * 8);
-            const int64_t s_states = s_ctrl + pad256((int64_t)steps * I * ldw * 8);
-            const int64_t s_iters = s_states + pad256((int64_t)steps * 2 * ldw * 8);
-            const int64_t s_seq = s_iters + pad256((int64_t)steps * ldw * 4);
-            const int64_t s_status = s_seq + (sequences_out ? pad256((int64_t)steps * H * I * ldw * 8) : 0);
-            const int64_t s_rin = s_status + (d_status ? pad256((int64_t)steps * ldw * 4) : 0);
-            const int64_t s_rout = s_rin + (d_rin ? pad256((int64_t)steps * ldw * 8) : 0);
-            const int64_t s_dist = s_rout + (d_rout ? pad256((int64_t)steps * ldw * 8) : 0);
-            const int64_t s_end = s_dist + (plant_d ? pad256((int64_t)steps * 2 * ldw * 8) : 0);
-            rc = ensure(h, &h->stage, &h->stage_bytes, s_end);
-            if (rc) return rc;
-            char* b = (char*)h->stage;
-            if (new_last_targets) {
-                HIP_TRY(h, copy_rows(b + s_nlt, ldw * 8, new_last_targets, ld * 8, n * 8, (int64_t)steps * 2,
-                                     hipMemcpyHostToDevice, s));
-                d_nlt = b + s_nlt;
-            }
-            if (plant_d) {
-                HIP_TRY(h, copy_rows(b + s_dist, ldw * 8, plant->disturbance, plant->ld_d * 8, n * 8, (int64_t)steps * 2,
-                                     hipMemcpyHostToDevice, s));
-                d_dist = b + s_dist; ld_dist = ldw;
-            }
-            ld_nlt = ld_out = ldw;
-            d_ctrl = b + s_ctrl;
-            d_states = states_out ? b + s_states : nullptr;
-            d_iters = iters_out ? (int32_t*)(b + s_iters) : nullptr;
-            d_seq = sequences_out ? b + s_seq : nullptr;
-            if (d_status) d_status = (int32_t*)(b + s_status);
-            if (d_rin) d_rin = b + s_rin;
-            if (d_rout) d_rout = b + s_rout;
-        }
+        // the per-step arrays: the caller's (g), and what the kernels take for them (d)
+        const StepArrays g = step_arrays(io, H, steps, 8, new_last_targets, plant, controls_out, states_out, iters_out,
+                                         sequences_out, q);
+        StepArrays d;
+        rc = stage_steps(h, g, host, n, s, &d);
+        if (rc) return rc;
+        const void *d_nlt = d.in[0], *d_dist = d.in[1];
+        void *d_ctrl = d.out[kStepCtrl], *d_states = d.out[kStepStates], *d_seq = d.out[kStepSeq];
+        void *d_rin = d.out[kStepRin], *d_rout = d.out[kStepRout];
+        int32_t *d_iters = (int32_t*)d.out[kStepIters], *d_status = (int32_t*)d.out[kStepStatus];
+        const int64_t ld_nlt = d.ld_nlt, ld_out = d.ld_out, ld_dist = d.ld_d;
 
         bind(w, ldw);
         a.r.ld_out = ld_out; a.r.ld_nlt = ld_nlt;
@@ -1872,21 +1804,8 @@ static int rollout_newton_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const 
         if (io->v_inout) HIP_TRY(h, copy_rows(io->v_inout, ld * 8, d_vfinal, ldw * 8, n * 8, H * I, out_kind, s));
         if (first_unverified) HIP_TRY(h, hipMemcpyAsync(first_unverified, d_fu, (size_t)n * 4, out_kind, s));
         if (host) {
-            HIP_TRY(h, copy_rows(controls_out, ld * 8, d_ctrl, ldw * 8, n * 8, (int64_t)steps * I, hipMemcpyDeviceToHost, s));
-            if (states_out)
-                HIP_TRY(h, copy_rows(states_out, ld * 8, d_states, ldw * 8, n * 8, (int64_t)steps * 2, hipMemcpyDeviceToHost, s));
-            if (iters_out)
-                HIP_TRY(h, copy_rows(iters_out, ld * 4, d_iters, ldw * 4, n * 4, steps, hipMemcpyDeviceToHost, s));
-            if (sequences_out)
-                HIP_TRY(h, copy_rows(sequences_out, ld * 8, d_seq, ldw * 8, n * 8, (int64_t)steps * H * I,
-                                     hipMemcpyDeviceToHost, s));
-            if (d_status)
-                HIP_TRY(h, copy_rows(q->status, ld * 4, d_status, ldw * 4, n * 4, steps, hipMemcpyDeviceToHost, s));
-            if (d_rin)
-                HIP_TRY(h, copy_rows(q->residual_in, ld * 8, d_rin, ldw * 8, n * 8, steps, hipMemcpyDeviceToHost, s));
-            if (d_rout)
-                HIP_TRY(h, copy_rows(q->residual_out, ld * 8, d_rout, ldw * 8, n * 8, steps, hipMemcpyDeviceToHost, s));
-            HIP_TRY(h, hipStreamSynchronize(s));
+            rc = unstage_steps(h, g, d, n, s);
+            if (rc) return rc;
         }
         rc = order.end();
         if (rc) return rc;
@@ -1921,21 +1840,18 @@ static int compact_exact_impl(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t
         int rc = check_common(h, p, true);
         if (rc) return rc;
         if (p->dtype != TPC_MPC_F64)
-            return fail(h, TPC_MPC_ERR_BAD_ARG, "%s is fp64 only: p->dtype must be TPC_MPC_F64",
-                        warm   ? "tpc_mpc_solve_batch_compact_exact_from"
-                        : rows ? "tpc_mpc_solve_batch_compact_exact_rows"
-                               : "tpc_mpc_solve_batch_compact_exact");
+            return fp64_only(h, warm   ? "tpc_mpc_solve_batch_compact_exact_from"
+                                : rows ? "tpc_mpc_solve_batch_compact_exact_rows"
+                                       : "tpc_mpc_solve_batch_compact_exact");
         if (!rows) {
             rc = check_compact_model(h, p);
             if (rc) return rc;
         }
         if (n < 0 || n > 0x7fffffffll) return fail(h, TPC_MPC_ERR_BAD_ARG, "need 0 <= n < 2^31");
         if (mem != TPC_MPC_HOST && mem != TPC_MPC_DEVICE) return fail(h, TPC_MPC_ERR_BAD_ARG, "bad memory kind");
-        if (!q) return fail(h, TPC_MPC_ERR_BAD_ARG, "null polish struct");
-        if (!(q->tol > 0.0) || q->max_rounds < 0)
-            return fail(h, TPC_MPC_ERR_BAD_ARG, "polish needs tol > 0 and max_rounds >= 0");
-        if (fallback != TPC_MPC_NEWTON_FALLBACK_SOLVE && fallback != TPC_MPC_NEWTON_FALLBACK_NONE)
-            return fail(h, TPC_MPC_ERR_BAD_ARG, "unknown fallback %d", (int)fallback);
+        rc = check_polish(h, q);
+        if (!rc) rc = check_fallback(h, fallback);
+        if (rc) return rc;
         const bool solve = fallback == TPC_MPC_NEWTON_FALLBACK_SOLVE;
         if (h->host_only && solve)
             return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): the fallback solve runs on the device only; use TPC_MPC_NEWTON_FALLBACK_NONE");
@@ -2141,9 +2057,8 @@ static int compact_exact_backward_impl(tpc_mpc_handle h, const tpc_mpc_params* p
         int rc = check_common(h, p, true);
         if (rc) return rc;
         if (p->dtype != TPC_MPC_F64)
-            return fail(h, TPC_MPC_ERR_BAD_ARG, "%s is fp64 only: p->dtype must be TPC_MPC_F64",
-                        rows ? "tpc_mpc_solve_batch_compact_exact_rows_backward"
-                             : "tpc_mpc_solve_batch_compact_exact_backward");
+            return fp64_only(h, rows ? "tpc_mpc_solve_batch_compact_exact_rows_backward"
+                                     : "tpc_mpc_solve_batch_compact_exact_backward");
         if (!rows) {
             rc = check_compact_model(h, p);
             if (rc) return rc;
@@ -2299,8 +2214,7 @@ int tpc_mpc_rollout_plant(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_m
     int rc = guarded(h, [&]() -> int {
         int rc = check_common(h, p, true);
         if (rc) return rc;
-        if (p->dtype != TPC_MPC_F64)
-            return fail(h, TPC_MPC_ERR_BAD_ARG, "tpc_mpc_rollout_plant is fp64 only: p->dtype must be TPC_MPC_F64");
+        if (p->dtype != TPC_MPC_F64) return fp64_only(h, "tpc_mpc_rollout_plant");
         rc = check_general_io(h, io, mem);
         if (rc) return rc;
         rc = check_plant(h, io, plant);
@@ -2326,8 +2240,7 @@ static int rollout_backward_impl(tpc_mpc_handle h, const tpc_mpc_params* p, cons
     return guarded(h, [&]() -> int {
         int rc = check_common(h, p, true);
         if (rc) return rc;
-        if (p->dtype != TPC_MPC_F64)
-            return fail(h, TPC_MPC_ERR_BAD_ARG, "%s is fp64 only: p->dtype must be TPC_MPC_F64", name);
+        if (p->dtype != TPC_MPC_F64) return fp64_only(h, name);
         rc = check_general_io(h, io, mem);
         if (rc) return rc;
         if (!g) return fail(h, TPC_MPC_ERR_BAD_ARG, "null gradient struct");
@@ -2340,14 +2253,15 @@ static int rollout_backward_impl(tpc_mpc_handle h, const tpc_mpc_params* p, cons
             if (pg->ddisturbance && plant->ld_d != 0 && plant->ld_d < io->n)
                 return fail(h, TPC_MPC_ERR_BAD_ARG, "ddisturbance needs ld_d >= n (or 0: the io's ld)");
         }
-        if (steps < 0 || steps > (1 << 24)) return fail(h, TPC_MPC_ERR_BAD_ARG, "need 0 <= steps <= 2^24");
+        rc = check_steps(h, steps);
+        if (rc) return rc;
         if (g->dnew_last_targets && !new_last_targets)
             return fail(h, TPC_MPC_ERR_BAD_ARG, "dnew_last_targets asked for without new_last_targets");
         if (h->host_only && mem == TPC_MPC_DEVICE)
             return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): the backward pass takes HOST memory only");
         if (io->n == 0 || steps == 0) { if (flags_out) *flags_out = 0; return TPC_MPC_OK; }
-        if (!io->A || !io->B || !io->C || !io->Q || !io->R || !io->lower || !io->upper || !io->x0 || !io->targets)
-            return fail(h, TPC_MPC_ERR_BAD_ARG, "null batch pointer");
+        rc = check_model(h, io);
+        if (rc) return rc;
         if (!g->sequences || !g->states) return fail(h, TPC_MPC_ERR_BAD_ARG, "null sequences / states");
         const int I = io->inputs, H = p->horizon;
         const int64_t n = io->n, S = steps;
@@ -2363,87 +2277,43 @@ static int rollout_backward_impl(tpc_mpc_handle h, const tpc_mpc_params* p, cons
         void* dst[kOut] = {g->dA, g->dB, g->dC, g->dQ, g->dR, g->dlower, g->dupper, g->dx0, g->dtargets,
                            g->dnew_last_targets, g->kkt_residual, sep ? pg->dA : nullptr, sep ? pg->dB : nullptr,
                            sep ? pg->dC : nullptr, use_plant ? pg->ddisturbance : nullptr};
-        const int64_t comps[kIn + kOut] = {4, 2 * I, 2, 2, I, I, I, 2, 2 * H, 2 * S, S * H * I, 2 * S, S * I, 2 * S,
-                                           4, 2 * I, 2,
-                                           4, 2 * I, 2, 2, I, I, I, 2, 2 * H, 2 * S, 1, 4, 2 * I, 2, 2 * S};
-        grad::RollPlant pl;
-        std::memset(&pl, 0, sizeof(pl));
-        auto bind = [&](grad::RollArgs* a, const void* const* in, void* const* out, int64_t ld_d) {
-            a->A = (const double*)in[0]; a->B = (const double*)in[1]; a->C = (const double*)in[2];
-            a->Q = (const double*)in[3]; a->R = (const double*)in[4]; a->lo = (const double*)in[5];
-            a->hi = (const double*)in[6]; a->x0 = (const double*)in[7]; a->targets = (const double*)in[8];
-            a->nlt = (const double*)in[9]; a->seq = (const double*)in[10]; a->states = (const double*)in[11];
-            a->gu = (const double*)in[12]; a->gx = (const double*)in[13];
-            a->dA = (double*)out[0]; a->dB = (double*)out[1]; a->dC = (double*)out[2]; a->dQ = (double*)out[3];
-            a->dR = (double*)out[4]; a->dlo = (double*)out[5]; a->dhi = (double*)out[6]; a->dx0 = (double*)out[7];
-            a->dtargets = (double*)out[8]; a->dnlt = (double*)out[9]; a->kkt = (double*)out[10];
-            pl.separate = sep ? 1 : 0;
-            pl.A = sep ? (const double*)in[14] : a->A; pl.B = sep ? (const double*)in[15] : a->B;
-            pl.C = sep ? (const double*)in[16] : a->C;
-            pl.dA = (double*)out[11]; pl.dB = (double*)out[12]; pl.dC = (double*)out[13]; pl.dd = (double*)out[14];
-            pl.ld_d = ld_d;
-        };
-        grad::RollArgs a;
-        std::memset(&a, 0, sizeof(a));
-        a.n = n;
-        a.steps = steps;
-        if (h->host_only) {   // on the calling thread, straight from and into the caller's arrays
-            a.ld = io->ld;
-            bind(&a, src, dst, ld_dd);
-            const uint32_t f = use_plant ? rollout_plant_grad_host(I, H, a, pl) : rollout_grad_host(I, H, a);
-            if (flags_out) *flags_out = f;
-            return TPC_MPC_OK;
-        }
-        HIP_TRY(h, hipSetDevice(h->device));
-        hipStream_t s = (hipStream_t)stream;
-        StreamOrderScope order(h, s);
-        rc = order.begin();
-        if (rc) return rc;
-        rc = ensure(h, &h->grad_ws, &h->grad_ws_bytes, pad256(grad_scratch_bytes(I, H, n)));
-        if (rc) return rc;
-        const int64_t lds = (n + 63) / 64 * 64;
-        int64_t off[kIn + kOut] = {0};
-        if (mem == TPC_MPC_DEVICE) {
-            a.ld = io->ld;
-            bind(&a, src, dst, ld_dd);
-        } else {
-            // HOST arrays: every component row copied on its own (n elements, never ld), as tpc_mpc_solve_batch_general;
-            // only the arrays given are staged
-            int64_t total = 0;
-            for (int c = 0; c < kIn + kOut; ++c) {
-                const bool given = c < kIn ? src[c] != nullptr : dst[c - kIn] != nullptr;
-                off[c] = total;
-                if (given) total += pad256(comps[c] * lds * 8);
-            }
-            rc = ensure(h, &h->stage, &h->stage_bytes, total);
-            if (rc) return rc;
-            char* b = (char*)h->stage;
-            const void* sin[kIn];
-            void* sout[kOut];
-            for (int c = 0; c < kIn; ++c) {
-                sin[c] = src[c] ? b + off[c] : nullptr;
-                if (src[c])
-                    HIP_TRY(h, copy_rows(b + off[c], lds * 8, src[c], io->ld * 8, n * 8, comps[c], hipMemcpyHostToDevice, s));
-            }
-            for (int c = 0; c < kOut; ++c) sout[c] = dst[c] ? b + off[kIn + c] : nullptr;
-            a.ld = lds;
-            bind(&a, sin, sout, lds);
-        }
-        HIP_TRY(h, hipMemsetAsync(h->ws_words + 1, 0, sizeof(uint32_t), s));
-        hipError_t e = use_plant ? rollout_plant_grad(I, H, a, pl, h->grad_ws, h->ws_words + 1, s)
-                                 : rollout_grad(I, H, a, h->grad_ws, h->ws_words + 1, s);
-        if (e != hipSuccess) return hip_fail(h, e, "kernel launch");
-        if (mem == TPC_MPC_HOST) {
-            const char* b = (const char*)h->stage;
-            for (int c = 0; c < kOut; ++c)
-                if (dst[c])
-                    HIP_TRY(h, copy_rows(dst[c], (c == 14 ? ld_dd : io->ld) * 8, b + off[kIn + c], lds * 8, n * 8,
-                                         comps[kIn + c], hipMemcpyDeviceToHost, s));
-            HIP_TRY(h, hipStreamSynchronize(s));
-        }
-        rc = order.end();
-        if (rc) return rc;
-        return finish_flags(h, flags_out, s);
+        const int64_t rows[kIn + kOut] = {4, 2 * I, 2, 2, I, I, I, 2, 2 * H, 2 * S, S * H * I, 2 * S, S * I, 2 * S,
+                                          4, 2 * I, 2,
+                                          4, 2 * I, 2, 2, I, I, I, 2, 2 * H, 2 * S, 1, 4, 2 * I, 2, 2 * S};
+        int64_t dst_ld[kOut] = {0};
+        dst_ld[14] = ld_dd;
+        StagedExtra x;
+        x.dst_ld = dst_ld;
+        const bool staged = !h->host_only && mem == TPC_MPC_HOST;
+        return staged_run(h, io, mem, stream, flags_out, grad_scratch_bytes(I, H, n), src, dst, rows,
+                          [&](int64_t ld, const void* const* in, void* const* out, hipStream_t s, uint32_t* hf) {
+                              grad::RollArgs a;
+                              std::memset(&a, 0, sizeof(a));
+                              a.n = n; a.ld = ld; a.steps = steps;
+                              bind_model(&a, in);
+                              a.nlt = (const double*)in[9]; a.seq = (const double*)in[10];
+                              a.states = (const double*)in[11]; a.gu = (const double*)in[12];
+                              a.gx = (const double*)in[13];
+                              a.dA = (double*)out[0]; a.dB = (double*)out[1]; a.dC = (double*)out[2];
+                              a.dQ = (double*)out[3]; a.dR = (double*)out[4]; a.dlo = (double*)out[5];
+                              a.dhi = (double*)out[6]; a.dx0 = (double*)out[7]; a.dtargets = (double*)out[8];
+                              a.dnlt = (double*)out[9]; a.kkt = (double*)out[10];
+                              if (!use_plant) {
+                                  if (hf) { *hf = rollout_grad_host(I, H, a); return hipSuccess; }
+                                  return rollout_grad(I, H, a, h->grad_ws, h->ws_words + 1, s);
+                              }
+                              grad::RollPlant pl;
+                              std::memset(&pl, 0, sizeof(pl));
+                              pl.separate = sep ? 1 : 0;
+                              pl.A = sep ? (const double*)in[14] : a.A; pl.B = sep ? (const double*)in[15] : a.B;
+                              pl.C = sep ? (const double*)in[16] : a.C;
+                              pl.dA = (double*)out[11]; pl.dB = (double*)out[12]; pl.dC = (double*)out[13];
+                              pl.dd = (double*)out[14];
+                              pl.ld_d = staged ? ld : ld_dd;
+                              if (hf) { *hf = rollout_plant_grad_host(I, H, a, pl); return hipSuccess; }
+                              return rollout_plant_grad(I, H, a, pl, h->grad_ws, h->ws_words + 1, s);
+                          },
+                          x);
     });
 }
 
@@ -2468,8 +2338,7 @@ int tpc_mpc_solve_batch_general_forward(tpc_mpc_handle h, const tpc_mpc_params* 
     return guarded(h, [&]() -> int {
         int rc = check_common(h, p, true);
         if (rc) return rc;
-        if (p->dtype != TPC_MPC_F64)
-            return fail(h, TPC_MPC_ERR_BAD_ARG, "tpc_mpc_solve_batch_general_forward is fp64 only: p->dtype must be TPC_MPC_F64");
+        if (p->dtype != TPC_MPC_F64) return fp64_only(h, "tpc_mpc_solve_batch_general_forward");
         rc = check_general_io(h, io, mem);
         if (rc) return rc;
         if (!t) return fail(h, TPC_MPC_ERR_BAD_ARG, "null tangent struct");
@@ -2478,8 +2347,8 @@ int tpc_mpc_solve_batch_general_forward(tpc_mpc_handle h, const tpc_mpc_params* 
         if (h->host_only && mem == TPC_MPC_DEVICE)
             return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): the forward pass takes HOST memory only");
         if (io->n == 0) { if (flags_out) *flags_out = 0; return TPC_MPC_OK; }
-        if (!io->A || !io->B || !io->C || !io->Q || !io->R || !io->lower || !io->upper || !io->x0 || !io->targets)
-            return fail(h, TPC_MPC_ERR_BAD_ARG, "null batch pointer");
+        rc = check_model(h, io);
+        if (rc) return rc;
         if (!controls || !tcontrols) return fail(h, TPC_MPC_ERR_BAD_ARG, "null controls / tcontrols");
         const int I = io->inputs, H = p->horizon, K = t->directions;
         const int64_t n = io->n;
@@ -2490,20 +2359,18 @@ int tpc_mpc_solve_batch_general_forward(tpc_mpc_handle h, const tpc_mpc_params* 
         const int64_t rows[21] = {4, 2 * I, 2, 2, I, I, I, 2, 2 * H, H * I,
                                   4 * K, 2 * I * K, 2 * K, 2 * K, I * K, I * K, I * K, 2 * K, 2 * H * K, 0,
                                   (int64_t)H * I * K};
-        return forward_run(h, io, mem, stream, flags_out, tangent_scratch_bytes(I, H, n, K, true), src, dst, rows, 20, 1,
-                           [&](int64_t ld, const void* const* in, void* const* out, hipStream_t s, uint32_t* hf) {
-                               tangent::Args a;
-                               std::memset(&a, 0, sizeof(a));
-                               a.n = n; a.ld = ld; a.K = K;
-                               a.A = (const double*)in[0]; a.B = (const double*)in[1]; a.C = (const double*)in[2];
-                               a.Q = (const double*)in[3]; a.R = (const double*)in[4]; a.lo = (const double*)in[5];
-                               a.hi = (const double*)in[6]; a.x0 = (const double*)in[7];
-                               a.targets = (const double*)in[8]; a.u = (const double*)in[9];
-                               a.t = bind_dirs(in + 10);
-                               a.tu = (double*)out[0];
-                               if (hf) { *hf = tangent_general_host(I, H, a); return hipSuccess; }
-                               return tangent_general(I, H, a, h->grad_ws, h->ws_words + 1, s);
-                           });
+        return staged_run(h, io, mem, stream, flags_out, tangent_scratch_bytes(I, H, n, K, true), src, dst, rows,
+                          [&](int64_t ld, const void* const* in, void* const* out, hipStream_t s, uint32_t* hf) {
+                              tangent::Args a;
+                              std::memset(&a, 0, sizeof(a));
+                              a.n = n; a.ld = ld; a.K = K;
+                              bind_model(&a, in);
+                              a.u = (const double*)in[9];
+                              a.t = bind_dirs(in + 10);
+                              a.tu = (double*)out[0];
+                              if (hf) { *hf = tangent_general_host(I, H, a); return hipSuccess; }
+                              return tangent_general(I, H, a, h->grad_ws, h->ws_words + 1, s);
+                          });
     });
 }
 
@@ -2516,8 +2383,7 @@ static int rollout_forward_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const
     return guarded(h, [&]() -> int {
         int rc = check_common(h, p, true);
         if (rc) return rc;
-        if (p->dtype != TPC_MPC_F64)
-            return fail(h, TPC_MPC_ERR_BAD_ARG, "%s is fp64 only: p->dtype must be TPC_MPC_F64", name);
+        if (p->dtype != TPC_MPC_F64) return fp64_only(h, name);
         rc = check_general_io(h, io, mem);
         if (rc) return rc;
         if (!t) return fail(h, TPC_MPC_ERR_BAD_ARG, "null tangent struct");
@@ -2532,7 +2398,8 @@ static int rollout_forward_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const
             if (pt->tdisturbance && plant->ld_d != 0 && plant->ld_d < io->n)
                 return fail(h, TPC_MPC_ERR_BAD_ARG, "tdisturbance needs ld_d >= n (or 0: the io's ld)");
         }
-        if (steps < 0 || steps > (1 << 24)) return fail(h, TPC_MPC_ERR_BAD_ARG, "need 0 <= steps <= 2^24");
+        rc = check_steps(h, steps);
+        if (rc) return rc;
         if (t->directions < 1 || (int64_t)t->directions * io->n > 0x7fffffffll)
             return fail(h, TPC_MPC_ERR_BAD_ARG, "need directions >= 1 and directions * n < 2^31");
         if (t->tnew_last_targets && !new_last_targets)
@@ -2540,8 +2407,8 @@ static int rollout_forward_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const
         if (h->host_only && mem == TPC_MPC_DEVICE)
             return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): the forward pass takes HOST memory only");
         if (io->n == 0 || steps == 0) { if (flags_out) *flags_out = 0; return TPC_MPC_OK; }
-        if (!io->A || !io->B || !io->C || !io->Q || !io->R || !io->lower || !io->upper || !io->x0 || !io->targets)
-            return fail(h, TPC_MPC_ERR_BAD_ARG, "null batch pointer");
+        rc = check_model(h, io);
+        if (rc) return rc;
         if (!sequences || !states || !tcontrols) return fail(h, TPC_MPC_ERR_BAD_ARG, "null sequences / states / tcontrols");
         const int I = io->inputs, H = p->horizon, K = t->directions;
         const int64_t n = io->n, S = steps;
@@ -2566,34 +2433,34 @@ static int rollout_forward_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const
                                        4 * K, 2 * I * K, 2 * K, 2 * K, I * K, I * K, I * K, 2 * K, 2 * H * K, 2 * S * K,
                                        4, 2 * I, 2, 4 * K, 2 * I * K, 2 * K, 2 * S * K,
                                        S * I * K, 2 * S * K};
-        return forward_run(h, io, mem, stream, flags_out, tangent_scratch_bytes(I, H, n, K, false), src, dst, rows, kIn, 2,
-                           [&](int64_t ld, const void* const* in, void* const* out, hipStream_t s, uint32_t* hf) {
-                               tangent::RollArgs a;
-                               std::memset(&a, 0, sizeof(a));
-                               a.n = n; a.ld = ld; a.steps = steps; a.K = K;
-                               a.A = (const double*)in[0]; a.B = (const double*)in[1]; a.C = (const double*)in[2];
-                               a.Q = (const double*)in[3]; a.R = (const double*)in[4]; a.lo = (const double*)in[5];
-                               a.hi = (const double*)in[6]; a.x0 = (const double*)in[7];
-                               a.targets = (const double*)in[8]; a.nlt = (const double*)in[9];
-                               a.seq = (const double*)in[10]; a.states = (const double*)in[11];
-                               a.t = bind_dirs(in + 12);
-                               a.tu = (double*)out[0]; a.tx = (double*)out[1];
-                               if (!use_plant) {
-                                   if (hf) { *hf = rollout_tangent_host(I, H, a); return hipSuccess; }
-                                   return rollout_tangent(I, H, a, h->grad_ws, h->ws_words + 1, s);
-                               }
-                               tangent::RollPlant pl;
-                               std::memset(&pl, 0, sizeof(pl));
-                               pl.A = sep ? (const double*)in[22] : a.A; pl.B = sep ? (const double*)in[23] : a.B;
-                               pl.C = sep ? (const double*)in[24] : a.C;
-                               pl.tA = sep ? (const double*)in[25] : a.t.tA; pl.tB = sep ? (const double*)in[26] : a.t.tB;
-                               pl.tC = sep ? (const double*)in[27] : a.t.tC;
-                               pl.td = (const double*)in[28];
-                               pl.ld_d = staged ? ld : ld_td;
-                               if (hf) { *hf = rollout_plant_tangent_host(I, H, a, pl); return hipSuccess; }
-                               return rollout_plant_tangent(I, H, a, pl, h->grad_ws, h->ws_words + 1, s);
-                           },
-                           src_ld);
+        StagedExtra x;
+        x.src_ld = src_ld;
+        return staged_run(h, io, mem, stream, flags_out, tangent_scratch_bytes(I, H, n, K, false), src, dst, rows,
+                          [&](int64_t ld, const void* const* in, void* const* out, hipStream_t s, uint32_t* hf) {
+                              tangent::RollArgs a;
+                              std::memset(&a, 0, sizeof(a));
+                              a.n = n; a.ld = ld; a.steps = steps; a.K = K;
+                              bind_model(&a, in);
+                              a.nlt = (const double*)in[9]; a.seq = (const double*)in[10];
+                              a.states = (const double*)in[11];
+                              a.t = bind_dirs(in + 12);
+                              a.tu = (double*)out[0]; a.tx = (double*)out[1];
+                              if (!use_plant) {
+                                  if (hf) { *hf = rollout_tangent_host(I, H, a); return hipSuccess; }
+                                  return rollout_tangent(I, H, a, h->grad_ws, h->ws_words + 1, s);
+                              }
+                              tangent::RollPlant pl;
+                              std::memset(&pl, 0, sizeof(pl));
+                              pl.A = sep ? (const double*)in[22] : a.A; pl.B = sep ? (const double*)in[23] : a.B;
+                              pl.C = sep ? (const double*)in[24] : a.C;
+                              pl.tA = sep ? (const double*)in[25] : a.t.tA; pl.tB = sep ? (const double*)in[26] : a.t.tB;
+                              pl.tC = sep ? (const double*)in[27] : a.t.tC;
+                              pl.td = (const double*)in[28];
+                              pl.ld_d = staged ? ld : ld_td;
+                              if (hf) { *hf = rollout_plant_tangent_host(I, H, a, pl); return hipSuccess; }
+                              return rollout_plant_tangent(I, H, a, pl, h->grad_ws, h->ws_words + 1, s);
+                          },
+                          x);
     });
 }
 
