@@ -15,13 +15,16 @@ from typing import Optional
 import numpy as np
 
 from . import capi
+from ._arrays import LAST, Arrays
 
-_NP = {capi.F64: np.float64, capi.F32: np.float32}
 COMPACT_PARAM_NAMES = capi.COMPACT_PARAM_NAMES   # the order of solve_batch_compact_exact_backward's "params"
+_I32 = np.int32
 
 
-def _is_torch(x) -> bool:
-    return type(x).__module__.startswith("torch")
+def _rows(I: int, H: int, steps: int = 0) -> dict:
+    """Rows of every component-major general-form array [rows, n], by the name its gradient / tangent goes by."""
+    return {"A": 4, "B": 2 * I, "C": 2, "Q": 2, "R": I, "lower": I, "upper": I, "x0": 2, "targets": 2 * H,
+            "new_last_targets": 2 * steps, "kkt_residual": 1, "Ap": 4, "Bp": 2 * I, "Cp": 2, "disturbance": 2 * steps}
 
 
 class MpcSolver:
@@ -79,6 +82,29 @@ class MpcSolver:
             else:
                 setattr(p, k, val)
         return p
+
+    # -- what every array-taking call shares --------------------------------------------------------
+    def _run(self, entry, p, ar, *args, want_flags=True, mem=True):
+        """entry(handle, &p, *args, &flags, [mem,] stream), then last_flags: the end of every batch call.
+        want_flags=False passes a null flags_out (a DEVICE call then stays asynchronous) and leaves last_flags at 0."""
+        flags = C.c_uint32(0)
+        where = (ar.mem, ar.stream) if mem else (ar.stream,)
+        self._check(entry(self._h, C.byref(p), *args, C.byref(flags) if want_flags else None, *where))
+        self.last_flags = flags.value
+
+    @staticmethod
+    def _general(A, R, inputs, dtype=np.float64):
+        """(Arrays, I) of a general-form call: n is A's last dimension, I the rows of R unless given"""
+        return Arrays(A, LAST, dtype), inputs or np.shape(R)[0]
+
+    @staticmethod
+    def _io(ar, I, H, model, controls=None, v_state=None, u0=None, iters=None, match="shape"):
+        """capi.GeneralIO of the nine model arrays (read), controls / v_state (updated in place) and the outputs u0 /
+        iters that ar.new made"""
+        A, B, Cc, Q, R, lower, upper, x0, targets = ar.read_rows(model, (4, 2 * I, 2, 2, I, I, I, 2, 2 * H), match)
+        return capi.GeneralIO(inputs=I, n=ar.n, ld=ar.n, A=A, B=B, C=Cc, Q=Q, R=R, lower=lower, upper=upper, x0=x0,
+                              targets=targets, controls_inout=ar.update(controls, H * I),
+                              v_inout=ar.update(v_state, H * I), u0=ar.addr(u0), iters=ar.addr(iters))
 
     # -- measurement ------------------------------------------------------------------------------
     def set_profiling(self, enable: bool = True):
@@ -145,15 +171,11 @@ class MpcSolver:
         if hint is None:
             self._check(self._lib.tpc_mpc_x_set_work_hint(self._h, None, 0, capi.HOST))
             self._hint_ref = None
-        elif _is_torch(hint):
-            import torch
-            if not (hint.is_cuda and hint.dtype == torch.int32 and hint.is_contiguous()):
-                raise ValueError("a device hint must be a contiguous int32 CUDA tensor")
-            self._hint_ref = hint
-            self._check(self._lib.tpc_mpc_x_set_work_hint(self._h, hint.data_ptr(), hint.numel(), capi.DEVICE))
         else:
-            h = np.ascontiguousarray(hint, dtype=np.int32)
-            self._check(self._lib.tpc_mpc_x_set_work_hint(self._h, h.ctypes.data, h.shape[0], capi.HOST))
+            ar = Arrays(hint, None, _I32)
+            self._check(self._lib.tpc_mpc_x_set_work_hint(self._h, ar.read(hint, match="length"), ar.n, ar.mem))
+            if ar.mem == capi.DEVICE:
+                self._hint_ref = hint
 
     QUEUE_KEYS = ("lambda", "table", "hint")
 
@@ -173,37 +195,17 @@ class MpcSolver:
                             want_flags: bool = True, out=None, **over):
         """n independent mpcControllerTobi calls.  Returns (front, rear[, iters])."""
         p = self._params(**over)
-        if _is_torch(v):
-            import torch
-            tdt = torch.float64 if p.dtype == capi.F64 else torch.float32
-            n = v.numel()
-            for t in (v, delta_y, delta_phi):
-                if not (t.is_cuda and t.dtype == tdt and t.is_contiguous() and t.numel() == n):
-                    raise ValueError("device batch arrays must be contiguous CUDA tensors of the solver dtype")
-            if out is None:
-                front, rear = torch.empty_like(v), torch.empty_like(v)
-            else:
-                front, rear = out
-            iters = torch.empty(n, dtype=torch.int32, device=v.device) if want_iters else None
-            flags = C.c_uint32(0)
-            stream = torch.cuda.current_stream(v.device).cuda_stream
-            self._check(self._lib.tpc_mpc_solve_batch_compact(
-                self._h, C.byref(p), n, v.data_ptr(), delta_y.data_ptr(), delta_phi.data_ptr(),
-                front.data_ptr(), rear.data_ptr(), iters.data_ptr() if want_iters else None,
-                C.byref(flags) if want_flags else None, capi.DEVICE, C.c_void_p(stream)))
-            self.last_flags = flags.value
+        ar = Arrays(v, None, p.dtype, like=True)
+        ins = ar.read_rows((v, delta_y, delta_phi), None, "length")
+        if out is None or ar.mem == capi.HOST:     # (a HOST call has always returned fresh arrays, whatever out= is)
+            front, rear = ar.new(), ar.new()
+            outs = (ar.addr(front), ar.addr(rear))
         else:
-            dt = _NP[p.dtype]
-            v, delta_y, delta_phi = (np.ascontiguousarray(a, dtype=dt) for a in (v, delta_y, delta_phi))
-            n = v.shape[0]
-            front, rear = np.empty(n, dtype=dt), np.empty(n, dtype=dt)
-            iters = np.empty(n, dtype=np.int32) if want_iters else None
-            flags = C.c_uint32(0)
-            self._check(self._lib.tpc_mpc_solve_batch_compact(
-                self._h, C.byref(p), n, v.ctypes.data, delta_y.ctypes.data, delta_phi.ctypes.data,
-                front.ctypes.data, rear.ctypes.data, iters.ctypes.data if want_iters else None,
-                C.byref(flags), capi.HOST, None))
-            self.last_flags = flags.value
+            front, rear = out
+            outs = (ar.update(front, match="length"), ar.update(rear, match="length"))
+        iters = ar.new(dtype=_I32) if want_iters else None
+        self._run(self._lib.tpc_mpc_solve_batch_compact, p, ar, ar.n, *ins, *outs, ar.addr(iters),
+                  want_flags=want_flags or ar.mem == capi.HOST)   # (a HOST call is synchronous: it always reports)
         return (front, rear, iters) if want_iters else (front, rear)
 
     def solve_batch_compact_exact(self, v, delta_y, delta_phi, tol: float = 1e-9, max_rounds: int = 16,
@@ -237,73 +239,25 @@ class MpcSolver:
         Its derivative is solve_batch_compact_exact_backward (autograd: mpc_compact_exact)."""
         p = self._params(**over)
         H = p.horizon
-        fb = capi.NEWTON_FALLBACKS[fallback]
-        rows_shape = (len(COMPACT_PARAM_NAMES), v.numel() if _is_torch(v) else np.shape(v)[0])
-        if _is_torch(v):
-            import torch
-            n = v.numel()
-            for t in (v, delta_y, delta_phi):
-                if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == n):
-                    raise ValueError("device batch arrays must be contiguous fp64 CUDA tensors")
-            if params_rows is not None and not (
-                    _is_torch(params_rows) and params_rows.is_cuda and params_rows.dtype == torch.float64
-                    and params_rows.is_contiguous() and tuple(params_rows.shape) == rows_shape):
-                raise ValueError(f"params_rows must be a contiguous fp64 CUDA tensor {list(rows_shape)}")
-            if start is not None and not (
-                    _is_torch(start) and start.is_cuda and start.dtype == torch.float64 and start.is_contiguous()
-                    and tuple(start.shape) == (2 * H, n)):
-                raise ValueError(f"start must be a contiguous fp64 CUDA tensor {[2 * H, n]}")
-
-            def new(dtype, rows=None):
-                t = torch.empty(n if rows is None else (rows, n),
-                                dtype=torch.float64 if dtype is np.float64 else torch.int32, device=v.device)
-                return t, t.data_ptr()
-            ptr = lambda t: t.data_ptr()
-            stream = C.c_void_p(torch.cuda.current_stream(v.device).cuda_stream)
-            mem = capi.DEVICE
-        else:
-            v, delta_y, delta_phi = (np.ascontiguousarray(a, dtype=np.float64) for a in (v, delta_y, delta_phi))
-            n = v.shape[0]
-            if params_rows is not None:
-                params_rows = np.ascontiguousarray(params_rows, dtype=np.float64)
-                if params_rows.shape != rows_shape:
-                    raise ValueError(f"params_rows must be an array {list(rows_shape)}")
-            if start is not None:
-                start = np.ascontiguousarray(start, dtype=np.float64)
-                if start.shape != (2 * H, n):
-                    raise ValueError(f"start must be an array {[2 * H, n]}")
-
-            def new(dtype, rows=None):
-                a = np.empty(n if rows is None else (rows, n), dtype=dtype)
-                return a, a.ctypes.data
-            ptr = lambda a: a.ctypes.data
-            stream = None
-            mem = capi.HOST
-        front, fp = new(np.float64)
-        rear, rp = new(np.float64)
-        seq, sqp = new(np.float64, 2 * H) if want_sequence else (None, None)
-        status, sp = new(np.int32) if want_status else (None, None)
-        fell, fbp = new(np.int32) if want_status and fallback != "none" else (None, None)
-        rin, rip = new(np.float64) if want_residuals else (None, None)
-        rout, rop = new(np.float64) if want_residuals else (None, None)
-        q = capi.Polish(tol=float(tol), max_rounds=int(max_rounds), reserved=0, status=sp, residual_in=rip,
-                        residual_out=rop)
-        flags = C.c_uint32(0)
-        fp_flags = C.byref(flags) if want_status or fallback != "none" else None
+        ar = Arrays(v)
+        rd = ar.read
+        vectors = ar.read_rows((v, delta_y, delta_phi), None, "length")
+        front, rear = ar.new(), ar.new()
+        seq = ar.new(2 * H) if want_sequence else None
+        status = ar.new(dtype=_I32) if want_status else None
+        fell = ar.new(dtype=_I32) if want_status and fallback != "none" else None
+        rin, rout = (ar.new(), ar.new()) if want_residuals else (None, None)
+        q = capi.Polish(tol=float(tol), max_rounds=int(max_rounds), reserved=0, status=ar.addr(status),
+                        residual_in=ar.addr(rin), residual_out=ar.addr(rout))
         if start is not None:
-            self._check(self._lib.tpc_mpc_solve_batch_compact_exact_from(
-                self._h, C.byref(p), n, ptr(v), ptr(delta_y), ptr(delta_phi),
-                None if params_rows is None else ptr(params_rows), ptr(start), C.byref(q), fb, fp, rp, sqp, fbp,
-                fp_flags, mem, stream))
-        elif params_rows is None:
-            self._check(self._lib.tpc_mpc_solve_batch_compact_exact(
-                self._h, C.byref(p), n, ptr(v), ptr(delta_y), ptr(delta_phi), C.byref(q), fb, fp, rp, sqp, fbp,
-                fp_flags, mem, stream))
+            entry = self._lib.tpc_mpc_solve_batch_compact_exact_from
+            model = (rd(params_rows, len(COMPACT_PARAM_NAMES)), rd(start, 2 * H))
+        elif params_rows is not None:
+            entry, model = self._lib.tpc_mpc_solve_batch_compact_exact_rows, (rd(params_rows, len(COMPACT_PARAM_NAMES)),)
         else:
-            self._check(self._lib.tpc_mpc_solve_batch_compact_exact_rows(
-                self._h, C.byref(p), n, ptr(v), ptr(delta_y), ptr(delta_phi), ptr(params_rows), C.byref(q), fb, fp,
-                rp, sqp, fbp, fp_flags, mem, stream))
-        self.last_flags = flags.value
+            entry, model = self._lib.tpc_mpc_solve_batch_compact_exact, ()
+        self._run(entry, p, ar, ar.n, *vectors, *model, C.byref(q), capi.NEWTON_FALLBACKS[fallback], ar.addr(front),
+                  ar.addr(rear), ar.addr(seq), ar.addr(fell), want_flags=want_status or fallback != "none")
         out = (front, rear) + ((seq,) if want_sequence else ()) + (status, fell)
         return out + ((rin, rout) if want_residuals else ())
 
@@ -330,65 +284,22 @@ class MpcSolver:
         unknown = set(want) - set(self.COMPACT_GRAD_NAMES)
         if unknown:
             raise ValueError(f"unknown gradient names {sorted(unknown)}")
-        if _is_torch(v):
-            import torch
-            n = v.numel()
-
-            def ptr(t, rows=None, dtype=torch.float64):
-                if t is None:
-                    return None
-                shape = (n,) if rows is None else (rows, n)
-                if not (t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape):
-                    raise ValueError(f"expected a contiguous {dtype} CUDA tensor {list(shape)}")
-                return t.data_ptr()
-
-            def new(shape):
-                t = torch.empty(shape, dtype=torch.float64, device=v.device)
-                return t, t.data_ptr()
-            i32 = torch.int32
-            stream = C.c_void_p(torch.cuda.current_stream(v.device).cuda_stream)
-            mem = capi.DEVICE
-        else:
-            v = np.ascontiguousarray(v, dtype=np.float64)
-            n = v.shape[0]
-            keep = []
-
-            def ptr(a, rows=None, dtype=np.float64):
-                if a is None:
-                    return None
-                a = np.ascontiguousarray(a, dtype=dtype)
-                if a.shape != ((n,) if rows is None else (rows, n)):
-                    raise ValueError(f"expected an array {[n] if rows is None else [rows, n]}")
-                keep.append(a)
-                return a.ctypes.data
-
-            def new(shape):
-                a = np.empty(shape, dtype=np.float64)
-                return a, a.ctypes.data
-            i32 = np.int32
-            stream = None
-            mem = capi.HOST
-        shapes = {"v": n, "delta_y": n, "delta_phi": n, "params": len(COMPACT_PARAM_NAMES),
-                  "params_rows": (len(COMPACT_PARAM_NAMES), n), "kkt_residual": n}
-        out, optr = {}, {}
-        for k in self.COMPACT_GRAD_NAMES:
-            out[k], optr[k] = new(shapes[k]) if k in want else (None, None)
-        g = capi.CompactGrad(grad_front=ptr(grad_front), grad_rear=ptr(grad_rear),
-                             grad_sequence=ptr(grad_sequence, 2 * H), dv=optr["v"], ddelta_y=optr["delta_y"],
-                             ddelta_phi=optr["delta_phi"], dparams_rows=optr["params_rows"], dparams=optr["params"],
-                             kkt_residual=optr["kkt_residual"])
-        flags = C.c_uint32(0)
+        ar = Arrays(v)
+        NP = len(COMPACT_PARAM_NAMES)
+        out = {k: ar.new(NP, per_instance=False) if k == "params" else ar.new(NP) if k == "params_rows" else ar.new()
+               for k in self.COMPACT_GRAD_NAMES if k in want}
+        to = {k: ar.addr(a) for k, a in out.items()}
+        g = capi.CompactGrad(grad_front=ar.read(grad_front), grad_rear=ar.read(grad_rear),
+                             grad_sequence=ar.read(grad_sequence, 2 * H), dv=to.get("v"), ddelta_y=to.get("delta_y"),
+                             ddelta_phi=to.get("delta_phi"), dparams_rows=to.get("params_rows"),
+                             dparams=to.get("params"), kkt_residual=to.get("kkt_residual"))
         if params_rows is None:
-            self._check(self._lib.tpc_mpc_solve_batch_compact_exact_backward(
-                self._h, C.byref(p), n, ptr(v), ptr(delta_y), ptr(delta_phi), ptr(sequence, 2 * H),
-                ptr(status, dtype=i32), C.byref(g), C.byref(flags) if want_flags else None, mem, stream))
+            entry, rows = self._lib.tpc_mpc_solve_batch_compact_exact_backward, ()
         else:
-            self._check(self._lib.tpc_mpc_solve_batch_compact_exact_rows_backward(
-                self._h, C.byref(p), n, ptr(v), ptr(delta_y), ptr(delta_phi),
-                ptr(params_rows, len(COMPACT_PARAM_NAMES)), ptr(sequence, 2 * H), ptr(status, dtype=i32), C.byref(g),
-                C.byref(flags) if want_flags else None, mem, stream))
-        self.last_flags = flags.value
-        return {k: a for k, a in out.items() if a is not None}
+            entry, rows = self._lib.tpc_mpc_solve_batch_compact_exact_rows_backward, (ar.read(params_rows, NP),)
+        self._run(entry, p, ar, ar.n, ar.read(v), ar.read(delta_y), ar.read(delta_phi), *rows,
+                  ar.read(sequence, 2 * H), ar.read(status, dtype=_I32), C.byref(g), want_flags=want_flags)
+        return out
 
     def solve_batch_compact_mixed(self, horizons, v, delta_y, delta_phi, want_iters: bool = False, **over):
         """Mixed-horizon batch (BASELINE config 5): instance k is solved with horizon horizons[k]
@@ -396,38 +307,12 @@ class MpcSolver:
         bin, results back in the caller's order).  Arrays as in solve_batch_compact; `horizons` is an
         integer array/tensor of the same length."""
         p = self._params(**over)
-        flags = C.c_uint32(0)
-        if _is_torch(v):
-            import torch
-            tdt = torch.float64 if p.dtype == capi.F64 else torch.float32
-            n = v.numel()
-            for t in (v, delta_y, delta_phi):
-                if not (t.is_cuda and t.dtype == tdt and t.is_contiguous() and t.numel() == n):
-                    raise ValueError("device batch arrays must be contiguous CUDA tensors of the solver dtype")
-            hz = torch.as_tensor(horizons, device=v.device).to(torch.int32).contiguous()
-            if hz.numel() != n:
-                raise ValueError("horizons must have one entry per instance")
-            front, rear = torch.empty_like(v), torch.empty_like(v)
-            iters = torch.empty(n, dtype=torch.int32, device=v.device) if want_iters else None
-            stream = torch.cuda.current_stream(v.device).cuda_stream
-            self._check(self._lib.tpc_mpc_solve_batch_compact_mixed(
-                self._h, C.byref(p), n, hz.data_ptr(), v.data_ptr(), delta_y.data_ptr(), delta_phi.data_ptr(),
-                front.data_ptr(), rear.data_ptr(), iters.data_ptr() if want_iters else None,
-                C.byref(flags), capi.DEVICE, C.c_void_p(stream)))
-        else:
-            dt = _NP[p.dtype]
-            v, delta_y, delta_phi = (np.ascontiguousarray(a, dtype=dt) for a in (v, delta_y, delta_phi))
-            n = v.shape[0]
-            hz = np.ascontiguousarray(horizons, dtype=np.int32)
-            if hz.shape[0] != n:
-                raise ValueError("horizons must have one entry per instance")
-            front, rear = np.empty(n, dtype=dt), np.empty(n, dtype=dt)
-            iters = np.empty(n, dtype=np.int32) if want_iters else None
-            self._check(self._lib.tpc_mpc_solve_batch_compact_mixed(
-                self._h, C.byref(p), n, hz.ctypes.data, v.ctypes.data, delta_y.ctypes.data, delta_phi.ctypes.data,
-                front.ctypes.data, rear.ctypes.data, iters.ctypes.data if want_iters else None,
-                C.byref(flags), capi.HOST, None))
-        self.last_flags = flags.value
+        ar = Arrays(v, None, p.dtype, like=True)
+        front, rear = ar.new(), ar.new()
+        iters = ar.new(dtype=_I32) if want_iters else None
+        self._run(self._lib.tpc_mpc_solve_batch_compact_mixed, p, ar, ar.n,
+                  ar.read(horizons, dtype=_I32, match="length", convert=True),
+                  *ar.read_rows((v, delta_y, delta_phi), None, "length"), ar.addr(front), ar.addr(rear), ar.addr(iters))
         return (front, rear, iters) if want_iters else (front, rear)
 
     # -- sharding over the GPUs of a node ----------------------------------------------------------
@@ -457,29 +342,17 @@ class MpcSolver:
         (tpc_mpc_solve_batch_compact_sharded_split).  split "block": the shard is the contiguous block of shard_range;
         "interleaved": instances rank, rank + world, ... compacted (shard_map).  Device tensors; returns full-size
         (front, rear) in instance order under either split."""
-        import torch
         p = self._params(**over)
-        tdt = torch.float64 if p.dtype == capi.F64 else torch.float32
         first, count, stride = C.c_int64(), C.c_int64(), C.c_int64()
         self._lib.tpc_mpc_shard_map(int(n_total), self.rank, self.world, capi.SPLITS[split], C.byref(first), C.byref(count),
                                     C.byref(stride))
-        for t in (v_shard, dy_shard, dphi_shard):
-            if not (t.is_cuda and t.dtype == tdt and t.is_contiguous() and t.numel() == count.value):
-                raise ValueError(f"shard arrays must be contiguous CUDA tensors of the solver dtype holding this "
-                                 f"rank's {count.value} instances (rank {self.rank} of {self.world}, n_total {n_total})")
-        if out is None:
-            front = torch.empty(n_total, dtype=tdt, device=v_shard.device)
-            rear = torch.empty(n_total, dtype=tdt, device=v_shard.device)
-        else:
-            front, rear = out
-        iters = torch.empty(v_shard.numel(), dtype=torch.int32, device=v_shard.device) if want_iters else None
-        flags = C.c_uint32(0)
-        stream = torch.cuda.current_stream(v_shard.device).cuda_stream
-        self._check(self._lib.tpc_mpc_solve_batch_compact_sharded_split(
-            self._h, C.byref(p), int(n_total), capi.SPLITS[split], v_shard.data_ptr(), dy_shard.data_ptr(), dphi_shard.data_ptr(),
-            front.data_ptr(), rear.data_ptr(), iters.data_ptr() if want_iters else None,
-            C.byref(flags) if want_flags else None, C.c_void_p(stream)))
-        self.last_flags = flags.value
+        ar = self._device_only(Arrays(v_shard, count.value, p.dtype))   # this rank's count.value instances
+        shard = [ar.read(t, match="length") for t in (v_shard, dy_shard, dphi_shard)]
+        front, rear = out if out is not None else (ar.new(int(n_total), per_instance=False),
+                                                   ar.new(int(n_total), per_instance=False))
+        iters = ar.new(dtype=_I32) if want_iters else None
+        self._run(self._lib.tpc_mpc_solve_batch_compact_sharded_split, p, ar, int(n_total), capi.SPLITS[split], *shard,
+                  front.data_ptr(), rear.data_ptr(), ar.addr(iters), want_flags=want_flags, mem=False)
         return (front, rear, iters) if want_iters else (front, rear)
 
     def shard_range(self, n_total: int):
@@ -521,28 +394,13 @@ class MpcSolver:
         """The general form sharded (tpc_mpc_solve_batch_general_sharded): FULL-size component-major CUDA tensors
         [rows, n_total] on every rank (only this rank's block of columns has to be filled); solves that block in
         place and all-gathers the rows of u0 over RCCL.  Returns the full u0[I, n_total] (and this rank's iters)."""
-        import torch
         p = self._params(**over)
-        H = p.horizon
-        tdt = torch.float64 if p.dtype == capi.F64 else torch.float32
-        n = A.shape[-1]
-        I = inputs or R.shape[0]
-
-        def ptr(t, rows):
-            if not (t.is_cuda and t.dtype == tdt and t.is_contiguous() and tuple(t.shape) == (rows, n)):
-                raise ValueError(f"expected contiguous CUDA tensor [{rows},{n}] of the solver dtype")
-            return t.data_ptr()
-        u0 = torch.empty((I, n), dtype=tdt, device=A.device)
-        iters = torch.zeros(n, dtype=torch.int32, device=A.device) if want_iters else None
-        io = capi.GeneralIO(inputs=I, n=n, ld=n, A=ptr(A, 4), B=ptr(B, 2 * I), C=ptr(Cc, 2), Q=ptr(Q, 2),
-                            R=ptr(R, I), lower=ptr(lower, I), upper=ptr(upper, I), x0=ptr(x0, 2),
-                            targets=ptr(targets, 2 * H), controls_inout=None, v_inout=None, u0=u0.data_ptr(),
-                            iters=iters.data_ptr() if want_iters else None)
-        flags = C.c_uint32(0)
-        stream = torch.cuda.current_stream(A.device).cuda_stream
-        self._check(self._lib.tpc_mpc_solve_batch_general_sharded(self._h, C.byref(p), C.byref(io), C.byref(flags),
-                                                                  C.c_void_p(stream)))
-        self.last_flags = flags.value
+        ar, I = self._general(A, R, inputs, p.dtype)
+        self._device_only(ar)
+        u0 = ar.new(I)
+        iters = ar.new(dtype=_I32).zero_() if want_iters else None
+        io = self._io(ar, I, p.horizon, (A, B, Cc, Q, R, lower, upper, x0, targets), u0=u0, iters=iters)
+        self._run(self._lib.tpc_mpc_solve_batch_general_sharded, p, ar, C.byref(io), mem=False)
         return (u0, iters) if want_iters else u0
 
     def solve_batch_general(self, A, B, Cc, Q, R, lower, upper, x0, targets, controls=None,
@@ -554,56 +412,11 @@ class MpcSolver:
         x0[2,n] targets[2H,n]; controls / v_state [H*I, n] are updated in place when given.
         Returns (u0[I,n][, iters])."""
         p = self._params(**over)
-        H = p.horizon
-        torch_mode = _is_torch(A)
-        if torch_mode:
-            import torch
-            tdt = torch.float64 if p.dtype == capi.F64 else torch.float32
-            n = A.shape[-1]
-            I = inputs or R.shape[0]
-
-            def ptr(t, rows):
-                if t is None:
-                    return None
-                if not (t.is_cuda and t.dtype == tdt and t.is_contiguous() and tuple(t.shape) == (rows, n)):
-                    raise ValueError(f"expected contiguous CUDA tensor [{rows},{n}] of the solver dtype")
-                return t.data_ptr()
-            u0 = torch.empty((I, n), dtype=tdt, device=A.device)
-            iters = torch.empty(n, dtype=torch.int32, device=A.device) if want_iters else None
-            stream = C.c_void_p(torch.cuda.current_stream(A.device).cuda_stream)
-            mem = capi.DEVICE
-            ip = iters.data_ptr() if want_iters else None
-            up = u0.data_ptr()
-        else:
-            dt = _NP[p.dtype]
-            A = np.ascontiguousarray(A, dtype=dt)
-            n = A.shape[-1]
-            I = inputs or np.asarray(R).shape[0]
-            keep = []
-
-            def ptr(a, rows):
-                if a is None:
-                    return None
-                if not (isinstance(a, np.ndarray) and a.dtype == dt and a.flags.c_contiguous and a.shape == (rows, n)):
-                    raise ValueError(f"expected C-contiguous ndarray [{rows},{n}] of the solver dtype")
-                keep.append(a)
-                return a.ctypes.data
-            B, Cc, Q, R, lower, upper, x0, targets = (np.ascontiguousarray(a, dtype=dt) for a in
-                                                      (B, Cc, Q, R, lower, upper, x0, targets))
-            u0 = np.empty((I, n), dtype=dt)
-            iters = np.empty(n, dtype=np.int32) if want_iters else None
-            stream = None
-            mem = capi.HOST
-            ip = iters.ctypes.data if want_iters else None
-            up = u0.ctypes.data
-        io = capi.GeneralIO(inputs=I, n=n, ld=n, A=ptr(A, 4), B=ptr(B, 2 * I), C=ptr(Cc, 2), Q=ptr(Q, 2),
-                            R=ptr(R, I), lower=ptr(lower, I), upper=ptr(upper, I), x0=ptr(x0, 2),
-                            targets=ptr(targets, 2 * H), controls_inout=ptr(controls, H * I),
-                            v_inout=ptr(v_state, H * I), u0=up, iters=ip)
-        flags = C.c_uint32(0)
-        self._check(self._lib.tpc_mpc_solve_batch_general(self._h, C.byref(p), C.byref(io),
-                                                          C.byref(flags), mem, stream))
-        self.last_flags = flags.value
+        ar, I = self._general(A, R, inputs, p.dtype)
+        u0 = ar.new(I)
+        iters = ar.new(dtype=_I32) if want_iters else None
+        io = self._io(ar, I, p.horizon, (A, B, Cc, Q, R, lower, upper, x0, targets), controls, v_state, u0, iters)
+        self._run(self._lib.tpc_mpc_solve_batch_general, p, ar, C.byref(io))
         return (u0, iters) if want_iters else u0
 
     def polish_batch_general(self, A, B, Cc, Q, R, lower, upper, x0, targets, controls, tol: float = 1e-9,
@@ -617,54 +430,13 @@ class MpcSolver:
         used or -1, and sets last_flags (FLAG_NOT_POLISHED if any instance was left); want_status=False returns
         controls alone, leaves last_flags at 0 and keeps a DEVICE call asynchronous."""
         p = self._params(**over)
-        H = p.horizon
-        if _is_torch(A):
-            import torch
-            n = A.shape[-1]
-            I = inputs or R.shape[0]
-
-            def ptr(t, rows):
-                if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == (rows, n)):
-                    raise ValueError(f"expected contiguous fp64 CUDA tensor [{rows},{n}]")
-                return t.data_ptr()
-
-            def new(dtype):
-                t = torch.empty(n, dtype=torch.float64 if dtype is np.float64 else torch.int32, device=A.device)
-                return t, t.data_ptr()
-            stream = C.c_void_p(torch.cuda.current_stream(A.device).cuda_stream)
-            mem = capi.DEVICE
-        else:
-            n = np.asarray(A).shape[-1]
-            I = inputs or np.asarray(R).shape[0]
-            keep = []
-
-            def ptr(a, rows):
-                a = np.ascontiguousarray(a, dtype=np.float64)
-                if a.shape != (rows, n):
-                    raise ValueError(f"expected an array [{rows},{n}]")
-                keep.append(a)
-                return a.ctypes.data
-
-            def new(dtype):
-                a = np.empty(n, dtype=dtype)
-                return a, a.ctypes.data
-            if not (isinstance(controls, np.ndarray) and controls.dtype == np.float64 and controls.flags.c_contiguous):
-                raise ValueError("controls must be a C-contiguous fp64 ndarray (it is updated in place)")
-            stream = None
-            mem = capi.HOST
-        status, sp = new(np.int32) if want_status else (None, None)
-        rin, rip = new(np.float64) if want_status else (None, None)
-        rout, rop = new(np.float64) if want_status else (None, None)
-        io = capi.GeneralIO(inputs=I, n=n, ld=n, A=ptr(A, 4), B=ptr(B, 2 * I), C=ptr(Cc, 2), Q=ptr(Q, 2),
-                            R=ptr(R, I), lower=ptr(lower, I), upper=ptr(upper, I), x0=ptr(x0, 2),
-                            targets=ptr(targets, 2 * H), controls_inout=ptr(controls, H * I), v_inout=None, u0=None,
-                            iters=None)
-        q = capi.Polish(tol=float(tol), max_rounds=int(max_rounds), reserved=0, status=sp, residual_in=rip,
-                        residual_out=rop)
-        flags = C.c_uint32(0)
-        self._check(self._lib.tpc_mpc_polish_batch_general(self._h, C.byref(p), C.byref(io), C.byref(q),
-                                                           C.byref(flags) if want_status else None, mem, stream))
-        self.last_flags = flags.value
+        ar, I = self._general(A, R, inputs)
+        status = ar.new(dtype=_I32) if want_status else None
+        rin, rout = (ar.new(), ar.new()) if want_status else (None, None)
+        io = self._io(ar, I, p.horizon, (A, B, Cc, Q, R, lower, upper, x0, targets), controls)
+        q = capi.Polish(tol=float(tol), max_rounds=int(max_rounds), reserved=0, status=ar.addr(status),
+                        residual_in=ar.addr(rin), residual_out=ar.addr(rout))
+        self._run(self._lib.tpc_mpc_polish_batch_general, p, ar, C.byref(io), C.byref(q), want_flags=want_status)
         return (controls, status, rin, rout) if want_status else controls
 
     GRAD_NAMES = ("A", "B", "C", "Q", "R", "lower", "upper", "x0", "targets", "kkt_residual")
@@ -684,68 +456,33 @@ class MpcSolver:
         unknown = set(want) - set(self.GRAD_NAMES)
         if unknown:
             raise ValueError(f"unknown gradient names {sorted(unknown)}")
-        if _is_torch(A):
-            import torch
-            n = A.shape[-1]
-            I = inputs or R.shape[0]
-
-            def ptr(t, rows):
-                if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == (rows, n)):
-                    raise ValueError(f"expected contiguous fp64 CUDA tensor [{rows},{n}]")
-                return t.data_ptr()
-
-            def new(rows):
-                return torch.empty((rows, n), dtype=torch.float64, device=A.device)
-            stream = C.c_void_p(torch.cuda.current_stream(A.device).cuda_stream)
-            mem = capi.DEVICE
-        else:
-            A = np.ascontiguousarray(A, dtype=np.float64)
-            n = A.shape[-1]
-            I = inputs or np.asarray(R).shape[0]
-            keep = []
-
-            def ptr(a, rows):
-                a = np.ascontiguousarray(a, dtype=np.float64)
-                if a.shape != (rows, n):
-                    raise ValueError(f"expected an array [{rows},{n}]")
-                keep.append(a)
-                return a.ctypes.data
-
-            def new(rows):
-                return np.empty((rows, n), dtype=np.float64)
-            stream = None
-            mem = capi.HOST
-        rows = {"A": 4, "B": 2 * I, "C": 2, "Q": 2, "R": I, "lower": I, "upper": I, "x0": 2, "targets": 2 * H,
-                "kkt_residual": 1}
-        out = {k: new(rows[k]) for k in want}
-
-        def optr(k):
-            if k not in out:
-                return None
-            return out[k].data_ptr() if mem == capi.DEVICE else out[k].ctypes.data
-        io = capi.GeneralIO(inputs=I, n=n, ld=n, A=ptr(A, 4), B=ptr(B, 2 * I), C=ptr(Cc, 2), Q=ptr(Q, 2),
-                            R=ptr(R, I), lower=ptr(lower, I), upper=ptr(upper, I), x0=ptr(x0, 2),
-                            targets=ptr(targets, 2 * H), controls_inout=None, v_inout=None, u0=None, iters=None)
-        g = capi.GeneralGrad(controls=ptr(controls, H * I), grad_controls=ptr(grad_controls, H * I),
-                             dA=optr("A"), dB=optr("B"), dC=optr("C"), dQ=optr("Q"), dR=optr("R"),
-                             dlower=optr("lower"), dupper=optr("upper"), dx0=optr("x0"), dtargets=optr("targets"),
-                             kkt_residual=optr("kkt_residual"))
-        flags = C.c_uint32(0)
-        self._check(self._lib.tpc_mpc_solve_batch_general_backward(self._h, C.byref(p), C.byref(io), C.byref(g),
-                                                                   C.byref(flags) if want_flags else None, mem, stream))
-        self.last_flags = flags.value
+        ar, I = self._general(A, R, inputs)
+        rows = _rows(I, H)
+        out = {k: ar.new(rows[k]) for k in want}
+        to = {"d" + k: ar.addr(a) for k, a in out.items() if k != "kkt_residual"}
+        io = self._io(ar, I, H, (A, B, Cc, Q, R, lower, upper, x0, targets))
+        g = capi.GeneralGrad(controls=ar.read(controls, H * I), grad_controls=ar.read(grad_controls, H * I),
+                             kkt_residual=ar.addr(out.get("kkt_residual")), **to)
+        self._run(self._lib.tpc_mpc_solve_batch_general_backward, p, ar, C.byref(io), C.byref(g), want_flags=want_flags)
         if "kkt_residual" in out:
-            out["kkt_residual"] = out["kkt_residual"].reshape(n)
+            out["kkt_residual"] = out["kkt_residual"].reshape(ar.n)
         return out
 
-    def _plant(self, plant, disturbance, ptr, I, steps):
-        """capi.Plant of plant=(Ap, Bp, Cp) | None and disturbance [steps*2, n] | None, through the call's ptr()."""
+    @staticmethod
+    def _device_only(ar):
+        if ar.mem != capi.DEVICE:
+            raise ValueError("this entry takes CUDA tensors only")
+        return ar
+
+    @staticmethod
+    def _plant(ar, plant, disturbance, I, steps, match="shape"):
+        """capi.Plant of plant=(Ap, Bp, Cp) | None and disturbance [steps*2, n] | None"""
         if plant is not None and len(plant) != 3:
             raise ValueError("plant must be (Ap, Bp, Cp)")
         Ap, Bp, Cp = plant if plant is not None else (None, None, None)
-        d = ptr(disturbance, 2 * steps)
-        ld_d = 0 if disturbance is None else int(disturbance.shape[-1])
-        return capi.Plant(A=ptr(Ap, 4), B=ptr(Bp, 2 * I), C=ptr(Cp, 2), disturbance=d, ld_d=ld_d)
+        return capi.Plant(A=ar.read(Ap, 4, None, match), B=ar.read(Bp, 2 * I, None, match),
+                          C=ar.read(Cp, 2, None, match), disturbance=ar.read(disturbance, 2 * steps, None, match),
+                          ld_d=0 if disturbance is None else ar.n)
 
     def rollout(self, steps: int, A, B, Cc, Q, R, lower, upper, x0, targets, new_last_targets=None,
                 controls=None, v_state=None, inputs: Optional[int] = None, want_states: bool = True,
@@ -775,70 +512,23 @@ class MpcSolver:
                  inputs, want_states, want_iters, plant=None, disturbance=None, **over):
         p = self._params(**over)
         H = p.horizon
-        if _is_torch(A):
-            import torch
-            tdt = torch.float64 if p.dtype == capi.F64 else torch.float32
-            n = A.shape[-1]
-            I = inputs or R.shape[0]
-
-            def ptr(t, rows):
-                if t is None:
-                    return None
-                if not (t.is_cuda and t.dtype == tdt and t.is_contiguous() and tuple(t.shape) == (rows, n)):
-                    raise ValueError(f"expected contiguous CUDA tensor [{rows},{n}] of the solver dtype")
-                return t.data_ptr()
-            c_out = torch.empty((steps * I, n), dtype=tdt, device=A.device)
-            s_out = torch.empty((steps * 2, n), dtype=tdt, device=A.device) if want_states else None
-            i_out = torch.empty((steps, n), dtype=torch.int32, device=A.device) if want_iters else None
-            q_out = torch.empty((steps * H * I, n), dtype=tdt, device=A.device) if record else None
-            stream = C.c_void_p(torch.cuda.current_stream(A.device).cuda_stream)
-            mem = capi.DEVICE
-            optr = lambda t: None if t is None else t.data_ptr()
-        else:
-            dt = _NP[p.dtype]
-            A = np.ascontiguousarray(A, dtype=dt)
-            n = A.shape[-1]
-            I = inputs or np.asarray(R).shape[0]
-            keep = []
-
-            def ptr(a, rows):
-                if a is None:
-                    return None
-                if not (isinstance(a, np.ndarray) and a.dtype == dt and a.flags.c_contiguous and a.shape == (rows, n)):
-                    raise ValueError(f"expected C-contiguous ndarray [{rows},{n}] of the solver dtype")
-                keep.append(a)
-                return a.ctypes.data
-            B, Cc, Q, R, lower, upper, x0, targets = (np.ascontiguousarray(a, dtype=dt) for a in
-                                                      (B, Cc, Q, R, lower, upper, x0, targets))
-            if new_last_targets is not None:
-                new_last_targets = np.ascontiguousarray(new_last_targets, dtype=dt)
-            c_out = np.empty((steps * I, n), dtype=dt)
-            s_out = np.empty((steps * 2, n), dtype=dt) if want_states else None
-            i_out = np.empty((steps, n), dtype=np.int32) if want_iters else None
-            q_out = np.empty((steps * H * I, n), dtype=dt) if record else None
-            stream = None
-            mem = capi.HOST
-            optr = lambda a: None if a is None else a.ctypes.data
-        io = capi.GeneralIO(inputs=I, n=n, ld=n, A=ptr(A, 4), B=ptr(B, 2 * I), C=ptr(Cc, 2), Q=ptr(Q, 2),
-                            R=ptr(R, I), lower=ptr(lower, I), upper=ptr(upper, I), x0=ptr(x0, 2),
-                            targets=ptr(targets, 2 * H), controls_inout=ptr(controls, H * I),
-                            v_inout=ptr(v_state, H * I), u0=None, iters=None)
-        flags = C.c_uint32(0)
+        ar, I = self._general(A, R, inputs, p.dtype)
+        io = self._io(ar, I, H, (A, B, Cc, Q, R, lower, upper, x0, targets), controls, v_state)
+        c_out = ar.new(steps * I)
+        s_out = ar.new(steps * 2) if want_states else None
+        i_out = ar.new(steps, dtype=_I32) if want_iters else None
+        q_out = ar.new(steps * H * I) if record else None
+        nlt = ar.read(new_last_targets, 2 * steps)
+        outs = (ar.addr(c_out), ar.addr(s_out), ar.addr(i_out))
         if plant is not None or disturbance is not None:
-            pl = self._plant(plant, disturbance, ptr, I, steps)
-            self._check(self._lib.tpc_mpc_rollout_plant(self._h, C.byref(p), C.byref(io), C.byref(pl), capi.LOOP_RECORD,
-                                                        int(steps), ptr(new_last_targets, 2 * steps), None, 0,
-                                                        optr(c_out), optr(s_out), optr(i_out), optr(q_out), None,
-                                                        C.byref(flags), mem, stream))
+            pl = self._plant(ar, plant, disturbance, I, steps)
+            entry = self._lib.tpc_mpc_rollout_plant
+            args = (C.byref(io), C.byref(pl), capi.LOOP_RECORD, int(steps), nlt, None, 0, *outs, ar.addr(q_out), None)
         elif record:
-            self._check(self._lib.tpc_mpc_rollout_record(self._h, C.byref(p), C.byref(io), int(steps),
-                                                         ptr(new_last_targets, 2 * steps), optr(c_out), optr(s_out),
-                                                         optr(i_out), optr(q_out), C.byref(flags), mem, stream))
+            entry, args = self._lib.tpc_mpc_rollout_record, (C.byref(io), int(steps), nlt, *outs, ar.addr(q_out))
         else:
-            self._check(self._lib.tpc_mpc_rollout(self._h, C.byref(p), C.byref(io), int(steps),
-                                                  ptr(new_last_targets, 2 * steps), optr(c_out), optr(s_out),
-                                                  optr(i_out), C.byref(flags), mem, stream))
-        self.last_flags = flags.value
+            entry, args = self._lib.tpc_mpc_rollout, (C.byref(io), int(steps), nlt, *outs)
+        self._run(entry, p, ar, *args)
         return c_out, s_out, i_out, q_out
 
     def rollout_polished(self, steps: int, A, B, Cc, Q, R, lower, upper, x0, targets, new_last_targets=None,
@@ -856,76 +546,10 @@ class MpcSolver:
         of the inputs' kind that receive the polish's residual_in and residual_out of every (step, instance).
         plant=(Ap, Bp, Cp) and / or disturbance [steps*2, n]: the state moves with x <- Ap x + Bp u0 + Cp + d_k
         instead of the controller's model (tpc_mpc_rollout_plant); both None is the existing entry."""
-        p = self._params(**over)
-        H = p.horizon
-        if _is_torch(A):
-            import torch
-            n = A.shape[-1]
-            I = inputs or R.shape[0]
-
-            def ptr(t, rows):
-                if t is None:
-                    return None
-                if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == (rows, n)):
-                    raise ValueError(f"expected contiguous fp64 CUDA tensor [{rows},{n}]")
-                return t.data_ptr()
-
-            def new(rows, dtype=np.float64):
-                return torch.empty((rows, n), dtype=torch.float64 if dtype is np.float64 else torch.int32,
-                                   device=A.device)
-            stream = C.c_void_p(torch.cuda.current_stream(A.device).cuda_stream)
-            mem = capi.DEVICE
-            optr = lambda t: None if t is None else t.data_ptr()
-        else:
-            A = np.ascontiguousarray(A, dtype=np.float64)
-            n = A.shape[-1]
-            I = inputs or np.asarray(R).shape[0]
-            keep = []
-
-            def ptr(a, rows):
-                if a is None:
-                    return None
-                if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and
-                        a.shape == (rows, n)):
-                    raise ValueError(f"expected C-contiguous fp64 ndarray [{rows},{n}]")
-                keep.append(a)
-                return a.ctypes.data
-            B, Cc, Q, R, lower, upper, x0, targets = (np.ascontiguousarray(a, dtype=np.float64) for a in
-                                                      (B, Cc, Q, R, lower, upper, x0, targets))
-            if new_last_targets is not None:
-                new_last_targets = np.ascontiguousarray(new_last_targets, dtype=np.float64)
-
-            def new(rows, dtype=np.float64):
-                return np.empty((rows, n), dtype=dtype)
-            stream = None
-            mem = capi.HOST
-            optr = lambda a: None if a is None else a.ctypes.data
-        c_out, s_out, q_out = new(steps * I), new(steps * 2), new(steps * H * I)
-        i_out = new(steps, np.int32) if want_iters else None
-        status = new(steps, np.int32) if want_status else None
-        io = capi.GeneralIO(inputs=I, n=n, ld=n, A=ptr(A, 4), B=ptr(B, 2 * I), C=ptr(Cc, 2), Q=ptr(Q, 2),
-                            R=ptr(R, I), lower=ptr(lower, I), upper=ptr(upper, I), x0=ptr(x0, 2),
-                            targets=ptr(targets, 2 * H), controls_inout=ptr(controls, H * I),
-                            v_inout=ptr(v_state, H * I), u0=None, iters=None)
-        rin, rout = residuals if residuals is not None else (None, None)
-        q = capi.Polish(tol=float(tol), max_rounds=int(max_rounds), reserved=0, status=optr(status),
-                        residual_in=ptr(rin, steps), residual_out=ptr(rout, steps))
-        flags = C.c_uint32(0)
-        if plant is not None or disturbance is not None:   # the same loop against a separate plant
-            pl = self._plant(plant, disturbance, ptr, I, steps)
-            self._check(self._lib.tpc_mpc_rollout_plant(self._h, C.byref(p), C.byref(io), C.byref(pl),
-                                                        capi.LOOP_POLISHED, int(steps),
-                                                        ptr(new_last_targets, 2 * steps), C.byref(q), 0, optr(c_out),
-                                                        optr(s_out), optr(i_out), optr(q_out), None,
-                                                        C.byref(flags) if want_status else None, mem, stream))
-            self.last_flags = flags.value
-            return c_out, s_out, q_out, status, i_out
-        self._check(self._lib.tpc_mpc_rollout_polished(self._h, C.byref(p), C.byref(io), int(steps),
-                                                       ptr(new_last_targets, 2 * steps), C.byref(q), optr(c_out),
-                                                       optr(s_out), optr(i_out), optr(q_out),
-                                                       C.byref(flags) if want_status else None, mem, stream))
-        self.last_flags = flags.value
-        return c_out, s_out, q_out, status, i_out
+        return self._rollout_exact(None, steps, (A, B, Cc, Q, R, lower, upper, x0, targets), new_last_targets,
+                                   controls=controls, v_state=v_state, inputs=inputs, tol=tol, max_rounds=max_rounds,
+                                   want_status=want_status, want_iters=want_iters, residuals=residuals, plant=plant,
+                                   disturbance=disturbance, **over)
 
     def rollout_newton(self, steps: int, A, B, Cc, Q, R, lower, upper, x0, targets, new_last_targets=None,
                        controls=None, v_state=None, inputs: Optional[int] = None, tol: float = 1e-9,
@@ -941,78 +565,42 @@ class MpcSolver:
         iters[steps, n] | None, first_unverified[n]) -- int32, the step phase 1 stopped at, `steps` for an instance
         it carried to the end.  iters is 0 for the steps of such an instance.  plant, disturbance: as
         rollout_polished."""
+        return self._rollout_exact(fallback, steps, (A, B, Cc, Q, R, lower, upper, x0, targets), new_last_targets,
+                                   controls=controls, v_state=v_state, inputs=inputs, tol=tol, max_rounds=max_rounds,
+                                   want_status=want_status, want_iters=want_iters, residuals=residuals, plant=plant,
+                                   disturbance=disturbance, **over)
+
+    def _rollout_exact(self, newton, steps, model, new_last_targets, *, controls, v_state, inputs, tol, max_rounds,
+                       want_status, want_iters, residuals, plant, disturbance, **over):
+        """rollout_polished (newton=None) and rollout_newton (newton=its fallback): the same arrays, the Newton loop
+        with `first_unverified` and the fallback on top."""
         p = self._params(**over)
         H = p.horizon
-        if _is_torch(A):
-            import torch
-            n = A.shape[-1]
-            I = inputs or R.shape[0]
-
-            def ptr(t, rows):
-                if t is None:
-                    return None
-                if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == (rows, n)):
-                    raise ValueError(f"expected contiguous fp64 CUDA tensor [{rows},{n}]")
-                return t.data_ptr()
-
-            def new(rows, dtype=np.float64):
-                return torch.empty((rows, n), dtype=torch.float64 if dtype is np.float64 else torch.int32,
-                                   device=A.device)
-            stream = C.c_void_p(torch.cuda.current_stream(A.device).cuda_stream)
-            mem = capi.DEVICE
-            optr = lambda t: None if t is None else t.data_ptr()
-        else:
-            A = np.ascontiguousarray(A, dtype=np.float64)
-            n = A.shape[-1]
-            I = inputs or np.asarray(R).shape[0]
-            keep = []
-
-            def ptr(a, rows):
-                if a is None:
-                    return None
-                if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and
-                        a.shape == (rows, n)):
-                    raise ValueError(f"expected C-contiguous fp64 ndarray [{rows},{n}]")
-                keep.append(a)
-                return a.ctypes.data
-            B, Cc, Q, R, lower, upper, x0, targets = (np.ascontiguousarray(a, dtype=np.float64) for a in
-                                                      (B, Cc, Q, R, lower, upper, x0, targets))
-            if new_last_targets is not None:
-                new_last_targets = np.ascontiguousarray(new_last_targets, dtype=np.float64)
-
-            def new(rows, dtype=np.float64):
-                return np.empty((rows, n), dtype=dtype)
-            stream = None
-            mem = capi.HOST
-            optr = lambda a: None if a is None else a.ctypes.data
-        c_out, s_out, q_out = new(steps * I), new(steps * 2), new(steps * H * I)
-        i_out = new(steps, np.int32) if want_iters else None
-        status = new(steps, np.int32) if want_status else None
-        first = new(1, np.int32)
-        io = capi.GeneralIO(inputs=I, n=n, ld=n, A=ptr(A, 4), B=ptr(B, 2 * I), C=ptr(Cc, 2), Q=ptr(Q, 2),
-                            R=ptr(R, I), lower=ptr(lower, I), upper=ptr(upper, I), x0=ptr(x0, 2),
-                            targets=ptr(targets, 2 * H), controls_inout=ptr(controls, H * I),
-                            v_inout=ptr(v_state, H * I), u0=None, iters=None)
+        ar, I = self._general(model[0], model[4], inputs)
+        io = self._io(ar, I, H, model, controls, v_state)
+        c_out, s_out, q_out = ar.new(steps * I), ar.new(steps * 2), ar.new(steps * H * I)
+        i_out = ar.new(steps, dtype=_I32) if want_iters else None
+        status = ar.new(steps, dtype=_I32) if want_status else None
+        first = ar.new(1, dtype=_I32) if newton else None
         rin, rout = residuals if residuals is not None else (None, None)
-        q = capi.Polish(tol=float(tol), max_rounds=int(max_rounds), reserved=0, status=optr(status),
-                        residual_in=ptr(rin, steps), residual_out=ptr(rout, steps))
-        flags = C.c_uint32(0)
+        q = capi.Polish(tol=float(tol), max_rounds=int(max_rounds), reserved=0, status=ar.addr(status),
+                        residual_in=ar.update(rin, steps), residual_out=ar.update(rout, steps))
+        nlt = ar.read(new_last_targets, 2 * steps)
+        fb = capi.NEWTON_FALLBACKS[newton] if newton else 0
+        outs = (ar.addr(c_out), ar.addr(s_out), ar.addr(i_out), ar.addr(q_out))
         if plant is not None or disturbance is not None:   # the same loop against a separate plant
-            pl = self._plant(plant, disturbance, ptr, I, steps)
-            self._check(self._lib.tpc_mpc_rollout_plant(self._h, C.byref(p), C.byref(io), C.byref(pl), capi.LOOP_NEWTON,
-                                                        int(steps), ptr(new_last_targets, 2 * steps), C.byref(q),
-                                                        capi.NEWTON_FALLBACKS[fallback], optr(c_out), optr(s_out),
-                                                        optr(i_out), optr(q_out), optr(first),
-                                                        C.byref(flags) if want_status else None, mem, stream))
-            self.last_flags = flags.value
-            return c_out, s_out, q_out, status, i_out, first[0]
-        self._check(self._lib.tpc_mpc_rollout_newton(self._h, C.byref(p), C.byref(io), int(steps),
-                                                     ptr(new_last_targets, 2 * steps), C.byref(q),
-                                                     capi.NEWTON_FALLBACKS[fallback], optr(c_out), optr(s_out),
-                                                     optr(i_out), optr(q_out), optr(first),
-                                                     C.byref(flags) if want_status else None, mem, stream))
-        self.last_flags = flags.value
-        return c_out, s_out, q_out, status, i_out, first[0]
+            pl = self._plant(ar, plant, disturbance, I, steps)
+            entry = self._lib.tpc_mpc_rollout_plant
+            args = (C.byref(io), C.byref(pl), capi.LOOP_NEWTON if newton else capi.LOOP_POLISHED, int(steps), nlt,
+                    C.byref(q), fb, *outs, ar.addr(first))
+        elif newton:
+            entry = self._lib.tpc_mpc_rollout_newton
+            args = (C.byref(io), int(steps), nlt, C.byref(q), fb, *outs, ar.addr(first))
+        else:
+            entry, args = self._lib.tpc_mpc_rollout_polished, (C.byref(io), int(steps), nlt, C.byref(q), *outs)
+        self._run(entry, p, ar, *args, want_flags=want_status)
+        out = (c_out, s_out, q_out, status, i_out)
+        return out + (first[0],) if newton else out
 
     ROLLOUT_GRAD_NAMES = GRAD_NAMES[:-1] + ("new_last_targets", "kkt_residual")
     PLANT_GRAD_NAMES = ("Ap", "Bp", "Cp", "disturbance")
@@ -1044,85 +632,34 @@ class MpcSolver:
         unknown = set(want) - set(self.ROLLOUT_GRAD_NAMES) - set(self.PLANT_GRAD_NAMES)
         if unknown:
             raise ValueError(f"unknown gradient names {sorted(unknown)}")
-        if _is_torch(A):
-            import torch
-            n = A.shape[-1]
-            I = inputs or R.shape[0]
-
-            def ptr(t, rows):
-                if t is None:
-                    return None
-                if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == (rows, n)):
-                    raise ValueError(f"expected contiguous fp64 CUDA tensor [{rows},{n}]")
-                return t.data_ptr()
-
-            def new(rows):
-                return torch.empty((rows, n), dtype=torch.float64, device=A.device)
-            stream = C.c_void_p(torch.cuda.current_stream(A.device).cuda_stream)
-            mem = capi.DEVICE
-        else:
-            A = np.ascontiguousarray(A, dtype=np.float64)
-            n = A.shape[-1]
-            I = inputs or np.asarray(R).shape[0]
-            keep = []
-
-            def ptr(a, rows):
-                if a is None:
-                    return None
-                a = np.ascontiguousarray(a, dtype=np.float64)
-                if a.shape != (rows, n):
-                    raise ValueError(f"expected an array [{rows},{n}]")
-                keep.append(a)
-                return a.ctypes.data
-
-            def new(rows):
-                return np.empty((rows, n), dtype=np.float64)
-            stream = None
-            mem = capi.HOST
-        rows = {"A": 4, "B": 2 * I, "C": 2, "Q": 2, "R": I, "lower": I, "upper": I, "x0": 2, "targets": 2 * H,
-                "new_last_targets": 2 * steps, "kkt_residual": 1, "Ap": 4, "Bp": 2 * I, "Cp": 2,
-                "disturbance": 2 * steps}
-        out = {k: new(rows[k]) for k in want}
-
-        def optr(k):
-            if k not in out:
-                return None
-            return out[k].data_ptr() if mem == capi.DEVICE else out[k].ctypes.data
-        io = capi.GeneralIO(inputs=I, n=n, ld=n, A=ptr(A, 4), B=ptr(B, 2 * I), C=ptr(Cc, 2), Q=ptr(Q, 2),
-                            R=ptr(R, I), lower=ptr(lower, I), upper=ptr(upper, I), x0=ptr(x0, 2),
-                            targets=ptr(targets, 2 * H), controls_inout=None, v_inout=None, u0=None, iters=None)
-        g = capi.RolloutGrad(sequences=ptr(sequences, steps * H * I), states=ptr(states, 2 * steps),
-                             grad_controls=ptr(grad_controls, steps * I), grad_states=ptr(grad_states, 2 * steps),
-                             dA=optr("A"), dB=optr("B"), dC=optr("C"), dQ=optr("Q"), dR=optr("R"),
-                             dlower=optr("lower"), dupper=optr("upper"), dx0=optr("x0"), dtargets=optr("targets"),
-                             dnew_last_targets=optr("new_last_targets"), kkt_residual=optr("kkt_residual"))
-        flags = C.c_uint32(0)
+        ar, I = self._general(A, R, inputs)
+        rows = _rows(I, H, steps)
+        out = {k: ar.new(rows[k]) for k in want}
+        to = {k: ar.addr(a) for k, a in out.items()}
+        io = self._io(ar, I, H, (A, B, Cc, Q, R, lower, upper, x0, targets))
+        g = capi.RolloutGrad(sequences=ar.read(sequences, steps * H * I), states=ar.read(states, 2 * steps),
+                             grad_controls=ar.read(grad_controls, steps * I), grad_states=ar.read(grad_states, 2 * steps),
+                             dnew_last_targets=to.get("new_last_targets"), kkt_residual=to.get("kkt_residual"),
+                             **{"d" + k: to.get(k) for k in self.GRAD_NAMES[:-1]})
+        nlt = ar.read(new_last_targets, 2 * steps)
         if plant_call:
-            pl = self._plant(plant, None, ptr, I, steps)   # (the disturbance itself is not read: the states are recorded)
-            pg = capi.PlantGrad(dA=optr("Ap"), dB=optr("Bp"), dC=optr("Cp"), ddisturbance=optr("disturbance"))
-            self._check(self._lib.tpc_mpc_rollout_plant_backward(self._h, C.byref(p), C.byref(io), C.byref(pl),
-                                                                 int(steps), ptr(new_last_targets, 2 * steps),
-                                                                 C.byref(g), C.byref(pg),
-                                                                 C.byref(flags) if want_flags else None, mem, stream))
-            self.last_flags = flags.value
-            if "kkt_residual" in out:
-                out["kkt_residual"] = out["kkt_residual"].reshape(n)
-            return out
-        self._check(self._lib.tpc_mpc_rollout_backward(self._h, C.byref(p), C.byref(io), int(steps),
-                                                       ptr(new_last_targets, 2 * steps), C.byref(g),
-                                                       C.byref(flags) if want_flags else None, mem, stream))
-        self.last_flags = flags.value
+            pl = self._plant(ar, plant, None, I, steps)   # (the disturbance itself is not read: the states are recorded)
+            pg = capi.PlantGrad(dA=to.get("Ap"), dB=to.get("Bp"), dC=to.get("Cp"), ddisturbance=to.get("disturbance"))
+            entry = self._lib.tpc_mpc_rollout_plant_backward
+            args = (C.byref(io), C.byref(pl), int(steps), nlt, C.byref(g), C.byref(pg))
+        else:
+            entry, args = self._lib.tpc_mpc_rollout_backward, (C.byref(io), int(steps), nlt, C.byref(g))
+        self._run(entry, p, ar, *args, want_flags=want_flags)
         if "kkt_residual" in out:
-            out["kkt_residual"] = out["kkt_residual"].reshape(n)
+            out["kkt_residual"] = out["kkt_residual"].reshape(ar.n)
         return out
 
     TANGENT_NAMES = ("A", "B", "C", "Q", "R", "lower", "upper", "x0", "targets", "new_last_targets")
     PLANT_TANGENT_NAMES = ("Ap", "Bp", "Cp", "disturbance")
 
-    def _forward_setup(self, A, R, inputs, tangents, rows):
-        """What the two forward-mode calls share: (n, I, K, ptr, new, stream, mem, Tangents factory).  `tangents` maps
-        names of TANGENT_NAMES (and PLANT_TANGENT_NAMES -> the PlantTangents struct) to arrays [K, c, n] (2-D [c, n]: K = 1);
-        rows(I) gives c per name."""
+    def _tangents(self, ar, rows, tangents):
+        """(K, capi.Tangents, capi.PlantTangents) of `tangents`: names of TANGENT_NAMES and PLANT_TANGENT_NAMES ->
+        arrays [K, c, n] (2-D [c, n]: K = 1) with c = rows[name]"""
         unknown = set(tangents) - set(self.TANGENT_NAMES) - set(self.PLANT_TANGENT_NAMES)
         if unknown:
             raise ValueError(f"unknown tangent names {sorted(unknown)}")
@@ -1135,50 +672,10 @@ class MpcSolver:
             if k is None or (K is not None and k != K):
                 raise ValueError(f"tangent {name!r}: expected [K, c, n] (or [c, n] for K = 1) with one K for all")
             K = k
-        if _is_torch(A):
-            import torch
-            n = A.shape[-1]
-            I = inputs or R.shape[0]
-
-            def ptr(t, r):
-                if t is None:
-                    return None
-                if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == r * n
-                        and t.shape[-1] == n):
-                    raise ValueError(f"expected contiguous fp64 CUDA tensor [{r},{n}]")
-                return t.data_ptr()
-
-            def new(*shape):
-                return torch.empty(shape + (n,), dtype=torch.float64, device=A.device)
-            stream = C.c_void_p(torch.cuda.current_stream(A.device).cuda_stream)
-            mem = capi.DEVICE
-            optr = lambda t: None if t is None else t.data_ptr()
-        else:
-            n = np.asarray(A).shape[-1]
-            I = inputs or np.asarray(R).shape[0]
-            keep = []
-
-            def ptr(a, r):
-                if a is None:
-                    return None
-                a = np.ascontiguousarray(a, dtype=np.float64)
-                if a.size != r * n or a.shape[-1] != n:
-                    raise ValueError(f"expected an array [{r},{n}]")
-                keep.append(a)
-                return a.ctypes.data
-
-            def new(*shape):
-                return np.empty(shape + (n,), dtype=np.float64)
-            stream = None
-            mem = capi.HOST
-            optr = lambda a: None if a is None else a.ctypes.data
-        c = rows(I)
-        fields = {("t" + name): ptr(tangents.get(name), K * c[name]) for name in self.TANGENT_NAMES}
-        tan = capi.Tangents(directions=K, reserved=0, **fields)
-        ptan = capi.PlantTangents(
-            tA=ptr(tangents.get("Ap"), K * 4), tB=ptr(tangents.get("Bp"), K * 2 * I), tC=ptr(tangents.get("Cp"), K * 2),
-            tdisturbance=ptr(tangents.get("disturbance"), K * c.get("disturbance", 0)))
-        return n, I, K, ptr, new, optr, stream, mem, tan, ptan
+        at = {name: ar.read(v, K * rows[name], None, "loose") for name, v in tangents.items()}
+        tan = capi.Tangents(directions=K, reserved=0, **{"t" + name: at.get(name) for name in self.TANGENT_NAMES})
+        ptan = capi.PlantTangents(tA=at.get("Ap"), tB=at.get("Bp"), tC=at.get("Cp"), tdisturbance=at.get("disturbance"))
+        return K, tan, ptan
 
     def solve_batch_general_forward(self, A, B, Cc, Q, R, lower, upper, x0, targets, controls, tangents,
                                     inputs: Optional[int] = None, want_flags: bool = True, **over):
@@ -1192,18 +689,12 @@ class MpcSolver:
         H = p.horizon
         if set(tangents) & ({"new_last_targets"} | set(self.PLANT_TANGENT_NAMES)):
             raise ValueError("the single solve has no new_last_targets and no plant")
-        n, I, K, ptr, new, optr, stream, mem, tan, ptan = self._forward_setup(
-            A, R, inputs, tangents, lambda I: {"A": 4, "B": 2 * I, "C": 2, "Q": 2, "R": I, "lower": I, "upper": I,
-                                               "x0": 2, "targets": 2 * H, "new_last_targets": 0})
-        io = capi.GeneralIO(inputs=I, n=n, ld=n, A=ptr(A, 4), B=ptr(B, 2 * I), C=ptr(Cc, 2), Q=ptr(Q, 2),
-                            R=ptr(R, I), lower=ptr(lower, I), upper=ptr(upper, I), x0=ptr(x0, 2),
-                            targets=ptr(targets, 2 * H), controls_inout=None, v_inout=None, u0=None, iters=None)
-        tu = new(K, H * I)
-        flags = C.c_uint32(0)
-        self._check(self._lib.tpc_mpc_solve_batch_general_forward(self._h, C.byref(p), C.byref(io),
-                                                                  ptr(controls, H * I), C.byref(tan), optr(tu),
-                                                                  C.byref(flags) if want_flags else None, mem, stream))
-        self.last_flags = flags.value
+        ar, I = self._general(A, R, inputs)
+        K, tan, _ = self._tangents(ar, _rows(I, H), tangents)
+        io = self._io(ar, I, H, (A, B, Cc, Q, R, lower, upper, x0, targets), match="loose")
+        tu = ar.new(K, H * I)
+        self._run(self._lib.tpc_mpc_solve_batch_general_forward, p, ar, C.byref(io),
+                  ar.read(controls, H * I, None, "loose"), C.byref(tan), ar.addr(tu), want_flags=want_flags)
         return tu
 
     def rollout_forward(self, steps: int, A, B, Cc, Q, R, lower, upper, x0, targets, new_last_targets=None, *,
@@ -1220,32 +711,20 @@ class MpcSolver:
         p = self._params(**over)
         H = p.horizon
         plant_call = plant is not None or disturbance is not None or bool(set(tangents) & set(self.PLANT_TANGENT_NAMES))
-        n, I, K, ptr, new, optr, stream, mem, tan, ptan = self._forward_setup(
-            A, R, inputs, tangents, lambda I: {"A": 4, "B": 2 * I, "C": 2, "Q": 2, "R": I, "lower": I, "upper": I,
-                                               "x0": 2, "targets": 2 * H, "new_last_targets": 2 * steps,
-                                               "disturbance": 2 * steps})
-        io = capi.GeneralIO(inputs=I, n=n, ld=n, A=ptr(A, 4), B=ptr(B, 2 * I), C=ptr(Cc, 2), Q=ptr(Q, 2),
-                            R=ptr(R, I), lower=ptr(lower, I), upper=ptr(upper, I), x0=ptr(x0, 2),
-                            targets=ptr(targets, 2 * H), controls_inout=None, v_inout=None, u0=None, iters=None)
-        tu = new(K, steps * I)
-        tx = new(K, steps * 2) if want_states else None
-        flags = C.c_uint32(0)
+        ar, I = self._general(A, R, inputs)
+        K, tan, ptan = self._tangents(ar, _rows(I, H, steps), tangents)
+        io = self._io(ar, I, H, (A, B, Cc, Q, R, lower, upper, x0, targets), match="loose")
+        tu = ar.new(K, steps * I)
+        tx = ar.new(K, steps * 2) if want_states else None
+        at = (ar.read(new_last_targets, 2 * steps, None, "loose"), ar.read(sequences, steps * H * I, None, "loose"),
+              ar.read(states, 2 * steps, None, "loose"), C.byref(tan))
         if plant_call:
-            pl = self._plant(plant, None, ptr, I, steps)   # (the disturbance itself is not read: the states are recorded)
-            self._check(self._lib.tpc_mpc_rollout_plant_forward(self._h, C.byref(p), C.byref(io), C.byref(pl), int(steps),
-                                                                ptr(new_last_targets, 2 * steps),
-                                                                ptr(sequences, steps * H * I), ptr(states, 2 * steps),
-                                                                C.byref(tan), C.byref(ptan), optr(tu),
-                                                                optr(tx), C.byref(flags) if want_flags else None, mem,
-                                                                stream))
-            self.last_flags = flags.value
-            return tu, tx
-        self._check(self._lib.tpc_mpc_rollout_forward(self._h, C.byref(p), C.byref(io), int(steps),
-                                                      ptr(new_last_targets, 2 * steps),
-                                                      ptr(sequences, steps * H * I), ptr(states, 2 * steps),
-                                                      C.byref(tan), optr(tu), optr(tx),
-                                                      C.byref(flags) if want_flags else None, mem, stream))
-        self.last_flags = flags.value
+            pl = self._plant(ar, plant, None, I, steps, "loose")   # (the disturbance itself is not read: the states are recorded)
+            entry = self._lib.tpc_mpc_rollout_plant_forward
+            args = (C.byref(io), C.byref(pl), int(steps), *at, C.byref(ptan))
+        else:
+            entry, args = self._lib.tpc_mpc_rollout_forward, (C.byref(io), int(steps), *at)
+        self._run(entry, p, ar, *args, ar.addr(tu), ar.addr(tx), want_flags=want_flags)
         return tu, tx
 
     def follow_batch(self, pos_x, pos_y, dir_x, dir_y, velocity, count, car_velocity, look_ahead,
@@ -1256,34 +735,8 @@ class MpcSolver:
         car_velocity, look_ahead float32 [n]; lookup: optional (x, y) float32 CUDA tensors of the
         velocity lookup table.  Returns (steering_front f64, steering_rear f64, target_speed f32,
         target_distance f32[, iters])."""
-        import torch
-        p = self._params(**over)
-        P, n = pos_x.shape
-        dev = pos_x.device
-        for tns in (pos_x, pos_y, dir_x, dir_y, velocity):
-            if not (tns.is_cuda and tns.dtype == torch.float32 and tns.is_contiguous() and tuple(tns.shape) == (P, n)):
-                raise ValueError("trajectory arrays must be contiguous float32 CUDA tensors [max_points, n]")
-        for tns, dt in ((count, torch.int32), (car_velocity, torch.float32), (look_ahead, torch.float32)):
-            if not (tns.is_cuda and tns.dtype == dt and tns.is_contiguous() and tns.numel() == n):
-                raise ValueError("per-instance arrays must be contiguous CUDA tensors of length n")
-        tr = capi.Trajectories(n=n, ld=n, max_points=P, pos_x=pos_x.data_ptr(), pos_y=pos_y.data_ptr(),
-                               dir_x=dir_x.data_ptr(), dir_y=dir_y.data_ptr(), velocity=velocity.data_ptr(),
-                               count=count.data_ptr(), car_velocity=car_velocity.data_ptr(),
-                               look_ahead=look_ahead.data_ptr())
-        front = torch.empty(n, dtype=torch.float64, device=dev)
-        rear = torch.empty(n, dtype=torch.float64, device=dev)
-        tspeed = torch.empty(n, dtype=torch.float32, device=dev)
-        tdist = torch.empty(n, dtype=torch.float32, device=dev)
-        iters = torch.empty(n, dtype=torch.int32, device=dev) if want_iters else None
-        lx, ly, ln = (None, None, 0) if lookup is None else (lookup[0].data_ptr(), lookup[1].data_ptr(), lookup[0].numel())
-        flags = C.c_uint32(0)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        self._check(self._lib.tpc_mpc_follow_batch(self._h, C.byref(p), C.byref(tr), lx, ly, ln,
-                                                   front.data_ptr(), rear.data_ptr(), tspeed.data_ptr(),
-                                                   tdist.data_ptr(), iters.data_ptr() if want_iters else None,
-                                                   C.byref(flags), stream))
-        self.last_flags = flags.value
-        return (front, rear, tspeed, tdist, iters) if want_iters else (front, rear, tspeed, tdist)
+        return self._follow(False, pos_x, pos_y, dir_x, dir_y, velocity, count, car_velocity, look_ahead,
+                            step_spacing=None, lookup=lookup, want_iters=want_iters, want_targets=False, **over)
 
     def follow_batch_horizon(self, pos_x, pos_y, dir_x, dir_y, velocity, count, car_velocity, look_ahead,
                              step_spacing=None, lookup=None, want_iters: bool = False,
@@ -1292,41 +745,31 @@ class MpcSolver:
         step t's target is the polyline point at arc length look_ahead + t * spacing.  step_spacing:
         optional float32 CUDA tensor [n] (None: |v| * step_size).  Returns (front, rear, target_speed,
         target_distance[, targets f64 [2H, n]][, iters])."""
-        import torch
+        return self._follow(True, pos_x, pos_y, dir_x, dir_y, velocity, count, car_velocity, look_ahead,
+                            step_spacing=step_spacing, lookup=lookup, want_iters=want_iters, want_targets=want_targets,
+                            **over)
+
+    def _follow(self, horizon, pos_x, pos_y, dir_x, dir_y, velocity, count, car_velocity, look_ahead, *, step_spacing,
+                lookup, want_iters, want_targets, **over):
+        """follow_batch (tpc_mpc_follow_batch) and, with horizon=True, follow_batch_horizon with its two options"""
         p = self._params(**over)
         P, n = pos_x.shape
-        dev = pos_x.device
-        for tns in (pos_x, pos_y, dir_x, dir_y, velocity):
-            if not (tns.is_cuda and tns.dtype == torch.float32 and tns.is_contiguous() and tuple(tns.shape) == (P, n)):
-                raise ValueError("trajectory arrays must be contiguous float32 CUDA tensors [max_points, n]")
-        per = [(count, torch.int32), (car_velocity, torch.float32), (look_ahead, torch.float32)]
-        if step_spacing is not None:
-            per.append((step_spacing, torch.float32))
-        for tns, dt in per:
-            if not (tns.is_cuda and tns.dtype == dt and tns.is_contiguous() and tns.numel() == n):
-                raise ValueError("per-instance arrays must be contiguous CUDA tensors of length n")
-        tr = capi.Trajectories(n=n, ld=n, max_points=P, pos_x=pos_x.data_ptr(), pos_y=pos_y.data_ptr(),
-                               dir_x=dir_x.data_ptr(), dir_y=dir_y.data_ptr(), velocity=velocity.data_ptr(),
-                               count=count.data_ptr(), car_velocity=car_velocity.data_ptr(),
-                               look_ahead=look_ahead.data_ptr())
-        front = torch.empty(n, dtype=torch.float64, device=dev)
-        rear = torch.empty(n, dtype=torch.float64, device=dev)
-        tspeed = torch.empty(n, dtype=torch.float32, device=dev)
-        tdist = torch.empty(n, dtype=torch.float32, device=dev)
-        targets = torch.empty((2 * p.horizon, n), dtype=torch.float64, device=dev) if want_targets else None
-        iters = torch.empty(n, dtype=torch.int32, device=dev) if want_iters else None
+        ar = self._device_only(Arrays(pos_x, n, np.float32))
+        tr = capi.Trajectories(n=n, ld=n, max_points=P, pos_x=ar.read(pos_x, P), pos_y=ar.read(pos_y, P),
+                               dir_x=ar.read(dir_x, P), dir_y=ar.read(dir_y, P), velocity=ar.read(velocity, P),
+                               count=ar.read(count, None, _I32, "length"),
+                               car_velocity=ar.read(car_velocity, match="length"),
+                               look_ahead=ar.read(look_ahead, match="length"))
+        front, rear = ar.new(dtype=np.float64), ar.new(dtype=np.float64)
+        tspeed, tdist = ar.new(), ar.new()
+        targets = ar.new(2 * p.horizon, dtype=np.float64) if want_targets else None
+        iters = ar.new(dtype=_I32) if want_iters else None
         lx, ly, ln = (None, None, 0) if lookup is None else (lookup[0].data_ptr(), lookup[1].data_ptr(), lookup[0].numel())
-        flags = C.c_uint32(0)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        self._check(self._lib.tpc_mpc_follow_batch_horizon(
-            self._h, C.byref(p), C.byref(tr), step_spacing.data_ptr() if step_spacing is not None else None,
-            lx, ly, ln, front.data_ptr(), rear.data_ptr(), tspeed.data_ptr(), tdist.data_ptr(),
-            targets.data_ptr() if want_targets else None, iters.data_ptr() if want_iters else None,
-            C.byref(flags), stream))
-        self.last_flags = flags.value
-        out = [front, rear, tspeed, tdist]
-        if want_targets:
-            out.append(targets)
-        if want_iters:
-            out.append(iters)
-        return tuple(out)
+        outs = (ar.addr(front), ar.addr(rear), ar.addr(tspeed), ar.addr(tdist))
+        if horizon:
+            self._run(self._lib.tpc_mpc_follow_batch_horizon, p, ar, C.byref(tr), ar.read(step_spacing, match="length"),
+                      lx, ly, ln, *outs, ar.addr(targets), ar.addr(iters), mem=False)
+        else:
+            self._run(self._lib.tpc_mpc_follow_batch, p, ar, C.byref(tr), lx, ly, ln, *outs, ar.addr(iters), mem=False)
+        out = (front, rear, tspeed, tdist) + ((targets,) if want_targets else ())
+        return out + (iters,) if want_iters else out
