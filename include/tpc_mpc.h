@@ -597,8 +597,8 @@ int tpc_mpc_solve_batch_compact_exact_backward(tpc_mpc_handle h, const tpc_mpc_p
  *   [10] stays their column sum over the contributing instances, by the same fixed-order reduction -- the gradient of
  *   a parameter the caller broadcast to every instance.  With constant rows every output equals the shared entry's bits.
  * Everything else -- the argument checks, n == 0, the optional outputs, asynchronous DEVICE calls with flags_out == NULL,
- * the host-only handle -- is as the two entries above have it.  Kernels: compact_exact_rows_* (csrc/mpc_newton_compact.hip)
- * and compact_grad_rows_* (csrc/mpc_compact_grad.hip), one lane per instance, the ten values loaded once per lane. */
+ * the host-only handle -- is as the two entries above have it.  Kernels: the ROWS instantiations of the parents'
+ * (csrc/mpc_newton_compact.hip, csrc/mpc_compact_grad.hip), one lane per instance, the ten values loaded once per lane. */
 int tpc_mpc_solve_batch_compact_exact_rows(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t n, const void* v,
                                            const void* delta_y, const void* delta_phi,
                                            const void* params_rows /* [10], ld n */, const tpc_mpc_polish* q,
@@ -637,7 +637,7 @@ int tpc_mpc_solve_batch_compact_exact_rows_backward(tpc_mpc_handle h, const tpc_
  *   unverified instance returns (0, 0), a zero sequence and status -1, so the next call finds a column of zeros there.
  *   Aliasing.  sequence_out == start is allowed (update the stored sequences in place): a lane reads its whole column
  *   before its first write.  No other overlap of an input with an output is.
- * Kernels: compact_exact_warm_* (csrc/mpc_newton_compact.hip), launched as the parents' -- one lane per instance, the
+ * Kernels: the WARM instantiations of the parents' (csrc/mpc_newton_compact.hip), launched as the parents' -- one lane per instance, the
  * start loaded once; at horizons 4 and 5 the per-step values stay in registers. */
 int tpc_mpc_solve_batch_compact_exact_from(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t n, const void* v,
                                            const void* delta_y, const void* delta_phi,

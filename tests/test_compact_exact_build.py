@@ -1,68 +1,43 @@
 """CPU test of the code objects of the exact compact solve (csrc/mpc_newton_compact.hip): the kernels are in the library
 for gfx950; the register kernels (horizon at compile time, H = 4 and 5) keep their per-step values in registers -- no
-private segment, no spilled register, no dynamic stack, at most 256 VGPRs; the workspace kernel (run-time H) and the
-fallback's gather-expand / scatter kernels have no private segment and no spill either.
+private segment, no spilled register, no dynamic stack, at most 256 VGPRs and AGPRs; the workspace kernel (run-time H)
+and the fallback's gather-expand / scatter kernels have no private segment and no spill either.
 
-Measured on this code: 155 VGPRs at H = 4, 176 at H = 5, 93 for the workspace kernel, 70 / 12 gather / scatter."""
+Measured on this code: 130 VGPRs at H = 4, 147 at H = 5, 78 for the workspace kernel, 72 / 12 gather / scatter."""
 import os
-import re
-import subprocess
-import sys
-import tempfile
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-REGISTER_HORIZONS = (4, 5)
+from tests.model import code_objects as co
 
-
-def _metadata():
-    sys.path.insert(0, os.path.join(ROOT, "scripts"))
-    import check_loop_scratch
-    lib = os.path.join(ROOT, "trajectory_controller_amd", "lib", "libtpc_mpc.so")
-    meta = {}
-    with tempfile.TemporaryDirectory() as tmp:
-        for co in check_loop_scratch.device_objects(lib, tmp):
-            notes = subprocess.run([READELF, "--notes", co], capture_output=True, text=True, check=True).stdout
-            if "compact_exact_" not in notes:
-                continue
-            assert "amdgcn-amd-amdhsa--gfx950" in notes
-            for block in notes.split("- .agpr_count")[1:]:     # one block of fields per kernel
-                fields = dict(re.findall(r"^\s+(\.[a-z_]+):\s+(\S+)\s*$", block, flags=re.M))
-                m = re.search(r"(compact_exact_[a-z_]+_kernel)(?:ILi(\d+)E)?", fields.get(".name", ""))
-                if m:
-                    meta[(m.group(1), int(m.group(2) or 0))] = fields
-    return meta
+COLD = co.family("compact_exact", False, False)      # <ROWS, WARM> = <false, false>: [workspace, register H = 4, 5]
+FALLBACK = [("compact_exact_gather_kernel", ()), ("compact_exact_scatter_kernel", ())]
 
 
 @pytest.fixture(scope="module")
 def meta():
-    if not os.path.exists(READELF):
+    if not os.path.exists(co.READELF):
         pytest.skip("needs llvm-readelf")
-    return _metadata()
+    return co.metadata(r"compact_exact_[a-z_]+_kernel")
 
 
 def test_kernels_are_in_the_library(meta):
-    want = {("compact_exact_ws_kernel", 0), ("compact_exact_gather_kernel", 0), ("compact_exact_scatter_kernel", 0)}
-    want |= {("compact_exact_reg_kernel", H) for H in REGISTER_HORIZONS}
-    assert want <= set(meta), sorted(meta)
+    assert set(COLD + FALLBACK) <= set(meta), sorted(meta)
 
 
 def test_register_kernels_hold_the_horizon_in_registers(meta):
-    for H in REGISTER_HORIZONS:
-        f = meta[("compact_exact_reg_kernel", H)]
-        print(f"H={H}", {k: f[k] for k in (".vgpr_count", ".sgpr_count", ".private_segment_fixed_size",
-                                           ".vgpr_spill_count", ".sgpr_spill_count")})
-        assert int(f[".private_segment_fixed_size"]) == 0, (H, f)
-        assert int(f[".vgpr_spill_count"]) == 0, (H, f)
-        assert f[".uses_dynamic_stack"] == "false", (H, f)
-        assert int(f[".vgpr_count"]) <= 256, (H, f)
+    for key in COLD[1:]:
+        f = meta[key]
+        print(key, co.show(f))
+        assert int(f[".private_segment_fixed_size"]) == 0, (key, f)
+        assert int(f[".vgpr_spill_count"]) == 0, (key, f)
+        assert f[".uses_dynamic_stack"] == "false", (key, f)
+        assert int(f[".vgpr_count"]) + int(f[".agpr_count"]) <= 256, (key, f)
 
 
 def test_workspace_and_fallback_kernels_use_no_private_memory(meta):
-    for name in ("compact_exact_ws_kernel", "compact_exact_gather_kernel", "compact_exact_scatter_kernel"):
-        f = meta[(name, 0)]
-        print(name, {k: f[k] for k in (".vgpr_count", ".sgpr_count", ".private_segment_fixed_size", ".vgpr_spill_count")})
-        assert int(f[".private_segment_fixed_size"]) == 0 and int(f[".vgpr_spill_count"]) == 0, (name, f)
-        assert f[".uses_dynamic_stack"] == "false", (name, f)
+    for key in COLD[:1] + FALLBACK:
+        f = meta[key]
+        print(key, co.show(f))
+        assert int(f[".private_segment_fixed_size"]) == 0 and int(f[".vgpr_spill_count"]) == 0, (key, f)
+        assert f[".uses_dynamic_stack"] == "false", (key, f)

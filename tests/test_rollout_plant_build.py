@@ -4,8 +4,8 @@ parent's occupancy bracket -- the plant's values and tangents are read at the st
 with no private segment and no spilled register, and the parents' figures are what they were before the plant existed
 (DESIGN.md sections 15-17).
 
-Measured on this code: Newton 127 / 96 VGPRs (I = 2 / 1), backward 207 / 172, tangent 160 / 127, fused polish + step
-125 / 92, all without private segment or spills."""
+Measured on this code: Newton 119 / 90 VGPRs (I = 2 / 1), backward 207 / 172, tangent 160 / 127, fused polish + step
+112 / 81, all without private segment or spills."""
 import os
 import re
 import subprocess
@@ -23,9 +23,10 @@ PLANT_BRACKETS = {("rollout_plant_bwd_kernel", 2): 256, ("rollout_plant_bwd_kern
                   ("rollout_plant_fwd_kernel", 2): 168, ("rollout_plant_fwd_kernel", 1): 128,
                   ("rollout_plant_newton_kernel", 2): 128, ("rollout_plant_newton_kernel", 1): 96,
                   ("rollout_plant_polish_step_kernel", 2): 128, ("rollout_plant_polish_step_kernel", 1): 128}
-# the parents' recorded figures (172 backward I = 2; 160 / 126 tangent; 127 / 96 Newton)
+# the parents' recorded figures (172 backward I = 2; 160 / 126 tangent; 118 / 90 Newton, on the polish's
+# shared newton_rounds)
 PARENT_VGPRS = {("rollout_grad_kernel", 2): 172, ("rollout_tangent_kernel", 2): 160, ("rollout_tangent_kernel", 1): 126,
-                ("rollout_newton_kernel", 2): 127, ("rollout_newton_kernel", 1): 96}
+                ("rollout_newton_kernel", 2): 118, ("rollout_newton_kernel", 1): 90}
 
 
 def _metadata():

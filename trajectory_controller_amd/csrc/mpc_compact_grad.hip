@@ -1,12 +1,12 @@
 // Backward pass of the exact compact solve (tpc_mpc_solve_batch_compact_exact_backward): one lane per instance runs the
 // adjoint sweep of the general form on the reference controller's model, built in registers from v, and folds the
 // chain rule of that model building in registers (mpc_compact_grad_model.h) -- 3 + 2H doubles and the incoming gradient
-// in, three doubles out.  Two kernel shapes on the same function, so the same bits:
-//   compact_grad_ws_kernel        run-time H (1 .. 64), per-step values in the handle's gradient workspace
-//                                 ([quantity][step][instance]), as the general backward keeps them
-//   compact_grad_reg_kernel<HC>   horizons 4 and 5: the horizon at compile time, every loop over it unrolled, the
-//                                 per-step values in an array of the lane's own that the compiler keeps in registers --
-//                                 no workspace memory is touched
+// in, three doubles out.  Two kernel templates on the same function, so the same bits:
+//   compact_grad_ws_kernel<ROWS>        run-time H (1 .. 64), per-step values in the handle's gradient workspace
+//                                       ([quantity][step][instance]), as the general backward keeps them
+//   compact_grad_reg_kernel<HC, ROWS>   horizons 4 and 5: the horizon at compile time, every loop over it unrolled, the
+//                                       per-step values in an array of the lane's own that the compiler keeps in
+//                                       registers -- no workspace memory is touched
 // The gradients of the ten shared parameters are summed over the batch without floating-point atomics, in an order that
 // depends on n alone: a fixed butterfly over the lanes of a wavefront, the block's wavefronts in order through LDS, one
 // partial row per block with plain stores, and compact_grad_reduce_kernel (one block) over the blocks in a fixed order.
@@ -14,6 +14,7 @@
 // the same per-instance bits.
 #include "mpc_compact_grad.h"
 
+#include <type_traits>
 #include <vector>
 
 namespace tpc {
@@ -63,30 +64,19 @@ __device__ __forceinline__ void lane_body(const cgrad::Args& a, int H, double* w
     if (partials) block_partials(row, partials);   // uniform over the block
 }
 
+// ROWS (tpc_mpc_solve_batch_compact_exact_rows_backward): the lane loads its instance's ten model values from a.params,
+// and its row is the gradient with respect to them
+template <bool ROWS>
 __global__ __launch_bounds__(256) void compact_grad_ws_kernel(cgrad::Args a, int H, double* ws, uint32_t* flags,
                                                               double* partials) {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    lane_body<0>(a, H, ws + (k < a.n ? k : 0), a.n, flags, partials);
+    lane_body<0, ROWS>(a, H, ws + (k < a.n ? k : 0), a.n, flags, partials);
 }
 
-template <int HC>
+template <int HC, bool ROWS>
 __global__ __launch_bounds__(256) void compact_grad_reg_kernel(cgrad::Args a, uint32_t* flags, double* partials) {
     double regs[cgrad::kSlots * HC];   // every index into it is a constant once the horizon's loops are unrolled
-    lane_body<HC>(a, HC, regs, 1, flags, partials);
-}
-
-// ... and the same two shapes for tpc_mpc_solve_batch_compact_exact_rows_backward: the lane loads its instance's ten
-// model values from a.params, and its row is the gradient with respect to them
-__global__ __launch_bounds__(256) void compact_grad_rows_ws_kernel(cgrad::Args a, int H, double* ws, uint32_t* flags,
-                                                                   double* partials) {
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    lane_body<0, true>(a, H, ws + (k < a.n ? k : 0), a.n, flags, partials);
-}
-
-template <int HC>
-__global__ __launch_bounds__(256) void compact_grad_rows_reg_kernel(cgrad::Args a, uint32_t* flags, double* partials) {
-    double regs[cgrad::kSlots * HC];
-    lane_body<HC, true>(a, HC, regs, 1, flags, partials);
+    lane_body<HC, ROWS>(a, HC, regs, 1, flags, partials);
 }
 
 // one block: dparams[c] = the sum of partials[c * blocks + b] over b, in an order that depends on `blocks` alone
@@ -130,13 +120,14 @@ hipError_t compact_grad(int H, const cgrad::Args& a, void* ws, double* partials,
     const int block = rollout_grad_block(a.n);
     const unsigned grid = (unsigned)compact_grad_blocks(a.n);
     double* part = dparams ? partials : nullptr;
-    if (a.params) {
-        if (H == 4) hipLaunchKernelGGL(compact_grad_rows_reg_kernel<4>, dim3(grid), dim3(block), 0, s, a, flags, part);
-        else if (H == 5) hipLaunchKernelGGL(compact_grad_rows_reg_kernel<5>, dim3(grid), dim3(block), 0, s, a, flags, part);
-        else hipLaunchKernelGGL(compact_grad_rows_ws_kernel, dim3(grid), dim3(block), 0, s, a, H, (double*)ws, flags, part);
-    } else if (H == 4) hipLaunchKernelGGL(compact_grad_reg_kernel<4>, dim3(grid), dim3(block), 0, s, a, flags, part);
-    else if (H == 5) hipLaunchKernelGGL(compact_grad_reg_kernel<5>, dim3(grid), dim3(block), 0, s, a, flags, part);
-    else hipLaunchKernelGGL(compact_grad_ws_kernel, dim3(grid), dim3(block), 0, s, a, H, (double*)ws, flags, part);
+    auto launch = [&](auto rows) {
+        constexpr bool R = decltype(rows)::value;
+        if (H == 4) hipLaunchKernelGGL((compact_grad_reg_kernel<4, R>), dim3(grid), dim3(block), 0, s, a, flags, part);
+        else if (H == 5) hipLaunchKernelGGL((compact_grad_reg_kernel<5, R>), dim3(grid), dim3(block), 0, s, a, flags, part);
+        else hipLaunchKernelGGL((compact_grad_ws_kernel<R>), dim3(grid), dim3(block), 0, s, a, H, (double*)ws, flags, part);
+    };
+    if (a.params) launch(std::true_type{});
+    else launch(std::false_type{});
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || !dparams) return e;
     hipLaunchKernelGGL(compact_grad_reduce_kernel, dim3(1), dim3(kReduceBlock), 0, s, part, (int)grid, dparams);

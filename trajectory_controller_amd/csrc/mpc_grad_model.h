@@ -125,7 +125,7 @@ struct Sums {
 // by free_at(j, u, g) on the values u(t, j), g(t, j) that u_at and g_at read.  Pass 1 reads step t's u and g before it
 // writes step t's slots, so g may live in the feed-forward's slot (2 I + j, t).  Leaves x_t, dx_t, w_t in the step's slots
 // and x_H, dx_H in (x0, x1, d0, d1); clears fin if a u or g read is not finite.  Shared by qp_step() and by
-// polish_instance() (mpc_polish_model.h).
+// polish::newton_rounds() (mpc_polish_model.h).
 template <int I, class U, class G, class FR>
 TPC_GRAD_HD void riccati_passes(const Model& m, int H, double xs0, double xs1, U u_at, G g_at, FR free_at, double* ws,
                                 int64_t wn, bool& fin, double& x0, double& x1, double& d0, double& d1) {

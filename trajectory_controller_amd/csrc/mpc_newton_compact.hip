@@ -1,22 +1,23 @@
 // The exact compact solve (tpc_mpc_solve_batch_compact_exact): one lane per instance runs the Newton rounds of the
 // polish from U = 0 on the reference controller's model, built in registers from v (mpc_newton_compact_model.h) --
-// three doubles in, two out, one launch.  Two kernel shapes on the same function, so the same bits:
-//   compact_exact_ws_kernel        run-time H (1 .. 64), per-step values in the handle's gradient workspace
-//                                  ([quantity][step][instance]), as the polish keeps them
-//   compact_exact_reg_kernel<HC>   the reference's horizons 4 and 5: the horizon at compile time, every loop over it
-//                                  unrolled, the per-step values in an array of the lane's own that the compiler keeps
-//                                  in registers -- no workspace memory is touched
-// compact_exact_rows_ws_kernel and compact_exact_rows_reg_kernel<HC> are the same two for
-// tpc_mpc_solve_batch_compact_exact_rows: each lane loads the ten model values of its own instance (Args::params) where
-// the kernels above read the call's from the kernel arguments.
-// compact_exact_warm_* are the same four for tpc_mpc_solve_batch_compact_exact_from: the lane starts from its column of
-// Args::start (one pass: load, clamp, track finiteness; a non-finite column is rewritten with the cold start).
+// three doubles in, two out, one launch.  Two kernel templates on the same function, so the same bits:
+//   compact_exact_ws_kernel<ROWS, WARM>        run-time H (1 .. 64), per-step values in the handle's gradient workspace
+//                                              ([quantity][step][instance]), as the polish keeps them
+//   compact_exact_reg_kernel<HC, ROWS, WARM>   the reference's horizons 4 and 5: the horizon at compile time, every loop
+//                                              over it unrolled, the per-step values in an array of the lane's own that
+//                                              the compiler keeps in registers -- no workspace memory is touched
+// ROWS (tpc_mpc_solve_batch_compact_exact_rows): each lane loads the ten model values of its own instance (Args::params)
+// where the others read the call's from the kernel arguments.  WARM (tpc_mpc_solve_batch_compact_exact_from): the lane
+// starts from its column of Args::start (one pass: load, clamp, track finiteness; a non-finite column is rewritten with
+// the cold start).  Each of the twelve instantiations is a kernel of its own: the cold entries' code objects do not
+// depend on the warm ones.
 // The instances phase 1 could not verify are collected for the fallback (one atomicAdd per wavefront, as
 // mpc_rollout_newton.hip); gather-expand writes their general form into a compact batch for tpc_mpc_solve_batch_general
 // and tpc_mpc_polish_batch_general, scatter brings the results back.  Explicit fma() only (-ffp-contract=off): device and
 // host path give the same bits, and both equal tpc_mpc_polish_batch_general on the expanded arrays.
 #include "mpc_newton_compact.h"
 
+#include <type_traits>
 #include <vector>
 
 namespace tpc {
@@ -39,72 +40,31 @@ __device__ __forceinline__ void exact_finish(const cexact::Args& a, int64_t k, u
     if (fb) a.fb_index[base + __popcll(m & ((1ull << lane) - 1ull))] = (int32_t)k;
 }
 
+template <bool ROWS, bool WARM>
 __global__ __launch_bounds__(256) void compact_exact_ws_kernel(cexact::Args a, int H, double* ws, uint32_t* flags) {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= a.n) return;
-    const uint32_t f = cexact::exact_instance<0>(a, H, k, ws + k, a.n);
+    const uint32_t f = cexact::exact_instance<0, ROWS, WARM>(a, H, k, ws + k, a.n);
     exact_finish(a, k, f, flags);
 }
 
-template <int HC>
+template <int HC, bool ROWS, bool WARM>
 __global__ __launch_bounds__(256) void compact_exact_reg_kernel(cexact::Args a, uint32_t* flags) {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= a.n) return;
     double regs[cexact::kSlots * HC];   // every index into it is a constant once the horizon's loops are unrolled
-    const uint32_t f = cexact::exact_instance<HC>(a, HC, k, regs, 1);
+    const uint32_t f = cexact::exact_instance<HC, ROWS, WARM>(a, HC, k, regs, 1);
     exact_finish(a, k, f, flags);
 }
 
-// ... and the same two shapes for the rows entry: the lane loads its instance's ten model values from a.params
-__global__ __launch_bounds__(256) void compact_exact_rows_ws_kernel(cexact::Args a, int H, double* ws, uint32_t* flags) {
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= a.n) return;
-    const uint32_t f = cexact::exact_instance<0, true>(a, H, k, ws + k, a.n);
-    exact_finish(a, k, f, flags);
-}
-
-template <int HC>
-__global__ __launch_bounds__(256) void compact_exact_rows_reg_kernel(cexact::Args a, uint32_t* flags) {
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= a.n) return;
-    double regs[cexact::kSlots * HC];
-    const uint32_t f = cexact::exact_instance<HC, true>(a, HC, k, regs, 1);
-    exact_finish(a, k, f, flags);
-}
-
-// tpc_mpc_solve_batch_compact_exact_from: the four shapes above with the working copy started from column k of a.start
-// (exact_instance's WARM) -- kernels of their own, so that the parents' code objects stay as they are
-__global__ __launch_bounds__(256) void compact_exact_warm_ws_kernel(cexact::Args a, int H, double* ws, uint32_t* flags) {
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= a.n) return;
-    const uint32_t f = cexact::exact_instance<0, false, true>(a, H, k, ws + k, a.n);
-    exact_finish(a, k, f, flags);
-}
-
-template <int HC>
-__global__ __launch_bounds__(256) void compact_exact_warm_reg_kernel(cexact::Args a, uint32_t* flags) {
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= a.n) return;
-    double regs[cexact::kSlots * HC];
-    const uint32_t f = cexact::exact_instance<HC, false, true>(a, HC, k, regs, 1);
-    exact_finish(a, k, f, flags);
-}
-
-__global__ __launch_bounds__(256) void compact_exact_warm_rows_ws_kernel(cexact::Args a, int H, double* ws,
-                                                                         uint32_t* flags) {
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= a.n) return;
-    const uint32_t f = cexact::exact_instance<0, true, true>(a, H, k, ws + k, a.n);
-    exact_finish(a, k, f, flags);
-}
-
-template <int HC>
-__global__ __launch_bounds__(256) void compact_exact_warm_rows_reg_kernel(cexact::Args a, uint32_t* flags) {
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= a.n) return;
-    double regs[cexact::kSlots * HC];
-    const uint32_t f = cexact::exact_instance<HC, true, true>(a, HC, k, regs, 1);
-    exact_finish(a, k, f, flags);
+// The entry a call is, as compile-time constants: f(ROWS, WARM) with ROWS = per-instance parameters given, WARM = a start
+// given.  The launcher and the host path pick their instantiation through it.
+template <class F>
+void with_entry(const cexact::Args& a, F f) {
+    using yes = std::true_type;
+    using no = std::false_type;
+    if (a.params) a.start ? f(yes{}, yes{}) : f(yes{}, no{});
+    else a.start ? f(no{}, yes{}) : f(no{}, no{});
 }
 
 __global__ __launch_bounds__(256) void compact_exact_gather_kernel(cexact::Args a, CompactExactBatch b) {
@@ -153,27 +113,12 @@ hipError_t compact_exact(int H, const cexact::Args& a, void* ws, uint32_t* flags
     if (a.n <= 0) return hipSuccess;
     const int block = rollout_grad_block(a.n);
     const unsigned grid = (unsigned)((a.n + block - 1) / block);
-    if (a.start) {   // the warm entry: the same launch shape on the warm kernels
-        if (a.params) {
-            if (H == 4) hipLaunchKernelGGL(compact_exact_warm_rows_reg_kernel<4>, dim3(grid), dim3(block), 0, s, a, flags);
-            else if (H == 5) hipLaunchKernelGGL(compact_exact_warm_rows_reg_kernel<5>, dim3(grid), dim3(block), 0, s, a, flags);
-            else hipLaunchKernelGGL(compact_exact_warm_rows_ws_kernel, dim3(grid), dim3(block), 0, s, a, H, (double*)ws, flags);
-        } else {
-            if (H == 4) hipLaunchKernelGGL(compact_exact_warm_reg_kernel<4>, dim3(grid), dim3(block), 0, s, a, flags);
-            else if (H == 5) hipLaunchKernelGGL(compact_exact_warm_reg_kernel<5>, dim3(grid), dim3(block), 0, s, a, flags);
-            else hipLaunchKernelGGL(compact_exact_warm_ws_kernel, dim3(grid), dim3(block), 0, s, a, H, (double*)ws, flags);
-        }
-        return hipGetLastError();
-    }
-    if (a.params) {
-        if (H == 4) hipLaunchKernelGGL(compact_exact_rows_reg_kernel<4>, dim3(grid), dim3(block), 0, s, a, flags);
-        else if (H == 5) hipLaunchKernelGGL(compact_exact_rows_reg_kernel<5>, dim3(grid), dim3(block), 0, s, a, flags);
-        else hipLaunchKernelGGL(compact_exact_rows_ws_kernel, dim3(grid), dim3(block), 0, s, a, H, (double*)ws, flags);
-        return hipGetLastError();
-    }
-    if (H == 4) hipLaunchKernelGGL(compact_exact_reg_kernel<4>, dim3(grid), dim3(block), 0, s, a, flags);
-    else if (H == 5) hipLaunchKernelGGL(compact_exact_reg_kernel<5>, dim3(grid), dim3(block), 0, s, a, flags);
-    else hipLaunchKernelGGL(compact_exact_ws_kernel, dim3(grid), dim3(block), 0, s, a, H, (double*)ws, flags);
+    with_entry(a, [&](auto rows, auto warm) {
+        constexpr bool R = decltype(rows)::value, W = decltype(warm)::value;
+        if (H == 4) hipLaunchKernelGGL((compact_exact_reg_kernel<4, R, W>), dim3(grid), dim3(block), 0, s, a, flags);
+        else if (H == 5) hipLaunchKernelGGL((compact_exact_reg_kernel<5, R, W>), dim3(grid), dim3(block), 0, s, a, flags);
+        else hipLaunchKernelGGL((compact_exact_ws_kernel<R, W>), dim3(grid), dim3(block), 0, s, a, H, (double*)ws, flags);
+    });
     return hipGetLastError();
 }
 
@@ -181,13 +126,13 @@ hipError_t compact_exact(int H, const cexact::Args& a, void* ws, uint32_t* flags
 uint32_t compact_exact_host(int H, const cexact::Args& a) {
     std::vector<double> ws((size_t)cexact::kSlots * H);
     uint32_t flags = 0;
-    for (int64_t k = 0; k < a.n; ++k) {
-        const uint32_t f = a.start ? (a.params ? cexact::exact_instance<0, true, true>(a, H, k, ws.data(), 1)
-                                               : cexact::exact_instance<0, false, true>(a, H, k, ws.data(), 1))
-                           : a.params ? cexact::exact_instance<0, true>(a, H, k, ws.data(), 1)
-                                      : cexact::exact_instance<0>(a, H, k, ws.data(), 1);
-        flags |= a.raise_not_polished ? f : (f & ~0x8u);
-    }
+    with_entry(a, [&](auto rows, auto warm) {
+        constexpr bool R = decltype(rows)::value, W = decltype(warm)::value;
+        for (int64_t k = 0; k < a.n; ++k) {
+            const uint32_t f = cexact::exact_instance<0, R, W>(a, H, k, ws.data(), 1);
+            flags |= a.raise_not_polished ? f : (f & ~0x8u);
+        }
+    });
     return flags;
 }
 

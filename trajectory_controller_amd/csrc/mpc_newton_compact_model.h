@@ -1,16 +1,16 @@
 // The exact compact solve (tpc_mpc_solve_batch_compact_exact, include/tpc_mpc.h): phase 1 of ONE instance, shared by
-// the gfx950 kernels (mpc_newton_compact.hip) and the host path of the same entry.  It is polish::polish_instance<2>
-// (mpc_polish_model.h) restated for the reference controller's model, started from U = 0:
+// the gfx950 kernels (mpc_newton_compact.hip) and the host path of the same entry.  It runs the polish's rounds,
+// polish::newton_rounds<2> (mpc_polish_model.h), on the reference controller's model, started from U = 0:
 //   - the model comes from v and the call's parameters, in registers: A = [1, Tv; 0, 1], B = [0, Tv; Tv/l, -Tv/l],
 //     C = 0, x0 = 0, every target (dy, dphi) -- no model or target array is read;
 //   - the per-step values go through one pointer, ws[(q * H + t) * wn]: the handle's gradient workspace (run-time H),
 //     or, with a compile-time horizon HC, an array of the lane's own whose every index is then a constant, so that it
 //     lives in registers (a private array indexed by a run-time step lands in scratch).
-// The operation sequence is the general form's on the expanded values, operation for operation -- the "+ C" and the x0
-// terms included: fma(a, b, +0) is not a * b when the product is -0 -- so the result equals
-// tpc_mpc_polish_batch_general on the expanded arrays with zero controls bit for bit (tests/test_compact_exact_host.py).
+// The rounds are the general form's own function on the expanded values -- the "+ C" and the x0 terms included:
+// fma(a, b, +0) is not a * b when the product is -0 -- so the result equals tpc_mpc_polish_batch_general on the expanded
+// arrays with zero controls bit for bit (tests/test_compact_exact_host.py).  What is this header's own: the model, the
+// start (cold or WARM), the outputs, and which inputs count as non-finite.
 // Every fused operation is an explicit fma() and the unit is built with -ffp-contract=off, as mpc_polish_model.h.
-// The Riccati passes are grad::riccati_passes, as they are.
 #pragma once
 
 #include "mpc_polish_model.h"
@@ -18,9 +18,7 @@
 namespace tpc {
 namespace cexact {
 
-using grad::gabs;
 using grad::gfinite;
-using grad::gfma;
 using polish::clampd;
 
 // v, dy, dphi [n]; the outputs: front, rear [n], seq [H*2] rows ld_seq apart (may be null), and the optional rows of
@@ -100,7 +98,7 @@ TPC_GRAD_HD uint32_t exact_instance(const Args& a, int Hrt, int64_t k, double* w
     // the rows entries decide a non-finite T or l per instance (l = inf leaves Tv / l finite); the call's own are checked
     // before the launch
     const bool fin = m.fin && gfinite(tg0) && gfinite(tg1) && (!ROWS || (gfinite(pa.T) && gfinite(pa.l)));
-    constexpr int kU = 4 + I, kDf = 2 * I;   // first slot of the working copy / of df
+    constexpr int kU = 4 + I;   // first slot of the working copy
 
     auto finish = [&](int32_t status, double r_in, double r_out) {
         if (a.status) a.status[k] = status;
@@ -141,63 +139,15 @@ TPC_GRAD_HD uint32_t exact_instance(const Args& a, int Hrt, int64_t k, double* w
             for (int j = 0; j < I; ++j) slot(kU + j, t) = clampd(0.0, m.lo[j], m.hi[j]);
     }
 
-    double res_in = 0.0, prev = 0.0;
-    bool inner = false;
-    for (int round = 0;; ++round) {
-        // ---- gradient, forward: x_{t+1}
-        double x0 = xs0, x1 = xs1;
-        for (int t = 0; t < H; ++t) {
-            double y0 = gfma(m.a00, x0, gfma(m.a01, x1, m.c0)), y1 = gfma(m.a10, x0, gfma(m.a11, x1, m.c1));
-#pragma unroll
-            for (int j = 0; j < I; ++j) {
-                const double u = slot(kU + j, t);
-                y0 = gfma(m.b0[j], u, y0);
-                y1 = gfma(m.b1[j], u, y1);
-            }
-            x0 = y0; x1 = y1;
-            slot(0, t) = x0; slot(1, t) = x1;
-        }
-        // ---- gradient, backward: costate, df, dlib's mask, the residual
-        double P0 = 0.0, P1 = 0.0, res = 0.0;
-        bool okdf = true;
-        for (int t = H - 1; t >= 0; --t) {
-            const double e0 = slot(0, t) - tg0, e1 = slot(1, t) - tg1;
-            const double p0 = gfma(m.a00, P0, gfma(m.a10, P1, m.q0 * e0)), p1 = gfma(m.a01, P0, gfma(m.a11, P1, m.q1 * e1));
-            P0 = p0; P1 = p1;
-#pragma unroll
-            for (int j = 0; j < I; ++j) {
-                const double u = slot(kU + j, t);
-                const double df = gfma(m.b0[j], p0, gfma(m.b1[j], p1, m.r[j] * u));
-                slot(kDf + j, t) = df;
-                okdf = okdf && gfinite(df);
-                const bool blocked = (u <= m.lo[j] && df > 0.0) || (u >= m.hi[j] && df < 0.0) || m.lo[j] == m.hi[j];
-                if (!blocked) res = gabs(df) > res ? gabs(df) : res;
-            }
-        }
-        if (round == 0) res_in = res;
-        if (!okdf) break;   // an intermediate overflowed: not verified
-        if (res <= a.tol) {
-            finish(round, res_in, res);
-            return 0u;
-        }
-        if (round >= a.max_rounds) break;
-        inner = !inner && round > 0 && !(res < prev);
-        prev = res;
-
-        // ---- w = H_FF^-1 df_F, then the clamped step
-        bool f2 = true;
-        double y0, y1, d0, d1;
-        grad::riccati_passes<I>(
-            m, H, xs0, xs1, [&](int t, int j) { return slot(kU + j, t); }, [&](int t, int j) { return slot(kDf + j, t); },
-            [&](int j, double u, double df) {
-                const bool blocked = (u <= m.lo[j] && df > 0.0) || (u >= m.hi[j] && df < 0.0) || m.lo[j] == m.hi[j];
-                return !blocked && !(inner && (u <= m.lo[j] || u >= m.hi[j]));
-            },
-            ws, wn, f2, y0, y1, d0, d1);
-        for (int t = 0; t < H; ++t)
-#pragma unroll
-            for (int j = 0; j < I; ++j) slot(kU + j, t) = clampd(slot(kU + j, t) - slot(4 + j, t), m.lo[j], m.hi[j]);
+    double res_in = 0.0, res_out = 0.0;
+    const int32_t round = polish::newton_rounds<I>(
+        m, H, xs0, xs1, [&](int, int c) { return c == 0 ? tg0 : tg1; }, a.tol, a.max_rounds, ws, wn, res_in, res_out);
+    if (round >= 0) {
+        finish(round, res_in, res_out);
+        return 0u;
     }
+    // the one difference from polish_instance's outputs: that leaves the caller's sequence and reports residual_out =
+    // residual_in; an unverified instance here has zeros for outputs, and its residual_out is one of them
     finish(-1, res_in, 0.0);
     return 0x8u;
 }

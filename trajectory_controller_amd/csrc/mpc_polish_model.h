@@ -24,8 +24,9 @@
 //   riccati_passes:           g = df read from slot 2 I + j (before the step's feed-forward is written there),
 //                             leaves w in slot 4 + j
 //   update:                   u in slot 4 + I + j, the working copy -- the caller's array is written on success only
-// The rounds below are restated for the compact model in mpc_newton_compact_model.h (exact_instance), which must stay
-// this function operation for operation: a change to the rounds is made in both (tests/test_compact_exact_host.py).
+// The rounds are newton_rounds() below, the one copy: polish_instance() calls it with the targets read from the caller's
+// array, the exact compact solve (mpc_newton_compact_model.h, exact_instance) with its two target values in registers.
+// tests/golden/newton_rounds_parent.npz pins the bits of both callers to the code before they shared it.
 #pragma once
 
 #include "mpc_grad_model.h"
@@ -53,6 +54,75 @@ TPC_GRAD_HD constexpr int slots(int I) { return grad::slots(I) + I; }
 
 TPC_GRAD_HD double clampd(double u, double lo, double hi) { return u < lo ? lo : (u > hi ? hi : u); }
 
+// The rounds, on the working copy the caller has put in slots 4 + I + j.  tg_at(t, c) is component c of step t's target.
+// Returns the round at which res <= tol, with that res in res_out and the verified sequence in the working copy; -1 when
+// a df overflowed or max_rounds were used up (res_out is left alone).  res_in is round 0's residual either way.
+// H may be a compile-time constant of the caller's (mpc_newton_compact.hip): the function is inlined, every loop over
+// the horizon below then unrolls, and a ws that is an array of the lane's own stays in registers.
+template <int I, class TG>
+TPC_GRAD_HD int32_t newton_rounds(const grad::Model& m, int H, double xs0, double xs1, TG tg_at, double tol,
+                                  int32_t max_rounds, double* ws, int64_t wn, double& res_in, double& res_out) {
+    auto slot = [&](int q, int t) -> double& { return ws[((int64_t)q * H + t) * wn]; };
+    constexpr int kU = 4 + I, kDf = 2 * I;   // first slot of the working copy / of df
+    auto blocked = [&](int j, double u, double df) {   // dlib's mask, mpc.h:298-299
+        return (u <= m.lo[j] && df > 0.0) || (u >= m.hi[j] && df < 0.0) || m.lo[j] == m.hi[j];
+    };
+    double prev = 0.0;
+    bool inner = false;
+    res_in = 0.0;
+    for (int32_t round = 0;; ++round) {
+        // ---- gradient, forward: x_{t+1}
+        double x0 = xs0, x1 = xs1;
+        for (int t = 0; t < H; ++t) {
+            double y0 = gfma(m.a00, x0, gfma(m.a01, x1, m.c0)), y1 = gfma(m.a10, x0, gfma(m.a11, x1, m.c1));
+#pragma unroll
+            for (int j = 0; j < I; ++j) {
+                const double u = slot(kU + j, t);
+                y0 = gfma(m.b0[j], u, y0);
+                y1 = gfma(m.b1[j], u, y1);
+            }
+            x0 = y0; x1 = y1;
+            slot(0, t) = x0; slot(1, t) = x1;
+        }
+        // ---- gradient, backward: costate, df, the mask, the residual
+        double P0 = 0.0, P1 = 0.0, res = 0.0;
+        bool okdf = true;
+        for (int t = H - 1; t >= 0; --t) {
+            const double e0 = slot(0, t) - tg_at(t, 0), e1 = slot(1, t) - tg_at(t, 1);
+            const double p0 = gfma(m.a00, P0, gfma(m.a10, P1, m.q0 * e0)), p1 = gfma(m.a01, P0, gfma(m.a11, P1, m.q1 * e1));
+            P0 = p0; P1 = p1;
+#pragma unroll
+            for (int j = 0; j < I; ++j) {
+                const double u = slot(kU + j, t);
+                const double df = gfma(m.b0[j], p0, gfma(m.b1[j], p1, m.r[j] * u));
+                slot(kDf + j, t) = df;
+                okdf = okdf && gfinite(df);
+                if (!blocked(j, u, df)) res = gabs(df) > res ? gabs(df) : res;
+            }
+        }
+        if (round == 0) res_in = res;
+        if (!okdf) return -1;   // an intermediate overflowed
+        if (res <= tol) {
+            res_out = res;
+            return round;
+        }
+        if (round >= max_rounds) return -1;
+        inner = !inner && round > 0 && !(res < prev);
+        prev = res;
+
+        // ---- w = H_FF^-1 df_F, then the clamped step
+        bool f2 = true;
+        double y0, y1, d0, d1;
+        grad::riccati_passes<I>(
+            m, H, xs0, xs1, [&](int t, int j) { return slot(kU + j, t); }, [&](int t, int j) { return slot(kDf + j, t); },
+            [&](int j, double u, double df) { return !blocked(j, u, df) && !(inner && (u <= m.lo[j] || u >= m.hi[j])); },
+            ws, wn, f2, y0, y1, d0, d1);
+        for (int t = 0; t < H; ++t)
+#pragma unroll
+            for (int j = 0; j < I; ++j) slot(kU + j, t) = clampd(slot(kU + j, t) - slot(4 + j, t), m.lo[j], m.hi[j]);
+    }
+}
+
 // One instance.  ws points at the instance's first workspace element (ws[(q * H + t) * wn]).  Returns its
 // TPC_MPC_FLAG_* bits: 0x1 non-finite, 0x4 bad model (both: nothing run, status -1), 0x8 not polished.
 template <int I>
@@ -63,7 +133,7 @@ TPC_GRAD_HD uint32_t polish_instance(const Args& a, int H, int64_t k, double* ws
     const grad::Model m = grad::load_model<I>(a.A, a.B, a.C, a.Q, a.R, a.lo, a.hi, ld, k);
     const double xs0 = in(a.x0, 0), xs1 = in(a.x0, 1);
     bool fin = m.fin && gfinite(xs0) && gfinite(xs1);
-    constexpr int kU = 4 + I, kDf = 2 * I;   // first slot of the working copy / of df
+    constexpr int kU = 4 + I;   // first slot of the working copy
 
     for (int t = 0; t < H; ++t) {
         fin = fin && gfinite(in(a.targets, 2 * t)) && gfinite(in(a.targets, 2 * t + 1));
@@ -88,66 +158,19 @@ TPC_GRAD_HD uint32_t polish_instance(const Args& a, int H, int64_t k, double* ws
         return bad;
     }
 
-    double res_in = 0.0, prev = 0.0;
-    bool inner = false;
-    for (int round = 0;; ++round) {
-        // ---- gradient, forward: x_{t+1}
-        double x0 = xs0, x1 = xs1;
-        for (int t = 0; t < H; ++t) {
-            double y0 = gfma(m.a00, x0, gfma(m.a01, x1, m.c0)), y1 = gfma(m.a10, x0, gfma(m.a11, x1, m.c1));
-#pragma unroll
-            for (int j = 0; j < I; ++j) {
-                const double u = slot(kU + j, t);
-                y0 = gfma(m.b0[j], u, y0);
-                y1 = gfma(m.b1[j], u, y1);
-            }
-            x0 = y0; x1 = y1;
-            slot(0, t) = x0; slot(1, t) = x1;
-        }
-        // ---- gradient, backward: costate, df, dlib's mask, the residual
-        double P0 = 0.0, P1 = 0.0, res = 0.0;
-        bool okdf = true;
-        for (int t = H - 1; t >= 0; --t) {
-            const double e0 = slot(0, t) - in(a.targets, 2 * t), e1 = slot(1, t) - in(a.targets, 2 * t + 1);
-            const double p0 = gfma(m.a00, P0, gfma(m.a10, P1, m.q0 * e0)), p1 = gfma(m.a01, P0, gfma(m.a11, P1, m.q1 * e1));
-            P0 = p0; P1 = p1;
-#pragma unroll
-            for (int j = 0; j < I; ++j) {
-                const double u = slot(kU + j, t);
-                const double df = gfma(m.b0[j], p0, gfma(m.b1[j], p1, m.r[j] * u));
-                slot(kDf + j, t) = df;
-                okdf = okdf && gfinite(df);
-                const bool blocked = (u <= m.lo[j] && df > 0.0) || (u >= m.hi[j] && df < 0.0) || m.lo[j] == m.hi[j];
-                if (!blocked) res = gabs(df) > res ? gabs(df) : res;
-            }
-        }
-        if (round == 0) res_in = res;
-        if (!okdf) break;   // an intermediate overflowed: not polished
-        if (res <= a.tol) {
-            for (int t = 0; t < H; ++t)
-#pragma unroll
-                for (int j = 0; j < I; ++j) a.u[(int64_t)(t * I + j) * ld + k] = slot(kU + j, t);
-            finish(round, res_in, res);
-            return 0u;
-        }
-        if (round >= a.max_rounds) break;
-        inner = !inner && round > 0 && !(res < prev);
-        prev = res;
-
-        // ---- w = H_FF^-1 df_F, then the clamped step
-        bool f2 = true;
-        double y0, y1, d0, d1;
-        grad::riccati_passes<I>(
-            m, H, xs0, xs1, [&](int t, int j) { return slot(kU + j, t); }, [&](int t, int j) { return slot(kDf + j, t); },
-            [&](int j, double u, double df) {
-                const bool blocked = (u <= m.lo[j] && df > 0.0) || (u >= m.hi[j] && df < 0.0) || m.lo[j] == m.hi[j];
-                return !blocked && !(inner && (u <= m.lo[j] || u >= m.hi[j]));
-            },
-            ws, wn, f2, y0, y1, d0, d1);
+    double res_in = 0.0, res_out = 0.0;
+    const int32_t round =
+        newton_rounds<I>(m, H, xs0, xs1, [&](int t, int c) { return in(a.targets, 2 * t + c); }, a.tol, a.max_rounds, ws,
+                         wn, res_in, res_out);
+    if (round >= 0) {
         for (int t = 0; t < H; ++t)
 #pragma unroll
-            for (int j = 0; j < I; ++j) slot(kU + j, t) = clampd(slot(kU + j, t) - slot(4 + j, t), m.lo[j], m.hi[j]);
+            for (int j = 0; j < I; ++j) a.u[(int64_t)(t * I + j) * ld + k] = slot(kU + j, t);
+        finish(round, res_in, res_out);
+        return 0u;
     }
+    // the caller's sequence stands, so its residual does: residual_out = residual_in.  (The exact compact solve, whose
+    // unverified outputs are zeros, reports 0.0 here -- the one difference between the two callers' outputs.)
     finish(-1, res_in, res_in);
     return 0x8u;
 }
