@@ -2,8 +2,8 @@
 
 What the CPU and GPU tests of the exact compact solve's backward pass (tpc_mpc_solve_batch_compact_exact_backward)
 share: the incoming gradient of the expanded form, the chain rule of the model building in numpy -- the lines of
-include/tpc_mpc.h, one rounded operation each -- applied to solve_batch_general_backward's dict, and the a-priori bound
-of a sum of n doubles.
+include/tpc_mpc.h, one rounded operation each -- applied to solve_batch_general_backward's dict, the a-priori bound
+of a sum of n doubles, and the device's own order of that sum (device_sum).
 """
 import math
 
@@ -73,3 +73,43 @@ def fsum_bound(rows):
 
 def fsum_rows(rows):
     return np.array([math.fsum(r) for r in np.asarray(rows, dtype=np.float64)])
+
+
+WAVE, REDUCE_BLOCK = 64, 256
+
+
+def grad_block(n):
+    """rollout_grad_block's rule: the largest of 256, 128, 64 lanes that still gives 256 blocks, else 64"""
+    for b in (256, 128):
+        if -(-n // b) >= 256:
+            return b
+    return 64
+
+
+def device_sum(rows):
+    """The ten doubles the device must return as "params" for the per-instance rows [10, n]: the summation order of
+    mpc_compact_grad.hip (block_partials, compact_grad_reduce_kernel) in numpy fp64, one rounded addition per addition
+    of the kernels.  No call into the library."""
+    rows = np.asarray(rows, dtype=np.float64)
+    P, n = rows.shape
+    block = grad_block(n)
+    blocks = -(-n // block)
+    lanes = np.zeros((P, blocks * block))                   # a lane past n holds +0.0
+    lanes[:, :n] = rows
+    a = lanes.reshape(P, blocks * block // WAVE, WAVE)
+    lane = np.arange(WAVE)
+    for mask in (32, 16, 8, 4, 2, 1):                       # the butterfly: every lane ends with the same value
+        a = a + a[:, :, lane ^ mask]
+    waves = a[:, :, 0].reshape(P, blocks, block // WAVE)
+    part = waves[:, :, 0].copy()                            # the block: wavefront 0, then 1.. in ascending order
+    for w in range(1, block // WAVE):
+        part = part + waves[:, :, w]
+    x = np.zeros((P, REDUCE_BLOCK))                         # the reduce: thread t adds partials t, t + 256, ...
+    for b0 in range(0, blocks, REDUCE_BLOCK):
+        m = min(REDUCE_BLOCK, blocks - b0)
+        x[:, :m] = x[:, :m] + part[:, b0:b0 + m]
+    half = REDUCE_BLOCK // 2
+    while half > 0:                                         # the tree: lds[t] = lds[t] + lds[t + half]
+        x[:, :half] = x[:, :half] + x[:, half:2 * half]
+        half >>= 1
+    return np.ascontiguousarray(x[:, 0])

@@ -1,7 +1,8 @@
 """GPU tests of the exact compact solve's backward pass (tpc_mpc_solve_batch_compact_exact_backward,
 MpcSolver.solve_batch_compact_exact_backward, mpc_compact_exact): the device against the host-only handle bit for bit
 through the register kernels (H = 4, 5) and the workspace kernel, the device's deterministic batch sum of the shared
-parameters' gradients, the handle's other entries untouched by a call, the autograd function against the raw entries,
+parameters' gradients held to the order mpc_compact_grad.hip documents (cg.device_sum) at the sizes where that order
+changes shape, the handle's other entries untouched by a call, the autograd function against the raw entries,
 the gradients against the general-form route mpc_compact(..., polish=True), and one full-size run."""
 import functools
 
@@ -113,6 +114,51 @@ def test_dparams_is_deterministic_and_within_the_bound_of_any_order(H):
             assert set(alone) == {"params"} and alone["params"].tobytes() == got["params"].tobytes(), n
             staged, _ = _backward(s, c, False, want=("params",))     # HOST arrays: the same launches
             assert staged["params"].tobytes() == got["params"].tobytes(), n
+            assert got["params"].tobytes() == cg.device_sum(rows).tobytes(), n     # the documented order, to the bit
+
+
+# n -> what the batch sum's order does there (cg.grad_block: the block, so the number of partials the reduce reads)
+SEAMS = {
+    16384: "64-lane blocks, 256 partials: every reduce thread has exactly one",
+    16385: "64-lane blocks, 257 partials: thread 0 makes a second trip; one live lane in the last block",
+    32640: "the last grid of 64-lane blocks, 510 partials, every block full",
+    32641: "the first grid of 128-lane blocks, 256 partials; one live lane in the last block, its second wavefront empty",
+    65280: "128-lane blocks, 510 partials, every block full",
+    65281: "the first grid of 256-lane blocks, 256 partials; three empty wavefronts in the last block",
+    65537: "256-lane blocks, 257 partials",
+}
+
+
+def check_params_at_a_seam(s, c, backward, n):
+    """What test_compact_rows_gpu.py asserts too: the device's per-instance outputs and flags are the host-only
+    handle's (c["want"], flags), and "params" is cg.device_sum of the device's own rows, byte for byte, on every call.
+    (tests/test_launch_shapes_gpu.py runs the same kernels at the three block thresholds WITHOUT "params", where a
+    lane past the batch leaves at once; the per-instance comparison with the sum requested lives here.)"""
+    got, flags = backward(s, c, True)
+    for k in cg.PER_INSTANCE:
+        assert got[k].shape[-1] == n and got[k].tobytes() == c["want"][k].tobytes(), k
+    rows = got["params_rows"]
+    assert rows[:, -1].any(), "the last instance's row is zero: its lane shows no work"
+    assert got["params"].tobytes() == cg.device_sum(rows).tobytes()
+    diff = np.abs(got["params"] - cg.fsum_rows(rows))
+    print(f"n={n}: max |dparams - fsum| / bound {np.max(diff / np.maximum(cg.fsum_bound(rows), 1e-300)):.2e}")
+    assert np.all(diff <= cg.fsum_bound(rows)), (diff, cg.fsum_bound(rows))
+    again, _ = backward(s, c, True)
+    assert again["params"].tobytes() == got["params"].tobytes()
+    alone, _ = backward(s, c, False, want=("params",))     # HOST arrays, the per-instance pointers null in the kernels
+    assert set(alone) == {"params"} and alone["params"].tobytes() == got["params"].tobytes()
+    return flags
+
+
+@pytest.mark.parametrize("n", list(SEAMS))
+@pytest.mark.parametrize("H", [4, 7], ids=["reg", "ws"])
+def test_dparams_is_the_documented_order_where_it_changes_shape(H, n):
+    """Two wavefronts per block, the reduce kernel's second trip, a last block whose other wavefronts are empty and
+    the seam at 256 / 257 partials (SEAMS), with excluded zero rows inside a wavefront (_case)."""
+    assert cg.grad_block(n) == (64 if n <= 32640 else 128 if n <= 65280 else 256)
+    c = _case(H, n)
+    with MpcSolver(horizon=H, device=0) as s:
+        assert check_params_at_a_seam(s, c, _backward, n) == c["flags"] == capi.FLAG_NONFINITE
 
 
 # ---- 3. the handle's other entries: the gradient workspace is shared
@@ -254,3 +300,4 @@ def test_full_size_call():
         assert np.all(np.isfinite(_np(got[k]))), k
     rows = _np(got["params_rows"])
     assert np.all(np.abs(_np(got["params"]) - cg.fsum_rows(rows)) <= cg.fsum_bound(rows))
+    assert _np(got["params"]).tobytes() == cg.device_sum(rows).tobytes()     # 256-lane blocks, 1024 partials

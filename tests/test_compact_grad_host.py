@@ -137,6 +137,35 @@ def test_dparams_is_the_sum_of_the_rows(n):
     assert np.array_equal(got["params"], acc)
 
 
+def _ascending(rows):
+    acc = np.zeros(rows.shape[0])
+    for k in range(rows.shape[1]):
+        acc = acc + rows[:, k]
+    return acc
+
+
+def test_device_sum_is_a_sum_and_a_real_order():
+    """cg.device_sum, the restatement the GPU tests hold "params" to, on rows whose magnitudes span six decades: a sum
+    of the rows within the a-priori bound at every block shape it takes (one lane, one lane into the second wavefront,
+    257 partials of 64-lane blocks, 257 partials of 256-lane blocks), and not the ascending order's bits."""
+    assert [cg.grad_block(n) for n in (1, 16384, 32640, 32641, 65280, 65281, 65537, 262144)] == \
+        [64, 64, 64, 128, 128, 256, 256, 256]
+    differs = []
+    for n in (1, 65, 16385, 65537):
+        rng = np.random.default_rng(n)
+        rows = rng.standard_normal((10, n)) * 10.0 ** rng.uniform(-3, 3, (10, n))
+        got = cg.device_sum(rows)
+        assert got.shape == (10,) and got.dtype == np.float64
+        diff = np.abs(got - cg.fsum_rows(rows))
+        print(f"n={n}: max |device_sum - fsum| / bound {np.max(diff / np.maximum(cg.fsum_bound(rows), 1e-300)):.3f}")
+        assert np.all(diff <= cg.fsum_bound(rows)), (n, diff, cg.fsum_bound(rows))
+        if n == 1:
+            assert got.tobytes() == np.ascontiguousarray(rows[:, 0]).tobytes()
+        else:
+            differs.append(got.tobytes() != _ascending(rows).tobytes())
+    assert any(differs), "the device's order gives the ascending sum's bits at every size: no constraint"
+
+
 def test_unverified_instances_are_excluded():
     H = 20
     v, dy, dphi, seq, st, _, _ = _forward(H, "default")

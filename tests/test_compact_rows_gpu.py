@@ -2,7 +2,8 @@
 backward pass, MpcSolver.solve_batch_compact_exact[_backward](params_rows=...), mpc_compact_exact with [.., n]
 parameters): the device against the host-only handle bit for bit through the register kernels (H = 4, 5) and the
 workspace kernels, forward and backward, HOST and DEVICE memory; the fallback against solve_batch_general +
-polish_batch_general on exactly the gathered instances expanded per instance; the device's batch sum; the handle's other
+polish_batch_general on exactly the gathered instances expanded per instance; the device's batch sum, held to the order
+mpc_compact_grad.hip documents (cg.device_sum) at the sizes where that order changes shape; the handle's other
 entries untouched by a rows call; the autograd function against the raw entries and against the general-form route
 mpc_compact(w [4, n], ..., polish=True); one full-size run."""
 import functools
@@ -15,6 +16,7 @@ torch = pytest.importorskip("torch")
 from tests.model import compact_grad_common as cg
 from tests.model import compact_rows_common as cr
 from tests.model.compact_exact_common import NAMES, ROUNDS, TOL, bits
+from tests.test_compact_grad_gpu import SEAMS, check_params_at_a_seam
 from trajectory_controller_amd import MpcSolver, capi, mpc_compact, mpc_compact_exact
 from trajectory_controller_amd.synth import compact_inputs
 
@@ -199,6 +201,18 @@ def test_dparams_is_deterministic_and_within_the_bound_of_any_order(H):
             assert again["params"].tobytes() == got["params"].tobytes(), n
             staged, _ = _backward(s, c, False, want=("params",))     # HOST arrays: the same launches
             assert staged["params"].tobytes() == got["params"].tobytes(), n
+            assert got["params"].tobytes() == cg.device_sum(out).tobytes(), n      # the documented order, to the bit
+
+
+@pytest.mark.parametrize("n", list(SEAMS))
+@pytest.mark.parametrize("H", [4, 7], ids=["reg", "ws"])
+def test_dparams_is_the_documented_order_where_it_changes_shape(H, n):
+    """tests/test_compact_grad_gpu.py's test of the same name through the rows kernels: SEAMS says what each size is;
+    the seven cases of cr.INVALID and one more excluded instance put zero rows inside a wavefront (_case)."""
+    c = _case(H, n)
+    with MpcSolver(horizon=H, device=0) as s:
+        flags = check_params_at_a_seam(s, c, _backward, n)
+    assert flags == c["bflags"] == capi.FLAG_NONFINITE | capi.FLAG_BAD_MODEL
 
 
 # ---- 4. the handle's other entries: the working sets are shared
@@ -357,3 +371,4 @@ def test_full_size_call():
         assert np.all(np.isfinite(_np(got[k]))), k
     out = _np(got["params_rows"])
     assert np.all(np.abs(_np(got["params"]) - cg.fsum_rows(out)) <= cg.fsum_bound(out))
+    assert _np(got["params"]).tobytes() == cg.device_sum(out).tobytes()      # 256-lane blocks, 1024 partials
