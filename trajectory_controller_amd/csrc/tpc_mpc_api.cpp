@@ -4,6 +4,7 @@
 // solves over RCCL: tpc_mpc_comm.cpp; the resident single-solve kernel: tpc_mpc_one.hip; the gradient kernel and its
 // host path for a host-only handle: mpc_grad.hip.)
 #include "tpc_mpc_context.h"
+#include "tpc_mpc_stage.h"
 #include "tpc_mpc_experimental.h"
 #include "auto_table.h"
 #include "mpc_queue_key_table.h"
@@ -437,7 +438,8 @@ int resolve_workspace(tpc_mpc_context* h, int H, int dtype, int64_t n, Workspace
 hipError_t copy_rows(void* dst, int64_t dpitch, const void* src, int64_t spitch, int64_t width, int64_t rows,
                      hipMemcpyKind kind, hipStream_t s) {
     if (rows <= 0 || width <= 0) return hipSuccess;
-    if (dpitch == width && spitch == width) return hipMemcpyAsync(dst, src, (size_t)(width * rows), kind, s);
+    if (rows == 1 || (dpitch == width && spitch == width))   // one run of bytes
+        return hipMemcpyAsync(dst, src, (size_t)(width * rows), kind, s);
     return hipMemcpy2DAsync(dst, (size_t)dpitch, src, (size_t)spitch, (size_t)width, (size_t)rows, kind, s);
 }
 
@@ -476,6 +478,26 @@ int check_fallback(tpc_mpc_context* h, int32_t fallback) {
 // (what an entry named `entry` returns for p->dtype != TPC_MPC_F64)
 int fp64_only(tpc_mpc_context* h, const char* entry) {
     return fail(h, TPC_MPC_ERR_BAD_ARG, "%s is fp64 only: p->dtype must be TPC_MPC_F64", entry);
+}
+// the batch size and memory kind of the compact entries (check_general_io makes these checks for an io)
+int check_batch(tpc_mpc_context* h, int64_t n, int mem) {
+    if (n < 0 || n > 0x7fffffffll) return fail(h, TPC_MPC_ERR_BAD_ARG, "need 0 <= n < 2^31");
+    if (mem != TPC_MPC_HOST && mem != TPC_MPC_DEVICE) return fail(h, TPC_MPC_ERR_BAD_ARG, "bad memory kind");
+    return TPC_MPC_OK;
+}
+// what a host-only handle refuses of the Newton-first entries: the fallback solve, and DEVICE memory
+int check_host_only_newton(tpc_mpc_context* h, bool solve, int mem) {
+    if (h->host_only && solve)
+        return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): the fallback solve runs on the device only; use TPC_MPC_NEWTON_FALLBACK_NONE");
+    if (h->host_only && mem == TPC_MPC_DEVICE)
+        return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): HOST memory only");
+    return TPC_MPC_OK;
+}
+// the ten model values of the compact form into the Args of the exact solve or its backward pass
+template <class Args> void bind_compact_model(Args* a, const tpc_mpc_params* p) {
+    a->T = p->step_size; a->l = p->wheelbase; a->q0 = p->weight_y; a->q1 = p->weight_phi;
+    a->r[0] = p->weight_steering_front; a->r[1] = p->weight_steering_rear;
+    for (int j = 0; j < 2; ++j) { a->lo[j] = p->lower[j]; a->hi[j] = p->upper[j]; }
 }
 
 }  // namespace
@@ -858,28 +880,56 @@ int compact_launch(tpc_mpc_context* h, const tpc_mpc_params* p, int64_t n, const
 
 namespace {
 
-// What only some users of staged_run need of their arrays in the caller's memory; each table may be null
+// HOST arrays go through h->stage, and through these two functions alone.  stage_in gives every array of the table
+// that is there a slot (tpc_mpc_stage.h: leading dimension stage_ld(n), 256-byte padded) and copies the inputs in;
+// stage_out copies the outputs back and waits for them.  Row by row, n elements per row: a caller's ld > n (a shard of a
+// wider batch) is neither over-read nor over-written.  On return of stage_in, t[c].dev is what the kernels take.
+int stage_in(tpc_mpc_context* h, StagedArray* t, int count, int64_t n, hipStream_t s) {
+    int rc = ensure(h, &h->stage, &h->stage_bytes, stage_layout(t, count, n));
+    if (rc) return rc;
+    for (int c = 0; c < count; ++c) {
+        StagedArray& a = t[c];
+        if (!a.ptr) continue;
+        a.dev = (char*)h->stage + a.off;
+        if (a.role & kStageIn)
+            HIP_TRY(h, copy_rows(a.dev, stage_pitch(a, n) * a.width, a.ptr, a.ld * a.width, stage_elems(a, n) * a.width,
+                                 a.rows, hipMemcpyHostToDevice, s));
+    }
+    return TPC_MPC_OK;
+}
+int stage_out(tpc_mpc_context* h, const StagedArray* t, int count, int64_t n, hipStream_t s) {
+    for (int c = 0; c < count; ++c) {
+        const StagedArray& a = t[c];
+        if (a.ptr && (a.role & kStageOut))
+            HIP_TRY(h, copy_rows(const_cast<void*>(a.ptr), a.ld * a.width, a.dev, stage_pitch(a, n) * a.width,
+                                 stage_elems(a, n) * a.width, a.rows, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return TPC_MPC_OK;
+}
+
+// What only some users of staged_run need of their arrays in the caller's memory; each table is [NIn + NOut] and may
+// be null
 struct StagedExtra {
-    const int64_t* src_ld = nullptr;   // [NIn] leading dimension of src[c] where not io->ld (0: io->ld)
-    const int64_t* dst_ld = nullptr;   // [NOut] ... and of dst[c]
-    const int* width = nullptr;        // [NIn + NOut] bytes per element where not 8 (0: 8)
-    int inout = -1;                    // src[inout] is written too: its staged copy always goes back to it
+    const int64_t* ld = nullptr;      // leading dimension where not the call's (0: the call's)
+    const int* width = nullptr;       // bytes per element where not 8 (0: 8)
+    const int64_t* elems = nullptr;   // elements per row where not n (0: n): a row that is not per instance
+    int inout = -1;                   // src[inout] is written too: its staged copy always goes back to it
 };
 
-// What the one-launch general-form entries share after their argument checks: NIn input arrays (a null one is not
-// staged) of rows[c] component rows and NOut output arrays of rows[NIn + c], run by `run(ld, in, out, s, host_flags)` --
-// on the calling thread for a host-only handle (host_flags != null), else as a launch on s: on the caller's own DEVICE
-// arrays and io->ld, or after HOST arrays were staged in h->stage with the leading dimension lds.  On the stream: the
-// gradient workspace grown to ws_bytes, the staging copies, the flag word zeroed, the launch, the copies back and a
-// synchronise (HOST only), the stream order's event, the flags.
+// What the one-launch entries share after their argument checks: NIn input arrays (a null one is not staged) of rows[c]
+// component rows and NOut output arrays of rows[NIn + c], n instances with the leading dimension ld in the caller's
+// memory, run by `run(ld, in, out, s, host_flags)` -- on the calling thread for a host-only handle (host_flags !=
+// null), else as a launch on s: on the caller's own DEVICE arrays and ld, or on the slots of HOST arrays (stage_in) and
+// stage_ld(n).  On the stream: the gradient workspace grown to ws_bytes, the staging copies, the flag word zeroed, the
+// launch, the copies back and a synchronise (HOST only), the stream order's event, the flags.
 template <int NIn, int NOut, class Run>
-int staged_run(tpc_mpc_context* h, const tpc_mpc_general_io* io, int mem, void* stream, uint32_t* flags_out,
-               int64_t ws_bytes, const void* const (&src)[NIn], void* const (&dst)[NOut],
-               const int64_t (&rows)[NIn + NOut], Run run, const StagedExtra& x = StagedExtra()) {
-    const int64_t n = io->n;
+int staged_run(tpc_mpc_context* h, int64_t n, int64_t ld, int mem, void* stream, uint32_t* flags_out, int64_t ws_bytes,
+               const void* const (&src)[NIn], void* const (&dst)[NOut], const int64_t (&rows)[NIn + NOut], Run run,
+               const StagedExtra& x = StagedExtra()) {
     if (h->host_only) {   // on the calling thread, straight from and into the caller's arrays
         uint32_t f = 0;
-        (void)run(io->ld, src, dst, (hipStream_t) nullptr, &f);
+        (void)run(ld, src, dst, (hipStream_t) nullptr, &f);
         if (flags_out) *flags_out = f;
         return TPC_MPC_OK;
     }
@@ -890,50 +940,26 @@ int staged_run(tpc_mpc_context* h, const tpc_mpc_general_io* io, int mem, void* 
     if (rc) return rc;
     rc = ensure(h, &h->grad_ws, &h->grad_ws_bytes, pad256(ws_bytes));
     if (rc) return rc;
-    const int64_t lds = (n + 63) / 64 * 64;
-    const void* sin[NIn];
-    void* sout[NOut];
-    for (int c = 0; c < NIn; ++c) sin[c] = src[c];
-    for (int c = 0; c < NOut; ++c) sout[c] = dst[c];
-    int64_t ld = io->ld;
     const bool host = mem == TPC_MPC_HOST;
-    auto width = [&](int c) -> int64_t { return x.width && x.width[c] ? x.width[c] : 8; };
-    auto ld_of = [&](const int64_t* lds_given, int c) { return lds_given && lds_given[c] ? lds_given[c] : io->ld; };
+    StagedArray t[NIn + NOut];
+    for (int c = 0; c < NIn + NOut; ++c)
+        t[c] = staged(c < NIn ? src[c] : dst[c - NIn], c == x.inout ? kStageInOut : c < NIn ? kStageIn : kStageOut, rows[c],
+                      x.ld && x.ld[c] ? x.ld[c] : ld, x.width && x.width[c] ? x.width[c] : 8, x.elems ? x.elems[c] : 0);
     if (host) {
-        // HOST arrays: every component row copied on its own (n elements, never ld); only the arrays given are staged
-        int64_t off[NIn + NOut], total = 0;
-        for (int c = 0; c < NIn + NOut; ++c) {
-            const bool given = c < NIn ? src[c] != nullptr : dst[c - NIn] != nullptr;
-            off[c] = total;
-            if (given) total += pad256(rows[c] * lds * width(c));
-        }
-        rc = ensure(h, &h->stage, &h->stage_bytes, total);
+        rc = stage_in(h, t, NIn + NOut, n, s);
         if (rc) return rc;
-        char* b = (char*)h->stage;
-        for (int c = 0; c < NIn; ++c) {
-            if (!src[c]) continue;
-            sin[c] = b + off[c];
-            HIP_TRY(h, copy_rows(b + off[c], lds * width(c), src[c], ld_of(x.src_ld, c) * width(c), n * width(c), rows[c],
-                                 hipMemcpyHostToDevice, s));
-        }
-        for (int c = 0; c < NOut; ++c)
-            if (dst[c]) sout[c] = b + off[NIn + c];
-        ld = lds;
+        ld = stage_ld(n);
     }
+    const void* in[NIn];
+    void* out[NOut];
+    for (int c = 0; c < NIn; ++c) in[c] = t[c].dev;
+    for (int c = 0; c < NOut; ++c) out[c] = t[NIn + c].dev;
     HIP_TRY(h, hipMemsetAsync(h->ws_words + 1, 0, sizeof(uint32_t), s));
-    hipError_t e = run(ld, sin, sout, s, (uint32_t*)nullptr);
+    hipError_t e = run(ld, in, out, s, (uint32_t*)nullptr);
     if (e != hipSuccess) return hip_fail(h, e, "kernel launch");
     if (host) {
-        if (x.inout >= 0) {
-            const int c = x.inout;
-            HIP_TRY(h, copy_rows(const_cast<void*>(src[c]), ld_of(x.src_ld, c) * width(c), sin[c], lds * width(c),
-                                 n * width(c), rows[c], hipMemcpyDeviceToHost, s));
-        }
-        for (int c = 0; c < NOut; ++c)
-            if (dst[c])
-                HIP_TRY(h, copy_rows(dst[c], ld_of(x.dst_ld, c) * width(NIn + c), sout[c], lds * width(NIn + c),
-                                     n * width(NIn + c), rows[NIn + c], hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipStreamSynchronize(s));
+        rc = stage_out(h, t, NIn + NOut, n, s);
+        if (rc) return rc;
     }
     rc = order.end();
     if (rc) return rc;
@@ -957,68 +983,63 @@ tangent::Dirs bind_dirs(const void* const* in) {
     return d;
 }
 
-// The per-step arrays of the closed loops (rollout_impl, rollout_newton_impl): new_last_targets and the plant's
-// disturbance in, seven outputs; a null one is not there.  The kernels take the caller's DEVICE arrays as they are.
-// HOST arrays go through h->stage: stage_steps gives every array that is there a slot with the leading dimension ldw
-// (n rounded up to a wavefront) and copies the inputs in, unstage_steps copies the outputs back -- n elements per row,
-// so a caller's ld > n (a shard of a wider batch) is neither over-read nor over-written.
-enum { kStepCtrl, kStepStates, kStepIters, kStepSeq, kStepStatus, kStepRin, kStepRout, kStepOuts };
+// The per-step arrays of the closed loops (rollout_impl, rollout_newton_impl) as a staging table: new_last_targets and
+// the plant's disturbance in, seven outputs; a null one is not there.  The kernels take t[c].dev with the leading
+// dimensions below: the caller's DEVICE arrays as they are, or after stage_steps the slots of HOST arrays, which
+// stage_out(h, g.t, kStepCount, n, s) copies back.
+enum { kStepNlt, kStepDist, kStepCtrl, kStepStates, kStepIters, kStepSeq, kStepStatus, kStepRin, kStepRout, kStepCount };
 struct StepArrays {
-    const void* in[2];      // new_last_targets [steps*2] (ld_nlt), disturbance [steps*2] (ld_d)
-    void* out[kStepOuts];   // (ld_out)
+    StagedArray t[kStepCount];
     int64_t ld_nlt, ld_d, ld_out;
-    int64_t rows[2 + kStepOuts], width[2 + kStepOuts];   // component rows and bytes per element: in, then out
+    template <class T = void> T* at(int c) const { return (T*)t[c].dev; }
 };
 // the caller's arrays; es: bytes per element of the loop's arithmetic (iters and status are int32, the residuals fp64
 // whatever it is); q null: a loop without the polish's outputs
-StepArrays step_arrays(const tpc_mpc_general_io* io, int H, int64_t S, int64_t es, const void* new_last_targets,
+StepArrays step_arrays(const tpc_mpc_general_io* io, int H, int64_t S, int es, const void* new_last_targets,
                        const tpc_mpc_plant* plant, void* controls_out, void* states_out, int32_t* iters_out,
                        void* sequences_out, const tpc_mpc_polish* q) {
-    const int64_t I = io->inputs;
+    const int64_t I = io->inputs, ld = io->ld;
     const void* dist = plant ? plant->disturbance : nullptr;
-    return StepArrays{{new_last_targets, dist},
-                      {controls_out, states_out, iters_out, sequences_out, q ? q->status : nullptr,
-                       q ? q->residual_in : nullptr, q ? q->residual_out : nullptr},
-                      io->ld, dist ? plant->ld_d : 0, io->ld,
-                      {2 * S, 2 * S, S * I, 2 * S, S, S * H * I, S, S, S},
-                      {es, es, es, es, 4, es, 4, 8, 8}};
+    StepArrays g;
+    g.ld_nlt = g.ld_out = ld;
+    g.ld_d = dist ? plant->ld_d : 0;
+    g.t[kStepNlt] = staged(new_last_targets, kStageIn, 2 * S, ld, es);
+    g.t[kStepDist] = staged(dist, kStageIn, 2 * S, g.ld_d, es);
+    g.t[kStepCtrl] = staged(controls_out, kStageOut, S * I, ld, es);
+    g.t[kStepStates] = staged(states_out, kStageOut, 2 * S, ld, es);
+    g.t[kStepIters] = staged(iters_out, kStageOut, S, ld, 4);
+    g.t[kStepSeq] = staged(sequences_out, kStageOut, S * H * I, ld, es);
+    g.t[kStepStatus] = staged(q ? q->status : nullptr, kStageOut, S, ld, 4);
+    g.t[kStepRin] = staged(q ? q->residual_in : nullptr, kStageOut, S, ld, 8);
+    g.t[kStepRout] = staged(q ? q->residual_out : nullptr, kStageOut, S, ld, 8);
+    return g;
 }
-// *d: what the kernels take for the caller's g
-int stage_steps(tpc_mpc_context* h, const StepArrays& g, bool host, int64_t n, hipStream_t s, StepArrays* d) {
-    *d = g;
-    if (!host) return TPC_MPC_OK;
-    const int64_t ldw = (n + 63) / 64 * 64;
-    int64_t off[2 + kStepOuts], total = 0;
-    for (int c = 0; c < 2 + kStepOuts; ++c) {
-        off[c] = total;
-        if (c < 2 ? g.in[c] != nullptr : g.out[c - 2] != nullptr) total += pad256(g.rows[c] * ldw * g.width[c]);
-    }
-    int rc = ensure(h, &h->stage, &h->stage_bytes, total);
-    if (rc) return rc;
-    char* b = (char*)h->stage;
-    const int64_t in_ld[2] = {g.ld_nlt, g.ld_d};
-    for (int c = 0; c < 2; ++c) {
-        if (!g.in[c]) continue;
-        const int64_t w = g.width[c];
-        HIP_TRY(h, copy_rows(b + off[c], ldw * w, g.in[c], in_ld[c] * w, n * w, g.rows[c], hipMemcpyHostToDevice, s));
-        d->in[c] = b + off[c];
-    }
-    for (int c = 0; c < kStepOuts; ++c)
-        if (g.out[c]) d->out[c] = b + off[2 + c];
-    d->ld_nlt = d->ld_out = ldw;
-    if (g.in[1]) d->ld_d = ldw;
-    return TPC_MPC_OK;
+// HOST arrays only: the slots, the inputs copied in
+int stage_steps(tpc_mpc_context* h, StepArrays* g, int64_t n, hipStream_t s) {
+    g->ld_nlt = g->ld_out = stage_ld(n);
+    if (g->t[kStepDist].ptr) g->ld_d = stage_ld(n);
+    return stage_in(h, g->t, kStepCount, n, s);
 }
-// HOST arrays only: the staged outputs d back into the caller's g, and the wait for them
-int unstage_steps(tpc_mpc_context* h, const StepArrays& g, const StepArrays& d, int64_t n, hipStream_t s) {
-    for (int c = 0; c < kStepOuts; ++c) {
-        const int64_t w = g.width[2 + c];
-        if (g.out[c])
-            HIP_TRY(h, copy_rows(g.out[c], g.ld_out * w, d.out[c], d.ld_out * w, n * w, g.rows[2 + c],
-                                 hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return TPC_MPC_OK;
+
+// tpc_mpc_solve_batch_compact's arrays as a staging table: v, dy, dphi in, front and rear out in the solve's
+// arithmetic, the optional iteration counts (int32) out
+enum { kCompactArrays = 6 };
+void compact_table(StagedArray (&t)[kCompactArrays], int dtype, int64_t n, const void* v, const void* dy, const void* dphi,
+                   void* front, void* rear, int32_t* iters) {
+    const int es = (int)esize(dtype);
+    t[0] = staged(v, kStageIn, 1, n, es);
+    t[1] = staged(dy, kStageIn, 1, n, es);
+    t[2] = staged(dphi, kStageIn, 1, n, es);
+    t[3] = staged(front, kStageOut, 1, n, es);
+    t[4] = staged(rear, kStageOut, 1, n, es);
+    t[5] = staged(iters, kStageOut, 1, n, 4);
+}
+// the bytes of h->stage that a HOST call of it takes at most (iters asked for): what tpc_mpc_reserve grows h->stage to
+int64_t compact_stage_bytes(int dtype, int64_t n) {
+    static int32_t there;   // any array: the layout asks only whether one is there
+    StagedArray t[kCompactArrays];
+    compact_table(t, dtype, n, &there, &there, &there, &there, &there, &there);
+    return stage_layout(t, kCompactArrays, n);
 }
 
 }  // namespace
@@ -1143,37 +1164,29 @@ int tpc_mpc_solve_batch_compact(tpc_mpc_handle h, const tpc_mpc_params* p, int64
         if (rc) return rc;
         rc = check_compact_model(h, p);
         if (rc) return rc;
-        if (n < 0 || n > 0x7fffffffll) return fail(h, TPC_MPC_ERR_BAD_ARG, "need 0 <= n < 2^31");
-        if (mem != TPC_MPC_HOST && mem != TPC_MPC_DEVICE) return fail(h, TPC_MPC_ERR_BAD_ARG, "bad memory kind");
+        rc = check_batch(h, n, mem);
+        if (rc) return rc;
         if (n == 0) { if (flags_out) *flags_out = 0; return TPC_MPC_OK; }
         if (!v || !delta_y || !delta_phi || !steering_front || !steering_rear)
             return fail(h, TPC_MPC_ERR_BAD_ARG, "null batch pointer");
         HIP_TRY(h, hipSetDevice(h->device));
         hipStream_t s = (hipStream_t)stream;
-        const int64_t es = (int64_t)esize(p->dtype);
         StreamOrderScope order(h, s);
         rc = order.begin();
         if (rc) return rc;
         HIP_TRY(h, hipMemsetAsync(h->ws_words + 1, 0, sizeof(uint32_t), s));
-        if (mem == TPC_MPC_DEVICE) {
-            rc = compact_launch(h, p, n, v, delta_y, delta_phi, steering_front, steering_rear, iters, s);
+        const bool host = mem == TPC_MPC_HOST;
+        StagedArray t[kCompactArrays];
+        compact_table(t, p->dtype, n, v, delta_y, delta_phi, steering_front, steering_rear, iters);
+        if (host) {
+            rc = stage_in(h, t, kCompactArrays, n, s);
             if (rc) return rc;
-        } else {
-            // staging layout: v | dy | dphi | front | rear | iters
-            const int64_t col = pad256(n * es), icol = pad256(n * 4);
-            rc = ensure(h, &h->stage, &h->stage_bytes, 5 * col + icol);
+        }
+        rc = compact_launch(h, p, n, t[0].dev, t[1].dev, t[2].dev, t[3].dev, t[4].dev, (int32_t*)t[5].dev, s);
+        if (rc) return rc;
+        if (host) {
+            rc = stage_out(h, t, kCompactArrays, n, s);
             if (rc) return rc;
-            char* b = (char*)h->stage;
-            HIP_TRY(h, hipMemcpyAsync(b, v, n * es, hipMemcpyHostToDevice, s));
-            HIP_TRY(h, hipMemcpyAsync(b + col, delta_y, n * es, hipMemcpyHostToDevice, s));
-            HIP_TRY(h, hipMemcpyAsync(b + 2 * col, delta_phi, n * es, hipMemcpyHostToDevice, s));
-            int32_t* d_it = iters ? (int32_t*)(b + 5 * col) : nullptr;
-            rc = compact_launch(h, p, n, b, b + col, b + 2 * col, b + 3 * col, b + 4 * col, d_it, s);
-            if (rc) return rc;
-            HIP_TRY(h, hipMemcpyAsync(steering_front, b + 3 * col, n * es, hipMemcpyDeviceToHost, s));
-            HIP_TRY(h, hipMemcpyAsync(steering_rear, b + 4 * col, n * es, hipMemcpyDeviceToHost, s));
-            if (iters) HIP_TRY(h, hipMemcpyAsync(iters, d_it, n * 4, hipMemcpyDeviceToHost, s));
-            HIP_TRY(h, hipStreamSynchronize(s));
         }
         rc = order.end();
         if (rc) return rc;
@@ -1354,7 +1367,7 @@ int tpc_mpc_solve_batch_general_backward(tpc_mpc_handle h, const tpc_mpc_params*
         void* dst[10] = {g->dA, g->dB, g->dC, g->dQ, g->dR, g->dlower, g->dupper, g->dx0, g->dtargets, g->kkt_residual};
         const int64_t rows[21] = {4, 2 * I, 2, 2, I, I, I, 2, 2 * H, H * I, H * I,
                                   4, 2 * I, 2, 2, I, I, I, 2, 2 * H, 1};
-        return staged_run(h, io, mem, stream, flags_out, grad_scratch_bytes(I, H, n), src, dst, rows,
+        return staged_run(h, n, io->ld, mem, stream, flags_out, grad_scratch_bytes(I, H, n), src, dst, rows,
                           [&](int64_t ld, const void* const* in, void* const* out, hipStream_t s, uint32_t* hf) {
                               grad::Args a;
                               std::memset(&a, 0, sizeof(a));
@@ -1400,7 +1413,7 @@ int tpc_mpc_polish_batch_general(tpc_mpc_handle h, const tpc_mpc_params* p, cons
         StagedExtra x;
         x.width = width;
         x.inout = 9;
-        return staged_run(h, io, mem, stream, flags_out, polish_scratch_bytes(I, H, n), src, dst, rows,
+        return staged_run(h, n, io->ld, mem, stream, flags_out, polish_scratch_bytes(I, H, n), src, dst, rows,
                           [&](int64_t ld, const void* const* in, void* const* out, hipStream_t s, uint32_t* hf) {
                               polish::Args a;
                               std::memset(&a, 0, sizeof(a));
@@ -1483,12 +1496,13 @@ int rollout_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_genera
             if (src[c]) HIP_TRY(h, copy_rows(w + off[c], ldw * es, src[c], ld * es, n * es, comps[c], in_kind, s));
             else HIP_TRY(h, hipMemsetAsync(w + off[c], 0, (size_t)((int64_t)comps[c] * ldw * es), s));
         }
-        // the per-step arrays: the caller's (g), and what the kernels take for them (d)
-        const StepArrays g = step_arrays(io, H, steps, es, new_last_targets, plant, controls_out, states_out, iters_out,
-                                         sequences_out, polished ? q : nullptr);
-        StepArrays d;
-        rc = stage_steps(h, g, host, n, s, &d);
-        if (rc) return rc;
+        // the per-step arrays: the kernels take the caller's DEVICE arrays, or the slots of HOST arrays
+        StepArrays g = step_arrays(io, H, steps, (int)es, new_last_targets, plant, controls_out, states_out, iters_out,
+                                   sequences_out, polished ? q : nullptr);
+        if (host) {
+            rc = stage_steps(h, &g, n, s);
+            if (rc) return rc;
+        }
 
         GeneralArgs a;
         std::memset(&a, 0, sizeof(a));
@@ -1501,12 +1515,12 @@ int rollout_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_genera
 
         RolloutStepArgs r;
         std::memset(&r, 0, sizeof(r));
-        r.n = n; r.ld = ldw; r.ld_out = d.ld_out; r.ld_nlt = d.ld_nlt; r.I = I; r.H = H; r.steps = steps;
+        r.n = n; r.ld = ldw; r.ld_out = g.ld_out; r.ld_nlt = g.ld_nlt; r.I = I; r.H = H; r.steps = steps;
         r.A = a.A; r.B = a.B; r.C = a.C;
-        r.x = w + off[7]; r.targets = w + off[8]; r.controls = w + off[9]; r.new_last_targets = d.in[0];
-        r.controls_out = d.out[kStepCtrl]; r.states_out = d.out[kStepStates];
-        r.iters_step = a.iters; r.iters_out = (int32_t*)d.out[kStepIters]; r.sequences_out = d.out[kStepSeq];
-        r.disturbance = d.in[1]; r.ld_d = d.ld_d;
+        r.x = w + off[7]; r.targets = w + off[8]; r.controls = w + off[9]; r.new_last_targets = g.at(kStepNlt);
+        r.controls_out = g.at(kStepCtrl); r.states_out = g.at(kStepStates);
+        r.iters_step = a.iters; r.iters_out = g.at<int32_t>(kStepIters); r.sequences_out = g.at(kStepSeq);
+        r.disturbance = g.at(kStepDist); r.ld_d = g.ld_d;
         if (plant_abc) {
             HIP_TRY(h, copy_rows(w + o_pa, ldw * es, plant->A, ld * es, n * es, 4, in_kind, s));
             HIP_TRY(h, copy_rows(w + o_pb, ldw * es, plant->B, ld * es, n * es, 2 * I, in_kind, s));
@@ -1533,10 +1547,10 @@ int rollout_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_genera
             if (e != hipSuccess) return hip_fail(h, e, "kernel launch");
             r.step = st;
             if (polished) {   // the step's rows of the polish outputs; the sequence is polished where the loop keeps it
-                const int64_t at = (int64_t)st * d.ld_out;
-                pa.status = d.out[kStepStatus] ? (int32_t*)d.out[kStepStatus] + at : nullptr;
-                pa.res_in = d.out[kStepRin] ? (double*)d.out[kStepRin] + at : nullptr;
-                pa.res_out = d.out[kStepRout] ? (double*)d.out[kStepRout] + at : nullptr;
+                const int64_t at = (int64_t)st * g.ld_out;
+                pa.status = g.at(kStepStatus) ? g.at<int32_t>(kStepStatus) + at : nullptr;
+                pa.res_in = g.at(kStepRin) ? g.at<double>(kStepRin) + at : nullptr;
+                pa.res_out = g.at(kStepRout) ? g.at<double>(kStepRout) + at : nullptr;
                 e = launch_rollout_polish_step(I, pa, r, h->grad_ws, h->ws_words + 1, s);
             } else {
                 e = launch_rollout_step(p->dtype, r, s);
@@ -1548,7 +1562,7 @@ int rollout_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_genera
             HIP_TRY(h, copy_rows(io->controls_inout, ld * es, w + off[9], ldw * es, n * es, H * I, out_kind, s));
         if (io->v_inout) HIP_TRY(h, copy_rows(io->v_inout, ld * es, w + off[10], ldw * es, n * es, H * I, out_kind, s));
         if (host) {
-            rc = unstage_steps(h, g, d, n, s);
+            rc = stage_out(h, g.t, kStepCount, n, s);
             if (rc) return rc;
         }
         rc = order.end();
@@ -1603,10 +1617,8 @@ static int rollout_newton_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const 
         if (!rc) rc = check_steps(h, steps);
         if (rc) return rc;
         const bool solve = fallback == TPC_MPC_NEWTON_FALLBACK_SOLVE;
-        if (h->host_only && solve)
-            return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): the fallback solve runs on the device only; use TPC_MPC_NEWTON_FALLBACK_NONE");
-        if (h->host_only && mem == TPC_MPC_DEVICE)
-            return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): HOST memory only");
+        rc = check_host_only_newton(h, solve, mem);
+        if (rc) return rc;
         if (io->n == 0 || steps == 0) { if (flags_out) *flags_out = 0; return TPC_MPC_OK; }
         rc = check_model(h, io, controls_out != nullptr);
         if (rc) return rc;
@@ -1699,17 +1711,18 @@ static int rollout_newton_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const 
         uint32_t* d_words = (uint32_t*)(w + o_words);   // [0] the fallback's count, [1] phase 1's flags
         HIP_TRY(h, hipMemsetAsync(d_words, 0, 8, s));
 
-        // the per-step arrays: the caller's (g), and what the kernels take for them (d)
-        const StepArrays g = step_arrays(io, H, steps, 8, new_last_targets, plant, controls_out, states_out, iters_out,
-                                         sequences_out, q);
-        StepArrays d;
-        rc = stage_steps(h, g, host, n, s, &d);
-        if (rc) return rc;
-        const void *d_nlt = d.in[0], *d_dist = d.in[1];
-        void *d_ctrl = d.out[kStepCtrl], *d_states = d.out[kStepStates], *d_seq = d.out[kStepSeq];
-        void *d_rin = d.out[kStepRin], *d_rout = d.out[kStepRout];
-        int32_t *d_iters = (int32_t*)d.out[kStepIters], *d_status = (int32_t*)d.out[kStepStatus];
-        const int64_t ld_nlt = d.ld_nlt, ld_out = d.ld_out, ld_dist = d.ld_d;
+        // the per-step arrays: the kernels take the caller's DEVICE arrays, or the slots of HOST arrays
+        StepArrays g = step_arrays(io, H, steps, 8, new_last_targets, plant, controls_out, states_out, iters_out,
+                                   sequences_out, q);
+        if (host) {
+            rc = stage_steps(h, &g, n, s);
+            if (rc) return rc;
+        }
+        const void *d_nlt = g.at(kStepNlt), *d_dist = g.at(kStepDist);
+        void *d_ctrl = g.at(kStepCtrl), *d_states = g.at(kStepStates), *d_seq = g.at(kStepSeq);
+        void *d_rin = g.at(kStepRin), *d_rout = g.at(kStepRout);
+        int32_t *d_iters = g.at<int32_t>(kStepIters), *d_status = g.at<int32_t>(kStepStatus);
+        const int64_t ld_nlt = g.ld_nlt, ld_out = g.ld_out, ld_dist = g.ld_d;
 
         bind(w, ldw);
         a.r.ld_out = ld_out; a.r.ld_nlt = ld_nlt;
@@ -1804,7 +1817,7 @@ static int rollout_newton_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const 
         if (io->v_inout) HIP_TRY(h, copy_rows(io->v_inout, ld * 8, d_vfinal, ldw * 8, n * 8, H * I, out_kind, s));
         if (first_unverified) HIP_TRY(h, hipMemcpyAsync(first_unverified, d_fu, (size_t)n * 4, out_kind, s));
         if (host) {
-            rc = unstage_steps(h, g, d, n, s);
+            rc = stage_out(h, g.t, kStepCount, n, s);
             if (rc) return rc;
         }
         rc = order.end();
@@ -1825,12 +1838,12 @@ int tpc_mpc_rollout_newton(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_
 // (mpc_newton_compact.hip); with TPC_MPC_NEWTON_FALLBACK_SOLVE the instances it could not verify are gathered and
 // expanded to the general form on the device, run through tpc_mpc_solve_batch_general and tpc_mpc_polish_batch_general
 // and scattered back.  One 4-byte read-back (the fallback's count) sits between the phases; a host-only handle runs
-// phase 1 on the calling thread.  The Newton working set of tpc_mpc_rollout_newton holds the staging rows, the queue and
-// the compact batch.
+// phase 1 on the calling thread.  The Newton working set of tpc_mpc_rollout_newton holds the queue and the compact
+// batch; HOST arrays are staged in h->stage (stage_in / stage_out).
 // `rows`: tpc_mpc_solve_batch_compact_exact_rows -- the ten model values per instance from params_rows ([10], ld n, in
-// `mem` like v), p's own neither read nor checked; HOST rows are staged behind v, dy, dphi.
-// `warm`: tpc_mpc_solve_batch_compact_exact_from -- phase 1 starts from `start` ([H*2], ld n, in `mem`; HOST rows are
-// staged behind the others) on the warm kernels; everything after phase 1 is the same code.
+// `mem` like v), p's own neither read nor checked.
+// `warm`: tpc_mpc_solve_batch_compact_exact_from -- phase 1 starts from `start` ([H*2], ld n, in `mem`) on the warm
+// kernels; everything after phase 1 is the same code.
 static int compact_exact_impl(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t n, const void* v, const void* delta_y,
                               const void* delta_phi, bool rows, const void* params_rows, bool warm, const void* start,
                               const tpc_mpc_polish* q,
@@ -1847,45 +1860,47 @@ static int compact_exact_impl(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t
             rc = check_compact_model(h, p);
             if (rc) return rc;
         }
-        if (n < 0 || n > 0x7fffffffll) return fail(h, TPC_MPC_ERR_BAD_ARG, "need 0 <= n < 2^31");
-        if (mem != TPC_MPC_HOST && mem != TPC_MPC_DEVICE) return fail(h, TPC_MPC_ERR_BAD_ARG, "bad memory kind");
-        rc = check_polish(h, q);
+        rc = check_batch(h, n, mem);
+        if (!rc) rc = check_polish(h, q);
         if (!rc) rc = check_fallback(h, fallback);
         if (rc) return rc;
         const bool solve = fallback == TPC_MPC_NEWTON_FALLBACK_SOLVE;
-        if (h->host_only && solve)
-            return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): the fallback solve runs on the device only; use TPC_MPC_NEWTON_FALLBACK_NONE");
-        if (h->host_only && mem == TPC_MPC_DEVICE)
-            return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): HOST memory only");
+        rc = check_host_only_newton(h, solve, mem);
+        if (rc) return rc;
         if (n == 0) { if (flags_out) *flags_out = 0; return TPC_MPC_OK; }
         if (!v || !delta_y || !delta_phi || !steering_front || !steering_rear)
             return fail(h, TPC_MPC_ERR_BAD_ARG, "null batch pointer");
         if (rows && !params_rows) return fail(h, TPC_MPC_ERR_BAD_ARG, "null params_rows");
         if (warm && !start) return fail(h, TPC_MPC_ERR_BAD_ARG, "null start");
         const int H = p->horizon;
-        constexpr int kP = cgrad::kParams;
 
         cexact::Args a;
         std::memset(&a, 0, sizeof(a));
         a.n = n;
-        if (!rows) {
-            a.T = p->step_size; a.l = p->wheelbase; a.q0 = p->weight_y; a.q1 = p->weight_phi;
-            a.r[0] = p->weight_steering_front; a.r[1] = p->weight_steering_rear;
-            for (int j = 0; j < 2; ++j) { a.lo[j] = p->lower[j]; a.hi[j] = p->upper[j]; }
-        }
-        a.params = rows ? (const double*)params_rows : nullptr;
-        a.ld_params = n;
+        if (!rows) bind_compact_model(&a, p);
         a.tol = q->tol; a.max_rounds = q->max_rounds;
         a.raise_not_polished = solve ? 0 : 1;
-        a.ld_seq = n;
-        a.start = warm ? (const double*)start : nullptr;
-        a.ld_start = n;
+        // the call's arrays, every one with the leading dimension n in the caller's memory
+        enum { kV, kDy, kDphi, kParams, kStart, kFront, kRear, kSeq, kRin, kRout, kStatus, kFell, kCount };
+        StagedArray t[kCount] = {staged(v, kStageIn, 1, n), staged(delta_y, kStageIn, 1, n), staged(delta_phi, kStageIn, 1, n),
+                                 staged(rows ? params_rows : nullptr, kStageIn, cgrad::kParams, n),
+                                 staged(warm ? start : nullptr, kStageIn, 2 * H, n),
+                                 staged(steering_front, kStageOut, 1, n), staged(steering_rear, kStageOut, 1, n),
+                                 staged(sequence_out, kStageOut, 2 * H, n), staged(q->residual_in, kStageOut, 1, n),
+                                 staged(q->residual_out, kStageOut, 1, n), staged(q->status, kStageOut, 1, n, 4),
+                                 staged(fell_back, kStageOut, 1, n, 4)};
+        // what the kernels take: the caller's arrays (DEVICE, or a host-only handle) or the slots of HOST arrays
+        auto bind = [&](int64_t ld) {
+            a.v = (const double*)t[kV].dev; a.dy = (const double*)t[kDy].dev; a.dphi = (const double*)t[kDphi].dev;
+            a.params = (const double*)t[kParams].dev; a.start = (const double*)t[kStart].dev;
+            a.front = (double*)t[kFront].dev; a.rear = (double*)t[kRear].dev; a.seq = (double*)t[kSeq].dev;
+            a.res_in = (double*)t[kRin].dev; a.res_out = (double*)t[kRout].dev;
+            a.status = (int32_t*)t[kStatus].dev; a.fell_back = (int32_t*)t[kFell].dev;
+            a.ld_params = a.ld_start = a.ld_seq = ld;
+        };
 
         if (h->host_only) {   // on the calling thread, straight from and into the caller's arrays
-            a.v = (const double*)v; a.dy = (const double*)delta_y; a.dphi = (const double*)delta_phi;
-            a.front = (double*)steering_front; a.rear = (double*)steering_rear; a.seq = (double*)sequence_out;
-            a.status = q->status; a.res_in = (double*)q->residual_in; a.res_out = (double*)q->residual_out;
-            a.fell_back = fell_back;
+            bind(n);
             const uint32_t f = compact_exact_host(H, a);
             if (flags_out) *flags_out = f;
             return TPC_MPC_OK;
@@ -1897,14 +1912,11 @@ static int compact_exact_impl(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t
         rc = order.begin();
         if (rc) return rc;
         const bool host = mem == TPC_MPC_HOST;
-        // the working set: the queue and two words ([0] the fallback's count, [1] phase 1's flags), then for HOST
-        // arrays the staging rows, leading dimension ldw: v dy dphi params[10] start[2H] | front rear seq[2H] res_in
-        // res_out | status fell_back
-        const int64_t ldw = (n + 63) / 64 * 64;
-        const int64_t o_words = ldw * 4, o_stage = o_words + 256;
-        const int64_t rows8 = 3 + (rows ? kP : 0) + (warm ? 2 * H : 0) + 2 + (sequence_out ? 2 * H : 0) + (q->residual_in ? 1 : 0) + (q->residual_out ? 1 : 0);
-        const int64_t o_i32 = o_stage + rows8 * ldw * 8;
-        rc = ensure(h, &h->newton, &h->newton_bytes, host ? o_i32 + 2 * ldw * 4 : o_stage);
+        // the working set: the queue and two words ([0] the fallback's count, [1] phase 1's flags); HOST arrays are
+        // staged in h->stage, which nothing writes between phase 1 and the copies back (the fallback's entries are
+        // called with TPC_MPC_DEVICE)
+        const int64_t o_words = stage_ld(n) * 4;
+        rc = ensure(h, &h->newton, &h->newton_bytes, o_words + 256);
         if (rc) return rc;
         if (!compact_exact_in_registers(H)) {
             rc = ensure(h, &h->grad_ws, &h->grad_ws_bytes, pad256(polish_scratch_bytes(2, H, n)));
@@ -1914,40 +1926,11 @@ static int compact_exact_impl(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t
         int32_t* d_idx = (int32_t*)w;
         uint32_t* d_words = (uint32_t*)(w + o_words);
         HIP_TRY(h, hipMemsetAsync(d_words, 0, 8, s));
-        if (!host) {
-            a.v = (const double*)v; a.dy = (const double*)delta_y; a.dphi = (const double*)delta_phi;
-            a.front = (double*)steering_front; a.rear = (double*)steering_rear; a.seq = (double*)sequence_out;
-            a.status = q->status; a.res_in = (double*)q->residual_in; a.res_out = (double*)q->residual_out;
-            a.fell_back = fell_back;
-        } else {
-            int64_t r = 0;
-            auto row = [&](bool on, int64_t rows) -> double* {
-                double* at = on ? (double*)(w + o_stage + r * ldw * 8) : nullptr;
-                if (on) r += rows;
-                return at;
-            };
-            double *sv = row(true, 1), *sdy = row(true, 1), *sdphi = row(true, 1);
-            HIP_TRY(h, hipMemcpyAsync(sv, v, (size_t)n * 8, hipMemcpyHostToDevice, s));
-            HIP_TRY(h, hipMemcpyAsync(sdy, delta_y, (size_t)n * 8, hipMemcpyHostToDevice, s));
-            HIP_TRY(h, hipMemcpyAsync(sdphi, delta_phi, (size_t)n * 8, hipMemcpyHostToDevice, s));
-            a.v = sv; a.dy = sdy; a.dphi = sdphi;
-            if (rows) {
-                double* sp = row(true, kP);
-                HIP_TRY(h, copy_rows(sp, ldw * 8, params_rows, n * 8, n * 8, kP, hipMemcpyHostToDevice, s));
-                a.params = sp; a.ld_params = ldw;
-            }
-            if (warm) {
-                double* ss = row(true, 2 * H);
-                HIP_TRY(h, copy_rows(ss, ldw * 8, start, n * 8, n * 8, 2 * H, hipMemcpyHostToDevice, s));
-                a.start = ss; a.ld_start = ldw;
-            }
-            a.front = row(true, 1); a.rear = row(true, 1);
-            a.seq = row(sequence_out != nullptr, 2 * H);
-            a.ld_seq = ldw;
-            a.res_in = row(q->residual_in != nullptr, 1); a.res_out = row(q->residual_out != nullptr, 1);
-            a.status = q->status ? (int32_t*)(w + o_i32) : nullptr;
-            a.fell_back = fell_back ? (int32_t*)(w + o_i32 + ldw * 4) : nullptr;
+        if (host) {
+            rc = stage_in(h, t, kCount, n, s);
+            if (rc) return rc;
         }
+        bind(host ? stage_ld(n) : n);
         a.fb_index = solve ? d_idx : nullptr;
         a.fb_count = d_words;
         hipError_t e = compact_exact(H, a, h->grad_ws, d_words + 1, s);
@@ -2002,15 +1985,8 @@ static int compact_exact_impl(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t
         if (e != hipSuccess) return hip_fail(h, e, "flag merge launch");
 
         if (host) {
-            HIP_TRY(h, hipMemcpyAsync(steering_front, a.front, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-            HIP_TRY(h, hipMemcpyAsync(steering_rear, a.rear, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-            if (sequence_out)
-                HIP_TRY(h, copy_rows(sequence_out, n * 8, a.seq, ldw * 8, n * 8, 2 * H, hipMemcpyDeviceToHost, s));
-            if (q->residual_in) HIP_TRY(h, hipMemcpyAsync(q->residual_in, a.res_in, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-            if (q->residual_out) HIP_TRY(h, hipMemcpyAsync(q->residual_out, a.res_out, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-            if (q->status) HIP_TRY(h, hipMemcpyAsync(q->status, a.status, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-            if (fell_back) HIP_TRY(h, hipMemcpyAsync(fell_back, a.fell_back, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-            HIP_TRY(h, hipStreamSynchronize(s));
+            rc = stage_out(h, t, kCount, n, s);
+            if (rc) return rc;
         }
         rc = order.end();
         if (rc) return rc;
@@ -2046,8 +2022,8 @@ int tpc_mpc_solve_batch_compact_exact_from(tpc_mpc_handle h, const tpc_mpc_param
 
 // The backward pass of the exact compact solve: one launch of the adjoint sweep on the model built from v
 // (mpc_compact_grad.hip), and with dparams one more, single-block launch that sums the blocks' partial rows.  The
-// per-step workspace (none at the register kernels' horizons) and the partial rows live in the gradient workspace; HOST
-// arrays are staged row by row, as tpc_mpc_solve_batch_compact_exact stages them.
+// per-step workspace (none at the register kernels' horizons) and the partial rows live in the gradient workspace; a
+// one-launch entry like the general backward pass (staged_run).
 // `rows`: tpc_mpc_solve_batch_compact_exact_rows_backward, as compact_exact_impl takes params_rows.
 static int compact_exact_backward_impl(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t n, const void* v,
                                        const void* delta_y, const void* delta_phi, bool rows, const void* params_rows,
@@ -2063,8 +2039,8 @@ static int compact_exact_backward_impl(tpc_mpc_handle h, const tpc_mpc_params* p
             rc = check_compact_model(h, p);
             if (rc) return rc;
         }
-        if (n < 0 || n > 0x7fffffffll) return fail(h, TPC_MPC_ERR_BAD_ARG, "need 0 <= n < 2^31");
-        if (mem != TPC_MPC_HOST && mem != TPC_MPC_DEVICE) return fail(h, TPC_MPC_ERR_BAD_ARG, "bad memory kind");
+        rc = check_batch(h, n, mem);
+        if (rc) return rc;
         if (!g) return fail(h, TPC_MPC_ERR_BAD_ARG, "null gradient struct");
         if (h->host_only && mem == TPC_MPC_DEVICE)
             return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): the backward pass takes HOST memory only");
@@ -2086,95 +2062,39 @@ static int compact_exact_backward_impl(tpc_mpc_handle h, const tpc_mpc_params* p
         if (!sequence) return fail(h, TPC_MPC_ERR_BAD_ARG, "null sequence");
         if (rows && !params_rows) return fail(h, TPC_MPC_ERR_BAD_ARG, "null params_rows");
         const int H = p->horizon;
-
-        cgrad::Args a;
-        std::memset(&a, 0, sizeof(a));
-        a.n = n; a.ld = n;
-        if (!rows) {
-            a.T = p->step_size; a.l = p->wheelbase; a.q0 = p->weight_y; a.q1 = p->weight_phi;
-            a.r[0] = p->weight_steering_front; a.r[1] = p->weight_steering_rear;
-            for (int j = 0; j < 2; ++j) { a.lo[j] = p->lower[j]; a.hi[j] = p->upper[j]; }
-        }
-        auto bind = [&]() {   // straight from and into the caller's arrays
-            a.params = rows ? (const double*)params_rows : nullptr;
-            a.v = (const double*)v; a.dy = (const double*)delta_y; a.dphi = (const double*)delta_phi;
-            a.seq = (const double*)sequence; a.status = status;
-            a.gf = (const double*)g->grad_front; a.gr = (const double*)g->grad_rear;
-            a.gs = (const double*)g->grad_sequence;
-            a.dv = (double*)g->dv; a.ddy = (double*)g->ddelta_y; a.ddphi = (double*)g->ddelta_phi;
-            a.rows = (double*)g->dparams_rows; a.kkt = (double*)g->kkt_residual;
-        };
-
-        if (h->host_only) {   // on the calling thread
-            bind();
-            const uint32_t f = compact_grad_host(H, a, (double*)g->dparams);
-            if (flags_out) *flags_out = f;
-            return TPC_MPC_OK;
-        }
-
-        HIP_TRY(h, hipSetDevice(h->device));
-        hipStream_t s = (hipStream_t)stream;
-        StreamOrderScope order(h, s);
-        rc = order.begin();
-        if (rc) return rc;
+        // the arrays in order: 9 inputs (params_rows and status, int32, may be null like the upstream gradients), then
+        // 6 outputs; dparams is one row of kP sums, not one element per instance
+        const void* src[9] = {rows ? params_rows : nullptr, v, delta_y, delta_phi, sequence, g->grad_front, g->grad_rear,
+                              g->grad_sequence, status};
+        void* dst[6] = {g->dv, g->ddelta_y, g->ddelta_phi, g->dparams_rows, g->kkt_residual, g->dparams};
+        const int64_t comps[15] = {kP, 1, 1, 1, 2 * H, 1, 1, 2 * H, 1, 1, 1, 1, kP, 1, 1};
+        int width[15] = {0};
+        width[8] = 4;
+        int64_t elems[15] = {0};
+        elems[14] = kP;
+        StagedExtra x;
+        x.width = width;
+        x.elems = elems;
         // the gradient workspace: the per-step slots, then the blocks' partial rows
         const int64_t ws_b = pad256(compact_grad_scratch_bytes(H, n));
         const int64_t part_b = g->dparams ? pad256(kP * compact_grad_blocks(n) * 8) : 0;
-        rc = ensure(h, &h->grad_ws, &h->grad_ws_bytes, ws_b + part_b);
-        if (rc) return rc;
-        double* partials = g->dparams ? (double*)((char*)h->grad_ws + ws_b) : nullptr;
-        double* d_dparams = (double*)g->dparams;
-
-        // HOST arrays: the rows in order, leading dimension ldw, each present one copied on its own (n elements)
-        const int64_t ldw = (n + 63) / 64 * 64;
-        const void* src[8] = {v, delta_y, delta_phi, sequence, g->grad_front, g->grad_rear, g->grad_sequence, status};
-        void* dst[6] = {g->dv, g->ddelta_y, g->ddelta_phi, g->dparams_rows, g->kkt_residual, g->dparams};
-        const int comps[14] = {1, 1, 1, 2 * H, 1, 1, 2 * H, 1, 1, 1, 1, kP, 1, 1};
-        int64_t off[14] = {0};
-        if (host) {
-            int64_t total = rows ? pad256((int64_t)kP * ldw * 8) : 0;   // params_rows first, when there are any
-            for (int c = 0; c < 14; ++c) {
-                const bool given = c < 8 ? src[c] != nullptr : dst[c - 8] != nullptr;
-                off[c] = total;
-                if (given) total += pad256((int64_t)comps[c] * ldw * 8);
-            }
-            rc = ensure(h, &h->stage, &h->stage_bytes, total);
-            if (rc) return rc;
-            char* b = (char*)h->stage;
-            if (rows) {
-                HIP_TRY(h, copy_rows(b, ldw * 8, params_rows, n * 8, n * 8, kP, hipMemcpyHostToDevice, s));
-                a.params = (const double*)b;
-            }
-            for (int c = 0; c < 8; ++c) {
-                if (!src[c]) continue;
-                const int64_t es = c == 7 ? 4 : 8;   // status is int32
-                HIP_TRY(h, copy_rows(b + off[c], ldw * es, src[c], n * es, n * es, comps[c], hipMemcpyHostToDevice, s));
-            }
-            auto in = [&](int c) { return src[c] ? (const double*)(b + off[c]) : nullptr; };
-            auto out = [&](int c) { return dst[c] ? (double*)(b + off[8 + c]) : nullptr; };
-            a.ld = ldw;
-            a.v = in(0); a.dy = in(1); a.dphi = in(2); a.seq = in(3); a.gf = in(4); a.gr = in(5); a.gs = in(6);
-            a.status = status ? (const int32_t*)(b + off[7]) : nullptr;
-            a.dv = out(0); a.ddy = out(1); a.ddphi = out(2); a.rows = out(3); a.kkt = out(4);
-            d_dparams = out(5);
-        } else {
-            bind();
-        }
-        HIP_TRY(h, hipMemsetAsync(h->ws_words + 1, 0, sizeof(uint32_t), s));
-        hipError_t e = compact_grad(H, a, h->grad_ws, partials, d_dparams, h->ws_words + 1, s);
-        if (e != hipSuccess) return hip_fail(h, e, "kernel launch");
-        if (host) {
-            const char* b = (const char*)h->stage;
-            for (int c = 0; c < 5; ++c)
-                if (dst[c])
-                    HIP_TRY(h, copy_rows(dst[c], n * 8, b + off[8 + c], ldw * 8, n * 8, comps[8 + c],
-                                         hipMemcpyDeviceToHost, s));
-            if (dst[5]) HIP_TRY(h, hipMemcpyAsync(dst[5], d_dparams, kP * 8, hipMemcpyDeviceToHost, s));
-            HIP_TRY(h, hipStreamSynchronize(s));
-        }
-        rc = order.end();
-        if (rc) return rc;
-        return finish_flags(h, flags_out, s);
+        return staged_run(h, n, n, mem, stream, flags_out, ws_b + part_b, src, dst, comps,
+                          [&](int64_t ld, const void* const* in, void* const* out, hipStream_t s, uint32_t* hf) {
+                              cgrad::Args a;
+                              std::memset(&a, 0, sizeof(a));
+                              a.n = n; a.ld = ld;
+                              if (!rows) bind_compact_model(&a, p);
+                              a.params = (const double*)in[0];
+                              a.v = (const double*)in[1]; a.dy = (const double*)in[2]; a.dphi = (const double*)in[3];
+                              a.seq = (const double*)in[4]; a.gf = (const double*)in[5]; a.gr = (const double*)in[6];
+                              a.gs = (const double*)in[7]; a.status = (const int32_t*)in[8];
+                              a.dv = (double*)out[0]; a.ddy = (double*)out[1]; a.ddphi = (double*)out[2];
+                              a.rows = (double*)out[3]; a.kkt = (double*)out[4];
+                              if (hf) { *hf = compact_grad_host(H, a, (double*)out[5]); return hipSuccess; }
+                              double* partials = out[5] ? (double*)((char*)h->grad_ws + ws_b) : nullptr;
+                              return compact_grad(H, a, h->grad_ws, partials, (double*)out[5], h->ws_words + 1, s);
+                          },
+                          x);
     });
 }
 
@@ -2280,12 +2200,12 @@ static int rollout_backward_impl(tpc_mpc_handle h, const tpc_mpc_params* p, cons
         const int64_t rows[kIn + kOut] = {4, 2 * I, 2, 2, I, I, I, 2, 2 * H, 2 * S, S * H * I, 2 * S, S * I, 2 * S,
                                           4, 2 * I, 2,
                                           4, 2 * I, 2, 2, I, I, I, 2, 2 * H, 2 * S, 1, 4, 2 * I, 2, 2 * S};
-        int64_t dst_ld[kOut] = {0};
-        dst_ld[14] = ld_dd;
+        int64_t lds[kIn + kOut] = {0};
+        lds[kIn + 14] = ld_dd;
         StagedExtra x;
-        x.dst_ld = dst_ld;
+        x.ld = lds;
         const bool staged = !h->host_only && mem == TPC_MPC_HOST;
-        return staged_run(h, io, mem, stream, flags_out, grad_scratch_bytes(I, H, n), src, dst, rows,
+        return staged_run(h, n, io->ld, mem, stream, flags_out, grad_scratch_bytes(I, H, n), src, dst, rows,
                           [&](int64_t ld, const void* const* in, void* const* out, hipStream_t s, uint32_t* hf) {
                               grad::RollArgs a;
                               std::memset(&a, 0, sizeof(a));
@@ -2359,7 +2279,7 @@ int tpc_mpc_solve_batch_general_forward(tpc_mpc_handle h, const tpc_mpc_params* 
         const int64_t rows[21] = {4, 2 * I, 2, 2, I, I, I, 2, 2 * H, H * I,
                                   4 * K, 2 * I * K, 2 * K, 2 * K, I * K, I * K, I * K, 2 * K, 2 * H * K, 0,
                                   (int64_t)H * I * K};
-        return staged_run(h, io, mem, stream, flags_out, tangent_scratch_bytes(I, H, n, K, true), src, dst, rows,
+        return staged_run(h, n, io->ld, mem, stream, flags_out, tangent_scratch_bytes(I, H, n, K, true), src, dst, rows,
                           [&](int64_t ld, const void* const* in, void* const* out, hipStream_t s, uint32_t* hf) {
                               tangent::Args a;
                               std::memset(&a, 0, sizeof(a));
@@ -2426,16 +2346,16 @@ static int rollout_forward_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const
                                 sep ? plant->A : nullptr, sep ? plant->B : nullptr, sep ? plant->C : nullptr,
                                 sep ? pt->tA : nullptr, sep ? pt->tB : nullptr, sep ? pt->tC : nullptr,
                                 use_plant ? pt->tdisturbance : nullptr};
-        int64_t src_ld[kIn] = {0};
-        src_ld[28] = ld_td;
+        int64_t lds[kIn + 2] = {0};
+        lds[28] = ld_td;
         void* dst[2] = {tcontrols, tstates};
         const int64_t rows[kIn + 2] = {4, 2 * I, 2, 2, I, I, I, 2, 2 * H, 2 * S, S * H * I, 2 * S,
                                        4 * K, 2 * I * K, 2 * K, 2 * K, I * K, I * K, I * K, 2 * K, 2 * H * K, 2 * S * K,
                                        4, 2 * I, 2, 4 * K, 2 * I * K, 2 * K, 2 * S * K,
                                        S * I * K, 2 * S * K};
         StagedExtra x;
-        x.src_ld = src_ld;
-        return staged_run(h, io, mem, stream, flags_out, tangent_scratch_bytes(I, H, n, K, false), src, dst, rows,
+        x.ld = lds;
+        return staged_run(h, n, io->ld, mem, stream, flags_out, tangent_scratch_bytes(I, H, n, K, false), src, dst, rows,
                           [&](int64_t ld, const void* const* in, void* const* out, hipStream_t s, uint32_t* hf) {
                               tangent::RollArgs a;
                               std::memset(&a, 0, sizeof(a));
@@ -2639,8 +2559,8 @@ int tpc_mpc_reserve(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t n, int me
     return guarded(h, [&]() -> int {
         int rc = check_common(h, p);
         if (rc) return rc;
-        if (n < 0 || n > 0x7fffffffll) return fail(h, TPC_MPC_ERR_BAD_ARG, "need 0 <= n < 2^31");
-        if (mem != TPC_MPC_HOST && mem != TPC_MPC_DEVICE) return fail(h, TPC_MPC_ERR_BAD_ARG, "bad memory kind");
+        rc = check_batch(h, n, mem);
+        if (rc) return rc;
         if (n == 0) return TPC_MPC_OK;
         HIP_TRY(h, hipSetDevice(h->device));
         // the larger of the kernel families' needs, so that every choice of AUTO is covered -- and the buffer the
@@ -2662,8 +2582,7 @@ int tpc_mpc_reserve(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t n, int me
             }
         }
         if (mem == TPC_MPC_HOST) {
-            const int64_t col = pad256(n * (int64_t)esize(p->dtype)), icol = pad256(n * 4);
-            rc = ensure(h, &h->stage, &h->stage_bytes, 5 * col + icol);
+            rc = ensure(h, &h->stage, &h->stage_bytes, compact_stage_bytes(p->dtype, n));
             if (rc) return rc;
         }
         return TPC_MPC_OK;
@@ -2677,11 +2596,11 @@ int tpc_mpc_x_set_work_hint(tpc_mpc_handle h, const int32_t* hint, int64_t n, in
         h->hint = nullptr;
         h->hint_n = 0;
         if (!hint || n == 0) return TPC_MPC_OK;   // cleared
-        if (n < 0 || n > 0x7fffffffll) return fail(h, TPC_MPC_ERR_BAD_ARG, "need 0 <= n < 2^31");
-        if (mem != TPC_MPC_HOST && mem != TPC_MPC_DEVICE) return fail(h, TPC_MPC_ERR_BAD_ARG, "bad memory kind");
+        int rc = check_batch(h, n, mem);
+        if (rc) return rc;
         // always the handle's own copy: no caller pointer outlives the call that received it
         HIP_TRY(h, hipSetDevice(h->device));
-        int rc = ensure(h, &h->hint_own, &h->hint_own_bytes, n * 4);
+        rc = ensure(h, &h->hint_own, &h->hint_own_bytes, n * 4);
         if (rc) return rc;
         // the previous solve may still be reading the old copy: wait for it (its stream-order event), then copy
         // synchronously -- a DEVICE hint must be complete when this is called
