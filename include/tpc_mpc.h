@@ -34,7 +34,7 @@ extern "C" {
 
 #define TPC_MPC_ABI_VERSION 5   /* 5 = 4 + new symbols only (the split-named sharded entries; later additions, such as
                                    tpc_mpc_solve_batch_general_backward, tpc_mpc_rollout_record / _backward / _polished / _newton, tpc_mpc_polish_batch_general
-                                   and tpc_mpc_solve_batch_compact_exact / _exact_backward / _exact_rows / _exact_rows_backward / _exact_from, are new symbols and structs only and keep 5);
+                                   and tpc_mpc_solve_batch_compact_exact / _exact_backward / _exact_rows / _exact_rows_backward / _exact_from / _exact_forward, are new symbols and structs only and keep 5);
                                    4 broke 3: tpc_mpc_params.reserved became .options and must be zero-initialised */
 
 typedef struct tpc_mpc_context* tpc_mpc_handle;
@@ -646,6 +646,68 @@ int tpc_mpc_solve_batch_compact_exact_from(tpc_mpc_handle h, const tpc_mpc_param
                                            int32_t fallback, void* steering_front, void* steering_rear,
                                            void* sequence_out, int32_t* fell_back, uint32_t* flags_out, int mem,
                                            void* stream);
+
+/* The K directions of tpc_mpc_solve_batch_compact_exact_forward, fp64: each a tangent of every input of
+ * tpc_mpc_solve_batch_compact_exact.  A NULL array is a zero tangent.  The ten parameters are indexed as in
+ * tpc_mpc_compact_grad. */
+typedef struct tpc_mpc_compact_tangents {
+    int32_t directions, reserved;           /* K >= 1, K * n < 2^31                                                  */
+    const void *tv, *tdelta_y, *tdelta_phi; /* optional [K], ld n: element (d, k) at base[d*n + k]; NULL = zero      */
+    const void *tparams;                    /* optional [K*10] ELEMENTS (not per instance), in `mem`, as dparams is
+                                               [10]: element (d, c) at base[d*10 + c], the tangent of the ten shared
+                                               parameters; without params_rows only                                   */
+    const void *tparams_rows;               /* optional [K*10], ld n: (d, c, k) at base[(d*10 + c)*n + k]; needs
+                                               params_rows                                                            */
+} tpc_mpc_compact_tangents;
+
+/* No reference counterpart.  The forward-mode derivative of tpc_mpc_solve_batch_compact_exact / _exact_rows: for K
+ * directions, the tangents of steering_front, steering_rear and (optionally) sequence_out along a tangent of v,
+ * delta_y, delta_phi and the ten parameters, without the general form ever being written.  It is what Gauss-Newton
+ * and Levenberg-Marquardt fits of a few shared parameters to many residuals need: the per-instance Jacobian, K
+ * columns per call.
+ *   Definition.  Instance k, direction d.  T, l, q0, q1, r[2], lo[2], hi[2] come from p, or from column k of
+ *   params_rows; the model is tpc_mpc_solve_batch_compact_exact's (Tv = T * v, tvl = Tv / l: A = [1, Tv; 0, 1],
+ *   B = [0, Tv; tvl, -tvl], C = 0, x0 = 0, every target (delta_y, delta_phi)).  The direction's values are tv, tdy,
+ *   tdphi and tp[0..9] = tq0, tq1, tr0, tr1, tT, tl, tlo0, tlo1, thi0, thi1; an absent array counts as +0.0.  Then,
+ *   every operation rounded on its own:
+ *     tTv  = tT * v + T * tv
+ *     ttvl = (tTv - tvl * tl) / l
+ *     tA = [0, tTv; 0, 0]      tB = [0, tTv; ttvl, -ttvl]      tC = 0      tx0 = 0
+ *     tQ, tR, tlower, tupper = (tq0, tq1), (tr0, tr1), (tlo0, tlo1), (thi0, thi1);  every target's tangent (tdy, tdphi)
+ *   and the tangent sweep of tpc_mpc_solve_batch_general_forward (csrc/mpc_tangent_model.h, step<2>, unchanged) runs
+ *   on that model, that tangent and `sequence`: tsequence is its tU, tfront = tU(0, 0), trear = tU(0, 1).  These equal,
+ *   as numbers (the sign of a zero is free), what tpc_mpc_solve_batch_general_forward returns for the expanded arrays
+ *   and tangents.  When `sequence` is the optimum this is the derivative of the optimum; the map is the transpose of
+ *   tpc_mpc_solve_batch_compact_exact_backward to rounding.
+ *   Excluded.  status != NULL && status[k] < 0: every direction's block of instance k is zero, without a flag of its
+ *   own.  A non-finite v, target, sequence or model value, or a non-finite tangent in direction d (given params_rows:
+ *   a non-finite step_size or wheelbase too): TPC_MPC_FLAG_NONFINITE, and the (d, k) block is zero -- the other
+ *   directions of k are not touched by one direction's tangent.  A model that breaks dlib's requires clause:
+ *   TPC_MPC_FLAG_BAD_MODEL, and the (d, k) block is zero.
+ *   params_rows == NULL: p's ten values, validated as tpc_mpc_solve_batch_compact_exact_backward validates them; a given
+ *   t->tparams_rows is TPC_MPC_ERR_BAD_ARG.  params_rows given ([10], ld n): the rows entry's rules -- p's ten model
+ *   fields neither read nor validated, invalid columns decided per instance; a given t->tparams is
+ *   TPC_MPC_ERR_BAD_ARG.
+ *   Method.  One lane per (direction, instance), L = d*n + k (csrc/mpc_compact_tangent.hip): 3 + 2H doubles and the
+ *   direction's values in, two doubles out; the per-step values in the handle's gradient workspace, at horizons 4 and
+ *   5 without tsequence in registers.  A tangent of shared parameters reads no per-instance tangent array.  The same
+ *   bits with and without tsequence.
+ * v, delta_y, delta_phi [n] and sequence (SoA [H*2], ld n, as sequence_out) are required; status (int32 [n]) is
+ * optional.  Outputs: tfront, trear [K] with ld n (element (d, k) at base[d*n + k]) and tsequence [K*2H] with ld n
+ * (element (d, t*2+j, k) at base[(d*2H + t*2+j)*n + k]); each may be NULL, not all three.  fp64 only, horizons 1..64.
+ * TPC_MPC_ERR_BAD_ARG: a null t, a null sequence or batch pointer, directions < 1 or directions * n >= 2^31, all
+ * three outputs NULL, a dtype other than TPC_MPC_F64.  n == 0 returns TPC_MPC_OK with flags 0.  HOST arrays are
+ * staged; with DEVICE memory and flags_out == NULL the call is asynchronous on `stream`.  A host-only handle
+ * (TPC_MPC_DEVICE_NONE) runs HOST batches on the calling thread with the kernel's bits and returns
+ * TPC_MPC_ERR_NO_DEVICE for DEVICE memory.  No output may overlap an input. */
+int tpc_mpc_solve_batch_compact_exact_forward(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t n, const void* v,
+                                              const void* delta_y, const void* delta_phi,
+                                              const void* params_rows /* optional [10], ld n */,
+                                              const void* sequence /* [H*2], ld n */,
+                                              const int32_t* status /* optional [n] */,
+                                              const tpc_mpc_compact_tangents* t, void* tfront /* [K], ld n */,
+                                              void* trear /* [K], ld n */, void* tsequence /* optional [K*2H], ld n */,
+                                              uint32_t* flags_out, int mem, void* stream);
 
 /* Inputs and outputs of tpc_mpc_rollout_backward, SoA with the io's leading dimension ld:
  *   sequences[steps*H*I]  the recorded sequences, as tpc_mpc_rollout_record returns them (required)

@@ -7,7 +7,8 @@ shape.  Anything else is a ValueError here, before a pointer reaches the library
 
 How an array is matched against the call's n: "shape" is [rows, n] exactly ([n] without rows), "loose" (the forward-mode
 arrays) leaves the leading dimensions free -- rows * n elements, last dimension n -- and "length" (the compact entries'
-vectors) asks for n elements only.
+vectors) asks for n elements only; "elems" is an array that is not per instance (the shared parameters' tangent):
+`rows` elements in all, whatever n is.
 """
 from __future__ import annotations
 
@@ -47,6 +48,8 @@ def _fits(shape, size, rows, n, match):
         return shape == ((n,) if rows is None else (rows, n))
     if match == "length":
         return size == n
+    if match == "elems":
+        return size == rows
     return size == rows * n and len(shape) >= 1 and shape[-1] == n
 
 
@@ -81,7 +84,7 @@ class Arrays:
             self.stream = None
 
     def _want(self, rows, dtype, match):
-        shape = {"length": f"of {self.n} elements", "loose": f"[..., {self.n}] of {rows} x {self.n} elements"}.get(
+        shape = {"length": f"of {self.n} elements", "elems": f"of {rows} elements", "loose": f"[..., {self.n}] of {rows} x {self.n} elements"}.get(
             match, f"[{self.n}]" if rows is None else f"[{rows}, {self.n}]")
         return f"{np.dtype(dtype).name} {shape}"
 

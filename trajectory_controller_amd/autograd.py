@@ -12,9 +12,10 @@ tpc_mpc_polish_batch_general onto the verified optimum -- the cheap way) or a sm
 tensors; both functions are once-differentiable.  Instances whose data are non-finite or break dlib's requires clause
 get zero gradients.
 
-Forward mode (torch.autograd.forward_ad) works on all three functions: the jvp of mpc_general / mpc_compact is
-tpc_mpc_solve_batch_general_forward, that of mpc_rollout tpc_mpc_rollout_forward, one direction per dual level, at
-the same sequences the backward is taken at.  torch.func transforms are not supported.
+Forward mode (torch.autograd.forward_ad) works on all four functions: the jvp of mpc_general / mpc_compact is
+tpc_mpc_solve_batch_general_forward, that of mpc_rollout tpc_mpc_rollout_forward, that of mpc_compact_exact
+tpc_mpc_solve_batch_compact_exact_forward (shared or per-instance parameters, no general form), one direction per
+dual level, at the same sequences the backward is taken at.  torch.func transforms are not supported.
 """
 from __future__ import annotations
 
@@ -307,7 +308,25 @@ class _MpcCompactExact(torch.autograd.Function):
         ctx.like = [None if t is None else (t.device, t.dtype, t.shape)
                     for t in (weights, step_size, wheelbase, lower, upper)]
         ctx.save_for_backward(*ins, sequence, status)
+        ctx.save_for_forward(*ins, sequence, status)
         return front, rear
+
+    @staticmethod
+    def jvp(ctx, _solver, _over, _polish, tv, tdy, tdphi, *tparams):
+        v, delta_y, delta_phi, sequence, status = ctx.saved_tensors
+        tan = {k: t.contiguous() for k, t in zip(("v", "delta_y", "delta_phi"), (tv, tdy, tdphi)) if t is not None}
+        if any(t is not None for t in tparams):
+            # the given parameters' tangents, sliced into one row of the ten and moved to v's device
+            row = torch.zeros(1, 10, dtype=torch.float64)
+            for name, t in zip(_MpcCompactExact.PARAMS, tparams):
+                if t is not None:
+                    row[0, _MpcCompactExact.SLICES[name]] = t.detach().to(device="cpu", dtype=torch.float64)
+            tan["params"] = row.to(v.device)
+        if not tan:
+            return torch.zeros_like(v), torch.zeros_like(v)
+        tf, tr = ctx.solver.solve_batch_compact_exact_forward(v, delta_y, delta_phi, sequence, tan, status=status,
+                                                              want_flags=False, **ctx.over)
+        return tf[0], tr[0]
 
     @staticmethod
     @once_differentiable
@@ -360,7 +379,26 @@ class _MpcCompactExactRows(torch.autograd.Function):
         ctx.like = [None if t is None else (t.device, t.dtype, t.shape)
                     for t in (weights, step_size, wheelbase, lower, upper)]
         ctx.save_for_backward(*ins, rows, sequence, status)
+        ctx.save_for_forward(*ins, rows, sequence, status)
         return front, rear
+
+    @staticmethod
+    def jvp(ctx, _solver, _over, _polish, _defaults, tv, tdy, tdphi, *tparams):
+        v, delta_y, delta_phi, rows, sequence, status = ctx.saved_tensors
+        tan = {k: t.contiguous() for k, t in zip(("v", "delta_y", "delta_phi"), (tv, tdy, tdphi)) if t is not None}
+        if any(t is not None for t in tparams):
+            # the ten rows' tangent, by the forward's broadcasting: a shared parameter's next to a per-instance one's
+            trows = torch.zeros(1, 10, v.numel(), dtype=torch.float64, device=v.device)
+            for name, t, per in zip(_MpcCompactExact.PARAMS, tparams, ctx.per_instance):
+                if t is not None:
+                    src = t.detach().to(device=v.device, dtype=torch.float64)
+                    trows[0, _MpcCompactExact.SLICES[name]] = src if per else src.unsqueeze(-1)
+            tan["params_rows"] = trows
+        if not tan:
+            return torch.zeros_like(v), torch.zeros_like(v)
+        tf, tr = ctx.solver.solve_batch_compact_exact_forward(v, delta_y, delta_phi, sequence, tan, status=status,
+                                                              params_rows=rows, want_flags=False, **ctx.over)
+        return tf[0], tr[0]
 
     @staticmethod
     @once_differentiable
@@ -402,8 +440,10 @@ def mpc_compact_exact(solver, v, delta_y, delta_phi, weights=None, step_size=Non
     given parameter and call when they live on the GPU (keep them on the CPU to avoid it).  Gradients reach v,
     delta_y, delta_phi and every given parameter that requires grad (the batch sum, reduced on the device in a fixed
     order, sliced onto the parameter tensors); an instance left unverified (status -1, fallback="none" or a failed
-    fallback) or with non-finite data gets zero gradients and adds nothing to the parameters'.  Once-differentiable,
-    no forward mode.
+    fallback) or with non-finite data gets zero gradients and adds nothing to the parameters'.  Once-differentiable.
+    Forward mode (torch.autograd.forward_ad): one call of tpc_mpc_solve_batch_compact_exact_forward at the saved
+    sequence and status, tangents on v, delta_y, delta_phi and every given parameter, shared (one small host-to-device
+    copy of the ten tangents per call) or per-instance; the excluded instances' tangents are zero.
 
     Per-instance parameters: any of them may carry a trailing n -- `weights` [4, n], `step_size` [n], `wheelbase` [n],
     `lower` / `upper` [2, n], CUDA fp64 -- for weights scheduled on speed, logs with different wheelbases or cycle

@@ -13,6 +13,7 @@
 #include "mpc_rollout_newton.h"
 #include "mpc_newton_compact.h"
 #include "mpc_compact_grad.h"
+#include "mpc_compact_tangent.h"
 #include "mpc_tangent_model.h"
 
 #include <cmath>
@@ -2113,6 +2114,73 @@ int tpc_mpc_solve_batch_compact_exact_rows_backward(tpc_mpc_handle h, const tpc_
                                                     uint32_t* flags_out, int mem, void* stream) {
     return compact_exact_backward_impl(h, p, n, v, delta_y, delta_phi, true, params_rows, sequence, status, g,
                                        flags_out, mem, stream);
+}
+
+// The forward mode of the exact compact solve: one launch, one lane per (direction, instance), of the tangent sweep on
+// the model and the model's tangent built from v and the direction (mpc_compact_tangent.hip).  One entry for both
+// parameter modes, as tpc_mpc_solve_batch_compact_exact_from takes an optional params_rows; a one-launch entry like the
+// general forward pass (staged_run), the shared parameters' tangent a row of K * 10 elements.
+int tpc_mpc_solve_batch_compact_exact_forward(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t n, const void* v,
+                                              const void* delta_y, const void* delta_phi, const void* params_rows,
+                                              const void* sequence, const int32_t* status,
+                                              const tpc_mpc_compact_tangents* t, void* tfront, void* trear,
+                                              void* tsequence, uint32_t* flags_out, int mem, void* stream) {
+    return guarded(h, [&]() -> int {
+        int rc = check_common(h, p, true);
+        if (rc) return rc;
+        if (p->dtype != TPC_MPC_F64) return fp64_only(h, "tpc_mpc_solve_batch_compact_exact_forward");
+        const bool rows = params_rows != nullptr;
+        if (!rows) {
+            rc = check_compact_model(h, p);
+            if (rc) return rc;
+        }
+        rc = check_batch(h, n, mem);
+        if (rc) return rc;
+        if (!t) return fail(h, TPC_MPC_ERR_BAD_ARG, "null tangent struct");
+        if (t->directions < 1 || (int64_t)t->directions * n > 0x7fffffffll)
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "need directions >= 1 and directions * n < 2^31");
+        if (rows && t->tparams)
+            return fail(h, TPC_MPC_ERR_BAD_ARG, "tparams is the shared parameters' tangent: with params_rows give tparams_rows");
+        if (!rows && t->tparams_rows) return fail(h, TPC_MPC_ERR_BAD_ARG, "tparams_rows needs params_rows");
+        if (!tfront && !trear && !tsequence) return fail(h, TPC_MPC_ERR_BAD_ARG, "no output asked for");
+        if (h->host_only && mem == TPC_MPC_DEVICE)
+            return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): the forward pass takes HOST memory only");
+        if (n == 0) { if (flags_out) *flags_out = 0; return TPC_MPC_OK; }
+        if (!v || !delta_y || !delta_phi) return fail(h, TPC_MPC_ERR_BAD_ARG, "null batch pointer");
+        if (!sequence) return fail(h, TPC_MPC_ERR_BAD_ARG, "null sequence");
+        const int H = p->horizon, K = t->directions;
+        constexpr int kP = ctan::kParams;
+        const bool whole = tsequence != nullptr;
+        // the arrays in order: 11 inputs (params_rows, status -- int32 -- and every tangent may be null), then 3
+        // outputs; tparams is one row of K * kP elements, not one element per instance
+        const void* src[11] = {params_rows, v, delta_y, delta_phi, sequence, status, t->tv, t->tdelta_y, t->tdelta_phi,
+                               t->tparams, t->tparams_rows};
+        void* dst[3] = {tfront, trear, tsequence};
+        const int64_t comps[14] = {kP, 1, 1, 1, 2 * H, 1, K, K, K, 1, (int64_t)K * kP, K, K, (int64_t)K * 2 * H};
+        int width[14] = {0};
+        width[5] = 4;
+        int64_t elems[14] = {0};
+        elems[9] = (int64_t)K * kP;
+        StagedExtra x;
+        x.width = width;
+        x.elems = elems;
+        return staged_run(h, n, n, mem, stream, flags_out, compact_tangent_scratch_bytes(H, n, K, whole), src, dst, comps,
+                          [&](int64_t ld, const void* const* in, void* const* out, hipStream_t s, uint32_t* hf) {
+                              ctan::Args a;
+                              std::memset(&a, 0, sizeof(a));
+                              a.n = n; a.ld = ld; a.K = K;
+                              if (!rows) bind_compact_model(&a, p);
+                              a.params = (const double*)in[0];
+                              a.v = (const double*)in[1]; a.dy = (const double*)in[2]; a.dphi = (const double*)in[3];
+                              a.seq = (const double*)in[4]; a.status = (const int32_t*)in[5];
+                              a.tv = (const double*)in[6]; a.tdy = (const double*)in[7]; a.tdphi = (const double*)in[8];
+                              a.tparams = (const double*)in[9]; a.tparams_rows = (const double*)in[10];
+                              a.tfront = (double*)out[0]; a.trear = (double*)out[1]; a.tseq = (double*)out[2];
+                              if (hf) { *hf = compact_tangent_host(H, a); return hipSuccess; }
+                              return compact_tangent(H, a, h->grad_ws, h->ws_words + 1, s);
+                          },
+                          x);
+    });
 }
 
 // what the three plant entries check of a tpc_mpc_plant (after check_common and check_general_io)

@@ -301,6 +301,57 @@ class MpcSolver:
                   ar.read(sequence, 2 * H), ar.read(status, dtype=_I32), C.byref(g), want_flags=want_flags)
         return out
 
+    COMPACT_TANGENT_NAMES = ("v", "delta_y", "delta_phi", "params", "params_rows")
+
+    def solve_batch_compact_exact_forward(self, v, delta_y, delta_phi, sequence, tangents, status=None,
+                                          params_rows=None, want_sequence: bool = False, want_flags: bool = True,
+                                          **over):
+        """Forward mode of solve_batch_compact_exact (tpc_mpc_solve_batch_compact_exact_forward), fp64 only: the
+        directional derivatives of (front, rear) -- with want_sequence of the whole sequence -- along K directions,
+        taken at `sequence` [2H, n] as want_sequence of the forward returns it.  K directions in one call are K columns
+        of the per-instance Jacobian: what Gauss-Newton and Levenberg-Marquardt fits of a few parameters need.
+
+        Arrays as in solve_batch_compact_exact_backward (numpy: HOST memory, CUDA tensors: DEVICE memory on the
+        current stream); `status` (int32 [n], optional) excludes the instances with a negative status.  `tangents`
+        maps "v", "delta_y", "delta_phi" to arrays [K, n] ([n]: K = 1), and the parameters' tangent, in the order of
+        COMPACT_PARAM_NAMES, either "params" [K, 10] ([10]: K = 1; the ten shared parameters, params_rows=None only;
+        a CUDA tensor in a DEVICE call) or "params_rows" [K, 10, n] ([10, n]: K = 1; with params_rows only).  A missing
+        name is a zero tangent.  Returns (tfront [K, n], trear [K, n]), and tsequence [K, 2H, n] with want_sequence;
+        a flagged (direction, instance) pair and an excluded instance get zeros (last_flags).  want_flags=False leaves
+        last_flags at 0 and keeps a DEVICE call asynchronous."""
+        p = self._params(**over)
+        H = p.horizon
+        unknown = set(tangents) - set(self.COMPACT_TANGENT_NAMES)
+        if unknown:
+            raise ValueError(f"unknown tangent names {sorted(unknown)}")
+        tangents = {k: t for k, t in tangents.items() if t is not None}
+        if not tangents:
+            raise ValueError("tangents is empty: give at least one direction array")
+        if "params" in tangents and params_rows is not None:
+            raise ValueError('"params" is the shared parameters\' tangent: with params_rows give "params_rows"')
+        if "params_rows" in tangents and params_rows is None:
+            raise ValueError('"params_rows" needs params_rows')
+        K = None
+        for name, t in tangents.items():
+            one = 3 if name == "params_rows" else 2   # dimensions of a K-direction array
+            k = 1 if t.ndim == one - 1 else t.shape[0] if t.ndim == one else None
+            if k is None or (K is not None and k != K):
+                raise ValueError(f"tangent {name!r}: expected a leading K (or none for K = 1) with one K for all")
+            K = k
+        ar = Arrays(v)
+        NP = len(COMPACT_PARAM_NAMES)
+        at = {name: ar.read(t, K * NP, None, "elems") if name == "params"
+              else ar.read(t, K * NP if name == "params_rows" else K, None, "loose") for name, t in tangents.items()}
+        tan = capi.CompactTangents(directions=K, reserved=0, tv=at.get("v"), tdelta_y=at.get("delta_y"),
+                                   tdelta_phi=at.get("delta_phi"), tparams=at.get("params"),
+                                   tparams_rows=at.get("params_rows"))
+        tfront, trear = ar.new(K), ar.new(K)
+        tseq = ar.new(K, 2 * H) if want_sequence else None
+        self._run(self._lib.tpc_mpc_solve_batch_compact_exact_forward, p, ar, ar.n, ar.read(v), ar.read(delta_y),
+                  ar.read(delta_phi), ar.read(params_rows, NP), ar.read(sequence, 2 * H), ar.read(status, dtype=_I32),
+                  C.byref(tan), ar.addr(tfront), ar.addr(trear), ar.addr(tseq), want_flags=want_flags)
+        return (tfront, trear, tseq) if want_sequence else (tfront, trear)
+
     def solve_batch_compact_mixed(self, horizons, v, delta_y, delta_phi, want_iters: bool = False, **over):
         """Mixed-horizon batch (BASELINE config 5): instance k is solved with horizon horizons[k]
         (tpc_mpc_solve_batch_compact_mixed: binned by horizon on the device, one launch sequence per
