@@ -118,6 +118,33 @@ def test_rollout8_bit_exact(oracle, I, H):
         assert bits_equal(c, g["controls"][k]) and bits_equal(s, g["states"][k]), k
 
 
+@pytest.mark.parametrize("I", [1, 2])
+@pytest.mark.parametrize("H", [4, 5, 10, 20, 30, 40])
+def test_general_full_models_bit_exact(oracle, I, H):
+    """Full 2x2 models (tests/model/full_models.py, make_golden_full.py): a10 != 0, a00 != a11, b00 != 0, complex,
+    unstable, negative-determinant and singular A -- the restatement pinned to real dlib off [1 a; 0 1]."""
+    g = load_golden(f"general_full_I{I}_H{H}.npz")
+    assert np.all(g["A"] != 0.0) and np.all(g["B"] != 0.0)
+    u0, controls, it = oracle.solve_general(I, H, g["A"], g["B"], g["C"], g["Q"], g["R"], g["lo"],
+                                            g["hi"], g["x0"], g["targets"], nthreads=4)
+    assert bits_equal(u0, g["u0"])
+    assert bits_equal(controls[:, 0, :], u0)
+
+
+@pytest.mark.parametrize("I", [1, 2])
+@pytest.mark.parametrize("H", [4, 5, 10, 20, 30, 40])
+def test_rollout_full_models_bit_exact(oracle, I, H):
+    """12 controllers x 5 warm-started steps on full models, from real dlib (make_golden_full.py): controls and the
+    states of x <- A x + B u + C with every entry of A live."""
+    g = load_golden(f"rollout_full_I{I}_H{H}.npz")
+    steps = int(g["steps"])
+    assert g["A"].shape[0] == 12 and np.all(g["A"] != 0.0) and np.all(g["B"] != 0.0)
+    for k in range(g["A"].shape[0]):
+        c, s, _ = oracle.rollout(I, H, steps, g["A"][k], g["B"][k], g["C"][k], g["Q"][k], g["R"][k],
+                                 g["lo"][k], g["hi"][k], g["x0"][k], g["targets"][k], g["new_last_targets"][k])
+        assert bits_equal(c, g["controls"][k]) and bits_equal(s, g["states"][k]), k
+
+
 def test_float_oracle_tracks_the_pinned_one(oracle, oracle32):
     """The float-typed build of the same source is deterministic and stays close to the fp64 result
     (it is the checker of the fp32 kernels; dlib has no fp32 form to pin it to)."""
