@@ -85,8 +85,14 @@ typedef enum tpc_mpc_memory { TPC_MPC_HOST = 0, TPC_MPC_DEVICE = 1 } tpc_mpc_mem
  *          value), fused multiply-adds, and the linear term folded into the backward recurrence (nothing
  *          of the model in memory): about half of LANE's instructions per iteration.  Same iteration and
  *          the same decisions as dlib on quantities that differ by rounding: max |du| vs dlib ~2e-13 at
- *          N = 20, ~1e-12 at N = 40, iteration counts identical on the BASELINE workloads (they can differ
- *          only where dlib's largest gradient component comes within rounding of eps).  Compact form
+ *          N = 20, ~1e-12 at N = 40, iteration counts identical on the BASELINE workloads.  They can differ
+ *          in two cases only: where dlib's largest gradient component comes within rounding of eps, and where
+ *          the coordinate-descent phase meets an arg-max that is a TIE in exact arithmetic -- dlib's strict '>'
+ *          and this family's rounding then pick different components, both valid descent steps, and the two
+ *          solves end at different points that both pass dlib's stop test.  Known: weight_phi <= 2^-30 weight_y
+ *          (the heading is then costed through the position alone; N = 5 with step_size * v in -0.31 .. -0.21:
+ *          2 % of a batch, |du| up to 1.3e-3).  Measured for WAVE too (7e-6); GROUP shares
+ *          the arithmetic.  Compact form
  *          (solve_batch_compact, _mixed, _sharded) with hi > lo finite, specialised horizons.  General
  *          form (solve_batch_general without controls_inout / v_inout, follow_batch) at N = 4, 5, 10, 20:
  *          the same arithmetic in dlib's own coordinates (per-instance bounds may be pinned or infinite)
@@ -116,7 +122,13 @@ typedef enum tpc_mpc_memory { TPC_MPC_HOST = 0, TPC_MPC_DEVICE = 1 } tpc_mpc_mem
  *          per instance, then LANE_FMA (csrc/auto_table.h, generated by scripts/measure_crossover.py on a 256-CU
  *          part and scaled by the CU count: at N = 20 in fp64 WAVE below 7 094 instances, GROUP up to 160 530,
  *          LANE_FMA beyond -- in fp32 GROUP up to 321 060; at N = 30 and 40 GROUP is never overtaken, in either dtype and
- *          either form); LANE where none of them takes the request.  Guarantee (fp64, the specialised horizons,
+ *          either form); LANE where none of them takes the request, and, in fp64, for every compact request with
+ *          weight_phi <= 2^-30 weight_y and smo_iters > 0, whatever its size (solve_one included: one LANE launch
+ *          instead of the resident wavefront) -- dlib's coordinate-descent arg-max can tie there (see LANE_FMA
+ *          above), which no tolerance family follows to within 1e-6.  NOT covered: the general form
+ *          (solve_batch_general, follow_batch_horizon, the rollouts) keeps its family when an instance's Q is
+ *          (q0, ~0): the same tie can occur there and has not been measured or routed; ask for LANE.
+ *          Guarantee (fp64, the specialised horizons,
  *          cold starts -- every compact entry point and the general form without controls_inout / v_inout): an
  *          instance that ends on max_iter has not converged, and over thousands of iterations of an ill-conditioned
  *          problem the tolerance families' rounding differences grow (2.3e-5 seen under adversarial parameters), so
@@ -185,7 +197,9 @@ int tpc_mpc_default_params(tpc_mpc_params* p, int horizon);
  * the reference's N = 4 a core needs ~3 us where the GPU round trip needs ~10.  The one other call it serves is
  * tpc_mpc_solve_batch_general_backward with TPC_MPC_HOST memory, also on the calling thread.  Every other batch entry
  * point returns TPC_MPC_ERR_NO_DEVICE on such a handle.  AUTO's re-solve of capped instances needs the GPU: a host-only handle
- * returns the tolerance answer and raises TPC_MPC_FLAG_MAX_ITER. */
+ * returns the tolerance answer and raises TPC_MPC_FLAG_MAX_ITER.  Likewise it has no bit-exact kernels for a request
+ * with weight_phi <= 2^-30 weight_y: its answer there is the LANE_FMA family's, which can leave dlib's path at a tied arg-max (see
+ * LANE_FMA above) and still passes dlib's stop test. */
 #define TPC_MPC_DEVICE_NONE (-1)
 int tpc_mpc_create(int device, tpc_mpc_handle* out);
 int tpc_mpc_destroy(tpc_mpc_handle h);

@@ -15,7 +15,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 MODEL_SO = os.path.join(_HERE, "libub_model.so")
 _ROOT = os.path.dirname(os.path.dirname(_HERE))
 _SRCS = [os.path.join(_HERE, "ub_model.cpp"),
-         os.path.join(_ROOT, "trajectory_controller_amd", "csrc", "mpc_ub_model.h")]
+         os.path.join(_ROOT, "trajectory_controller_amd", "csrc", "mpc_ub_model.h"),
+         os.path.join(_ROOT, "trajectory_controller_amd", "csrc", "mpc_ub_host.h")]
 
 ALPHA_MAX = 22.0 * np.pi / 180.0
 DEFAULT_WEIGHTS = (20.0, 7.0, 0.0005, 10.0)
@@ -42,6 +43,10 @@ class UbModel:
         self.fn.argtypes = [C.c_int, C.c_long, C.c_int, rp, rp, rp, rp, C.c_double, C.c_double, rp, rp,
                             C.c_double, C.c_ulong, C.c_ulong, C.c_int, rp, rp, C.POINTER(C.c_int),
                             C.POINTER(C.c_uint)]
+        if dtype == "f64":
+            self.fn_seq = self.lib.ub_model_solve_compact_seq_f64
+            self.fn_seq.restype = C.c_int
+            self.fn_seq.argtypes = self.fn.argtypes + [rp]
         self.gen = getattr(self.lib, f"ub_model_solve_general_{dtype}")
         self.gen.restype = C.c_int
         self.gen.argtypes = [C.c_int, C.c_int, C.c_long, C.c_int, rp, rp, rp, rp, rp, rp, rp, rp, rp,
@@ -49,9 +54,10 @@ class UbModel:
 
     def solve_compact(self, H, v, dy, dphi, weights=DEFAULT_WEIGHTS, T=0.1, l=0.21,
                       lo=(-ALPHA_MAX, -ALPHA_MAX), hi=(ALPHA_MAX, ALPHA_MAX), eps=0.01, max_iter=10000,
-                      smo_iters=50, nthreads=1, fast_stop=True):
+                      smo_iters=50, nthreads=1, fast_stop=True, want_sequence=False):
         """fast_stop: True / False = a screened build (fp32: which of the two, decided batch-wide by the second screen like the
-        kernels do) / the exact stop-test build; None = decided by the kernels' own screens."""
+        kernels do) / the exact stop-test build; None = decided by the kernels' own screens.
+        want_sequence (fp64): the whole solved sequence [n, H, 2] comes fifth -- the kernels publish its first step only."""
         a = lambda z: np.ascontiguousarray(z, dtype=self.np)
         p = lambda z: z.ctypes.data_as(self._rp)
         v, dy, dphi, w, lo, hi = a(v), a(dy), a(dphi), a(weights), a(lo), a(hi)
@@ -59,12 +65,14 @@ class UbModel:
         front, rear = np.empty(n, dtype=self.np), np.empty(n, dtype=self.np)
         iters = np.empty(n, dtype=np.int32)
         flags = C.c_uint(0)
-        rc = self.fn(H, n, nthreads, p(v), p(dy), p(dphi), p(w), T, l, p(lo), p(hi), eps, max_iter, smo_iters,
-                     -1 if fast_stop is None else int(fast_stop), p(front), p(rear), iters.ctypes.data_as(C.POINTER(C.c_int)),
-                     C.byref(flags))
+        seq = np.empty((n, H, 2), dtype=self.np) if want_sequence else None
+        rc = (self.fn_seq if want_sequence else self.fn)(
+            H, n, nthreads, p(v), p(dy), p(dphi), p(w), T, l, p(lo), p(hi), eps, max_iter, smo_iters,
+            -1 if fast_stop is None else int(fast_stop), p(front), p(rear), iters.ctypes.data_as(C.POINTER(C.c_int)),
+            C.byref(flags), *((p(seq),) if want_sequence else ()))
         if rc != 0:
             raise ValueError(f"ub model: unsupported H={H}")
-        return front, rear, iters, flags.value
+        return (front, rear, iters, flags.value) + ((seq,) if want_sequence else ())
 
     def solve_general(self, I, H, A, B, Cc, Q, R, lo, hi, x0, targets, eps=0.01, max_iter=10000, smo_iters=50,
                       nthreads=1, fast_stop=None):

@@ -42,9 +42,9 @@ int screen_dispatch(int H, T v, T ty, T tphi, const T* q, const T* r, double ste
 
 template <typename T, bool EQB>
 int dispatch(int H, T v, T ty, T tphi, const T* q, const T* r, double step, double wb, const T* lo, const T* hi,
-             double eps, unsigned long mi, unsigned long smo, int fast, T* fo, T* re, int* it, unsigned* fl) {
+             double eps, unsigned long mi, unsigned long smo, int fast, T* fo, T* re, int* it, unsigned* fl, T* seq) {
     switch (H) {
-#define X(h) case h: host_solve_compact<T, h, EQB>(v, ty, tphi, q, r, step, wb, lo, hi, eps, mi, smo, fast, fo, re, it, fl); return 0;
+#define X(h) case h: host_solve_compact<T, h, EQB>(v, ty, tphi, q, r, step, wb, lo, hi, eps, mi, smo, fast, fo, re, it, fl, seq); return 0;
         X(4) X(5) X(10) X(20) X(30) X(40)
 #undef X
     }
@@ -54,7 +54,7 @@ int dispatch(int H, T v, T ty, T tphi, const T* q, const T* r, double step, doub
 template <typename T>
 int batch(int H, long n, int nthreads, const T* v, const T* dy, const T* dphi, const T* w4, double step,
           double wb, const T* lo, const T* hi, double eps, unsigned long mi, unsigned long smo, int fast,
-          T* front, T* rear, int* iters, unsigned* flags_out) {
+          T* front, T* rear, int* iters, unsigned* flags_out, T* seq = nullptr /* [n][2 H] */) {
     const bool eqb = lo[0] == lo[1] && hi[0] == hi[1];
     const T q[2] = {w4[0], w4[1]}, r[2] = {w4[2], w4[3]};
     // The kernels' batch-wide choice (ub_pg_kernel's MODE): one instance outside the first screen sends the batch to the
@@ -80,9 +80,11 @@ int batch(int H, long n, int nthreads, const T* v, const T* dy, const T* dphi, c
             if (k0 >= n) break;
             for (long k = k0; k < n && k < k0 + 64; ++k) {
                 const int e = eqb ? dispatch<T, true>(H, v[k], dy[k], dphi[k], q, r, step, wb, lo, hi, eps, mi, smo,
-                                                       fast, front + k, rear + k, iters ? iters + k : nullptr, &f)
+                                                       fast, front + k, rear + k, iters ? iters + k : nullptr, &f,
+                                                       seq ? seq + 2 * H * k : nullptr)
                                   : dispatch<T, false>(H, v[k], dy[k], dphi[k], q, r, step, wb, lo, hi, eps, mi, smo,
-                                                        fast, front + k, rear + k, iters ? iters + k : nullptr, &f);
+                                                        fast, front + k, rear + k, iters ? iters + k : nullptr, &f,
+                                                        seq ? seq + 2 * H * k : nullptr);
                 if (e) rc = e;
             }
         }
@@ -293,6 +295,14 @@ int ub_model_solve_compact_f64(int H, long n, int nthreads, const double* v, con
                                double* front, double* rear, int* iters, unsigned* flags) {
     return batch<double>(H, n, nthreads, v, dy, dphi, weights4, T, l, lo2, hi2, eps, max_iter, smo_iters, fast_stop,
                          front, rear, iters, flags);
+}
+// the same with the whole solved sequence, seq [n][2 H] (step-major, front then rear)
+int ub_model_solve_compact_seq_f64(int H, long n, int nthreads, const double* v, const double* dy, const double* dphi,
+                                   const double* weights4, double T, double l, const double* lo2, const double* hi2,
+                                   double eps, unsigned long max_iter, unsigned long smo_iters, int fast_stop,
+                                   double* front, double* rear, int* iters, unsigned* flags, double* seq) {
+    return batch<double>(H, n, nthreads, v, dy, dphi, weights4, T, l, lo2, hi2, eps, max_iter, smo_iters, fast_stop,
+                         front, rear, iters, flags, seq);
 }
 int ub_model_solve_compact_f32(int H, long n, int nthreads, const float* v, const float* dy, const float* dphi,
                                const float* weights4, double T, double l, const float* lo2, const float* hi2,

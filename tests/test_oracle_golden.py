@@ -145,6 +145,23 @@ def test_rollout_full_models_bit_exact(oracle, I, H):
         assert bits_equal(c, g["controls"][k]) and bits_equal(s, g["states"][k]), k
 
 
+@pytest.mark.parametrize("H", [4, 5, 10, 20, 30, 40])
+def test_compact_vehicles_bit_exact(oracle, H):
+    """The compact form off the default vehicle (tests/model/vehicles.py, make_golden_vehicles.py): negative speeds,
+    a negative wheelbase and step size, weight_phi = 0, exchanged steering weights, unequal bounds and a box without
+    u = 0 -- the restatement pinned to real dlib where a, c and the bound offsets change sign."""
+    from tests.model import vehicles as vh
+    g = load_golden(f"compact_vehicles_H{H}.npz")
+    v, dy, dphi = vh.inputs(H, len(g["v"]))
+    assert bits_equal(v, g["v"]) and bits_equal(dy, g["dy"]) and bits_equal(dphi, g["dphi"])
+    assert (v < 0).sum() >= 8 and (v > 0).sum() >= 8 and v[3] == 0
+    assert sorted(k[6:] for k in g if k.startswith("front_")) == sorted(vh.names_at(H))
+    for name in vh.names_at(H):
+        f, r, it = oracle.solve_compact(H, v, dy, dphi, nthreads=4, **vh.oracle_kw(name))
+        assert bits_equal(f, g[f"front_{name}"]) and bits_equal(r, g[f"rear_{name}"]), name
+        assert np.abs(f).max() > 0 or np.abs(r).max() > 0, name
+
+
 def test_float_oracle_tracks_the_pinned_one(oracle, oracle32):
     """The float-typed build of the same source is deterministic and stays close to the fp64 result
     (it is the checker of the fp32 kernels; dlib has no fp32 form to pin it to)."""

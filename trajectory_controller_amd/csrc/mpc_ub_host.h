@@ -18,10 +18,14 @@ namespace ub {
 // (fp32; in fp64 the same as 2), 2 = read off the projected step (what the kernels run where ub::fast_stop_ok -- and, in
 // fp32, ub::moved_stop_ok -- hold), -1 = decided here by those screens on this instance (the kernels decide per batch).
 // *flags is OR-ed with TPC_MPC_FLAG_NONFINITE (1) / TPC_MPC_FLAG_MAX_ITER (2).
+// seq: CHECKER PLUMBING, not a product feature -- no product caller passes it (tpc_mpc_host.cpp leaves the default),
+// and with seq == nullptr no statement it guards runs.  Optional, [2 H], dlib's order (step-major, front then rear):
+// the whole solved sequence, so that tests/model/ can evaluate dlib's stop test on the answer itself; the kernels keep
+// it in registers and publish its first step only.
 template <typename T, int H, bool EQB>
 void host_solve_compact(T v, T ty, T tphi, const T* q, const T* r, double step, double wheelbase, const T* lo,
                const T* hi, double eps_d, unsigned long max_iter, unsigned long smo_iters, int fast_stop_in,
-               T* front, T* rear, int* iters, unsigned* flags) {
+               T* front, T* rear, int* iters, unsigned* flags, T* seq = nullptr) {
     const T eps = (T)eps_d;
     Unit<T, EQB> m;
     m.set_uniform((T)1, q, r, lo, hi);
@@ -88,6 +92,7 @@ void host_solve_compact(T v, T ty, T tphi, const T* q, const T* r, double step, 
             m.fwd_init(Z, Y);
             for (int i = 0; i < H; ++i) { m.fwd(Z, Y, x[2 * i], x[2 * i + 1]); wz[i] = Z; wy[i] = Y; }
             const T p0 = x[0], p1 = x[1];
+            if (seq) for (int qv = 0; qv < 2 * H; ++qv) dd[qv] = x[qv];   // (dd is free in this phase)
             T n0, n1, acc = (T)0;
             m.bwd_last(n0, n1, Z, Y);
             for (int i = H - 1; i >= 0; --i) {
@@ -116,13 +121,18 @@ void host_solve_compact(T v, T ty, T tphi, const T* q, const T* r, double step, 
                 }
                 if (RV && i > 0) m.rev(Z, Y, xo0, xo1);   // step i-1 from step i and the controls it was made from
             }
-            if (acc < geps) { x[0] = p0; x[1] = p1; break; }   // stop: the controls before this update
+            if (acc < geps) {   // stop: the controls before this update
+                x[0] = p0; x[1] = p1;
+                if (seq) for (int qv = 0; qv < 2 * H; ++qv) x[qv] = dd[qv];
+                break;
+            }
             ++iter;
             if (iter >= max_iter) { f |= 2u; break; }
         }
     }
     if (nonfinite) { *front = (T)0; *rear = (T)0; }
     else { *front = m.control(0, x[0]); *rear = m.control(1, x[1]); }
+    if (seq) for (int qv = 0; qv < 2 * H; ++qv) seq[qv] = nonfinite ? (T)0 : m.control(qv & 1, x[qv]);
     if (iters) *iters = (int)iter;
     *flags |= f;
 }

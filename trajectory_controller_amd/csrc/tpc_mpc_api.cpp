@@ -243,6 +243,27 @@ bool fma_usable(const tpc_mpc_params* p) {
     return true;
 }
 
+// A compact request whose coordinate-descent phase can meet an arg-max (mpc.h:289-309) that is a TIE in exact arithmetic.
+// With weight_phi == 0 the heading enters the cost through the position alone, and dlib's coordinate step divides by
+// Q_diag, which leaves R out (mpc.h:324): after a step on u[0](0) from the cold start the Q part of that component is
+// zero exactly (c N1[0] = 0), the predicted error is still linear in the step index (every later control is 0:
+// E[k] = E0 + k d), and for N = 3m - 1 the partial sum N0[m] = q0 sum_{k >= m} E[k] is a multiple of N1[0] and vanishes
+// with it -- df[m-1](0), df[m](0) and -df[m](1) are then one real number, the extremum of the first input's
+// components and, for part of the speed range, of the whole gradient; computed, they differ in their last bits
+// only (N = 5: m = 2, traced in NOTEBOOK.md).  dlib's strict '>' takes whichever its own rounding left
+// largest; another operation order takes another one, both valid descent steps, and the two paths part for good
+// (N = 5, reversing at |T v| ~ 0.21 .. 0.31: 2 % of a batch, |du| up to 1.3e-3; other ties of the same origin at
+// N = 6).  Not a rounding-of-eps event, so the tolerance families' statement does not cover it: AUTO sends such
+// requests to the bit-exact kernels.
+// How small is "zero".  A weight_phi > 0 moves the three components apart by about weight_phi / weight_y of their
+// size (the heading's terms against the position's, states and model entries being O(0.1 .. 1)); the families'
+// rounding moves them by ~1e-14 of it.  Measured on the batch of tests/test_vehicles_host.py (3000 reversing instances,
+// weight_y = 20): weight_phi / weight_y = 5e-22 parts 82 solves like 0 does, 1e-16: 65, 1e-14: 1, 1e-12 and every
+// larger ratio up to 1e-3: none.  The threshold is 2^-30 (9e-10): three decades above the last ratio that showed.
+bool cd_tie_prone(const tpc_mpc_params* p) {
+    return p->weight_phi <= p->weight_y * 0x1p-30 && p->smo_iters > 0 && p->max_iter > 0;
+}
+
 // General form, GROUP (mpc_groupg_inst.hip): N = 10, 20, 30, 40; fp32 only where the general-form LANE_FMA unit stands
 // in front of it (cold starts at N <= 20), fp64 also with the controller state in or out and at N = 30, 40.
 bool group_general_usable(int dtype, int H, const void* controls, const void* v) {
@@ -505,10 +526,17 @@ template <class Args> void bind_compact_model(Args* a, const tpc_mpc_params* p) 
 
 namespace tpc {
 
+// The family a compact request asks for.  AUTO's guarantee (include/tpc_mpc.h) covers fp64: there a request whose
+// coordinate-descent phase can tie (cd_tie_prone) is LANE's, whatever its size -- the one-instance entry included.
+int compact_algo(const tpc_mpc_params* p) {
+    return p->algo == TPC_MPC_ALGO_AUTO && p->dtype == TPC_MPC_F64 && cd_tie_prone(p) ? TPC_MPC_ALGO_LANE : p->algo;
+}
+
 // A bin of a mixed-horizon batch that the GROUP family takes (tpc_mpc_mixed.hip runs those side by side, each on its
 // share of the SIMDs): AUTO or GROUP asked for, bounds the unit box can take, a horizon with group kernels.
 bool group_applicable(const tpc_mpc_context* h, const tpc_mpc_params* p, int H) {
-    return (p->algo == TPC_MPC_ALGO_AUTO || p->algo == TPC_MPC_ALGO_GROUP) && fma_usable(p) && group_lanes(h, H) > 0;
+    const int algo = compact_algo(p);
+    return (algo == TPC_MPC_ALGO_AUTO || algo == TPC_MPC_ALGO_GROUP) && fma_usable(p) && group_lanes(h, H) > 0;
 }
 
 // `host_ok`: the entry point also serves a host-only handle (tpc_mpc_solve_one); every other one needs the device
@@ -757,7 +785,7 @@ static double presolve_lambda(const tpc_mpc_params* p) { return presolve_lambda_
 int presolve_begin(tpc_mpc_context* h, const tpc_mpc_params* p, int64_t n, const void* v, const void* dy, const void* dphi,
                    hipStream_t s, Presolve* ps) {
     *ps = Presolve();
-    const int algo = pick_algo(h, p->algo, 2, p->horizon, n, p->dtype, fma_usable(p));
+    const int algo = pick_algo(h, compact_algo(p), 2, p->horizon, n, p->dtype, fma_usable(p));
     if (algo != TPC_MPC_ALGO_GROUP || !wants_cap_resolve(p, algo) || !h->collect_flags) return TPC_MPC_OK;
     const double lf = presolve_lambda(p);
     if (!(lf > 0.0) || h->pre_busy) return TPC_MPC_OK;
@@ -807,7 +835,7 @@ int presolve_finish(tpc_mpc_context* h, const tpc_mpc_params* p, int64_t n, cons
         HIP_TRY(h, hipEventRecord(h->pre_done, h->pre_stream));
         HIP_TRY(h, hipStreamWaitEvent(s, h->pre_done, 0));
     }
-    const int algo = pick_algo(h, p->algo, 2, p->horizon, n, p->dtype, fma_usable(p));
+    const int algo = pick_algo(h, compact_algo(p), 2, p->horizon, n, p->dtype, fma_usable(p));
     if (algo < 0 || !wants_cap_resolve(p, algo) || !h->collect_flags) return TPC_MPC_OK;
     int32_t* sel = iters ? iters : ps->select;
     if (ps->lambda_from > 0.0) {
@@ -842,7 +870,7 @@ static bool queue_key_table_applies(const tpc_mpc_params* p, int algo) {
 // immediately unless ps->deferred
 int compact_launch_ps(tpc_mpc_context* h, const tpc_mpc_params* p, int64_t n, const void* v, const void* dy,
                       const void* dphi, void* front, void* rear, int32_t* iters, hipStream_t s, Presolve* ps) {
-    const int algo = pick_algo(h, p->algo, 2, p->horizon, n, p->dtype, fma_usable(p));
+    const int algo = pick_algo(h, compact_algo(p), 2, p->horizon, n, p->dtype, fma_usable(p));
     if (algo < 0) return fail(h, TPC_MPC_ERR_BAD_HORIZON, "the WAVE kernel exists for the specialised horizons with inputs*horizon <= 64 only; use LANE or AUTO");
     CompactArgs a;
     compact_args(h, p, n, v, dy, dphi, front, rear, iters, &a);
@@ -1206,7 +1234,9 @@ int tpc_mpc_solve_one(tpc_mpc_handle h, const tpc_mpc_params* p, double v, doubl
         if (rc) return rc;
         // the host path (csrc/tpc_mpc_host.cpp): a host-only handle always, a GPU handle up to the horizon its option names
         if (h->host_only || p->horizon <= h->opt_host_horizon) {
-            const bool takes = p->dtype == TPC_MPC_F64 && (p->algo == TPC_MPC_ALGO_AUTO || p->algo == TPC_MPC_ALGO_LANE_FMA) &&
+            // (a host-only handle has no bit-exact kernels to send a tie-prone AUTO request to: include/tpc_mpc.h says so)
+            const int want = h->host_only ? p->algo : compact_algo(p);
+            const bool takes = p->dtype == TPC_MPC_F64 && (want == TPC_MPC_ALGO_AUTO || want == TPC_MPC_ALGO_LANE_FMA) &&
                                fma_usable(p) && horizon_specialised(p->horizon) && host_path_usable();
             if (takes) {
                 int iters = 0;

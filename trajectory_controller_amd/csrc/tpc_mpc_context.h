@@ -222,6 +222,8 @@ int compact_launch_ps(tpc_mpc_context* h, const tpc_mpc_params* p, int64_t n, co
 int presolve_finish(tpc_mpc_context* h, const tpc_mpc_params* p, int64_t n, const void* v, const void* dy, const void* dphi,
                     void* front, void* rear, int32_t* iters, hipStream_t s, Presolve* ps);
 bool group_applicable(const tpc_mpc_context* h, const tpc_mpc_params* p, int H);
+// p->algo, or LANE where AUTO's guarantee needs the bit-exact kernels for this parameter set (tpc_mpc_api.cpp)
+int compact_algo(const tpc_mpc_params* p);
 // scratch of the LANE family for (H, dtype, n), without launching (grows the handle's workspace)
 int reserve_lane_workspace(tpc_mpc_context* h, int H, int dtype, int64_t n);
 

@@ -343,7 +343,7 @@ int one_shot_solve(tpc_mpc_context* h, const tpc_mpc_params* p, double v, double
     }
     OneShot* o = h->one;
     const int H = p->horizon;   // resident kernels exist for the specialised horizons the WAVE layout can take
-    const bool resident_ok = !o->disabled && p->dtype == TPC_MPC_F64 && p->algo != TPC_MPC_ALGO_LANE &&
+    const bool resident_ok = !o->disabled && p->dtype == TPC_MPC_F64 && compact_algo(p) != TPC_MPC_ALGO_LANE &&
                              (H == 4 || H == 5 || H == 10 || H == 20 || H == 30 || H == 40);
     if (!resident_ok) return launch_path(h, p, v, dy, dphi, front, rear);
     if (!o->stream) {
