@@ -723,6 +723,62 @@ int tpc_mpc_solve_batch_compact_exact_forward(tpc_mpc_handle h, const tpc_mpc_pa
                                               void* trear /* [K], ld n */, void* tsequence /* optional [K*2H], ld n */,
                                               uint32_t* flags_out, int mem, void* stream);
 
+/* No reference counterpart.  The compact closed loop: mpcControllerTobi's controller rolled forward `steps` steps on its
+ * own model, every step answered with the VERIFIED OPTIMUM -- tpc_mpc_rollout_newton on the model that
+ * tpc_mpc_solve_batch_compact_exact builds, without the general form: three doubles (+ x0) in per instance, two (+ the
+ * optional rows) out per step, the model built in registers.
+ * Instance k has tpc_mpc_solve_batch_compact_exact's model, with T = p->step_size, l = p->wheelbase, Tv = T * v:
+ *     A = [1, Tv; 0, 1]   B = [0, Tv; Tv/l, -Tv/l]   C = 0   Q, R, lower, upper from p
+ *     every one of the H targets (delta_y, delta_phi), at every step -- what tpc_mpc_rollout's target shift leaves when
+ *     no new_last_targets is given
+ *     x_0 = column k of x0 ([2] rows, leading dimension n), or zeros when x0 is NULL: the reference's case
+ * and the loop is tpc_mpc_rollout_newton's on that model, started from no carried controls.
+ *   Phase 1, every instance, ONE launch (csrc/mpc_compact_loop.hip; at horizons 4 and 5 the whole loop stays in
+ *   registers and no workspace memory is touched).  For k = 0 .. steps-1:
+ *     U   <- dlib's shift of the previous step's sequence (mpc.h:231-232: t <- t + 1, the last step kept); zeros at step 0
+ *     U   <- clamp(U, lower, upper), then the rounds of tpc_mpc_polish_batch_general at x_k with q->tol, q->max_rounds
+ *     verified: u0_k = row 0 of U;  x_{k+1} = A x_k + B u0_k + C in tpc_mpc_rollout's plant arithmetic on the expanded
+ *            values, literally: ((A00*x0 + A01*x1) + (B00*u0 + B01*u1)) + C0, the multiplies by 1.0 and 0.0 and the
+ *            "+ 0.0" kept (they decide signed zeros and what an Inf becomes);  record u0_k, x_{k+1}, U_k, status = the
+ *            rounds used and the two residuals
+ *     not verified: the instance stops, first_unverified = k
+ *   An instance carried to the end gets first_unverified = steps, and every output row of it equals, bit for bit, what
+ *   tpc_mpc_rollout_newton returns on the expanded arrays (the model above, x0 put in, new_last_targets = NULL,
+ *   controls_inout = NULL, the same q): controls, states, sequences, status, both residuals and first_unverified.
+ *   Phase 2, fallback TPC_MPC_NEWTON_FALLBACK_SOLVE.  The instances with first_unverified < steps and no other flag are
+ *   gathered and expanded to the general form on the device (those instances only), run from step 0 through
+ *   tpc_mpc_rollout_polished's loop (p's eps / max_iter / smo_iters / algo, the same q) and scattered back: every row of
+ *   theirs is what tpc_mpc_rollout_polished returns for exactly those instances in general form, and
+ *   TPC_MPC_FLAG_NOT_POLISHED is raised only for (instance, step) pairs that loop leaves at -1.  first_unverified keeps
+ *   phase 1's value, so the caller sees who fell back.  The order inside the gathered batch is not defined.  One
+ *   4-byte read-back (the number of such instances) sits between the phases.
+ *   Fallback TPC_MPC_NEWTON_FALLBACK_NONE.  Phase 1 only: the rows of an unverified instance from first_unverified on
+ *   are status -1, zero residuals and zero controls / states / sequences, and the instance raises
+ *   TPC_MPC_FLAG_NOT_POLISHED.  With flags_out == NULL and DEVICE memory the call is asynchronous.
+ *   Invalid instances (a non-finite v, delta_y, delta_phi or x0; a model value that is not finite; a state that stops
+ *   being finite at a later step) behave as in tpc_mpc_rollout_newton: they raise TPC_MPC_FLAG_NONFINITE, stop at that
+ *   step (first_unverified = the step, rows as under FALLBACK_NONE), are NOT sent to the fallback under either mode and
+ *   do not raise TPC_MPC_FLAG_NOT_POLISHED by themselves.
+ * Outputs, SoA with leading dimension n: controls_out [steps*2] (required), states_out [steps*2], sequences_out
+ * [steps*H*2] (tpc_mpc_rollout_record's layout: with states_out exactly what tpc_mpc_rollout_backward takes on the
+ * expanded arrays), q->status (int32), q->residual_in, q->residual_out [steps], first_unverified (int32) [n]; all but
+ * controls_out are optional.  p is validated as tpc_mpc_solve_batch_compact validates it.  A null q, tol <= 0 (or NaN),
+ * max_rounds < 0, an unknown fallback, steps < 0 or a dtype other than TPC_MPC_F64 return TPC_MPC_ERR_BAD_ARG.  fp64
+ * only, horizons 1..64, two inputs.  n == 0 or steps == 0 returns TPC_MPC_OK with flags 0.  HOST arrays are staged:
+ * three (+ 2) rows in, the per-step rows out.
+ * A host-only handle (TPC_MPC_DEVICE_NONE) runs FALLBACK_NONE on the calling thread with the kernel's bits (HOST memory
+ * only); with FALLBACK_SOLVE it returns TPC_MPC_ERR_NO_DEVICE, after the argument checks above.
+ * Not part of this entry: per-instance parameter rows, a caller-given start or controller state in and out, a separate
+ * plant or disturbance, a backward or forward-mode kernel of its own (differentiate with tpc_mpc_rollout_backward /
+ * tpc_mpc_rollout_forward on the expanded arrays at the recorded sequences and states), fp32. */
+int tpc_mpc_rollout_compact_exact(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t n, const void* v,
+                                  const void* delta_y, const void* delta_phi, const void* x0 /* optional [2], ld n */,
+                                  int32_t steps, const tpc_mpc_polish* q, int32_t fallback,
+                                  void* controls_out /* [steps*2], ld n */, void* states_out /* optional [steps*2] */,
+                                  void* sequences_out /* optional [steps*H*2] */,
+                                  int32_t* first_unverified /* optional [n] */, uint32_t* flags_out, int mem,
+                                  void* stream);
+
 /* Inputs and outputs of tpc_mpc_rollout_backward, SoA with the io's leading dimension ld:
  *   sequences[steps*H*I]  the recorded sequences, as tpc_mpc_rollout_record returns them (required)
  *   states[steps*2]       the recorded states_out of the same call (required)

@@ -1,0 +1,102 @@
+#!/usr/bin/env python3
+"""Timing of the compact closed loop (tpc_mpc_rollout_compact_exact), fp64, DEVICE memory, in one run on the same
+inputs: rollout_newton on the PRE-EXPANDED general-form arrays (the yardstick; the expansion is not timed) and
+rollout_compact_exact with both fallback modes ("none": the one-launch pass alone; "solve": plus gather-expand,
+rollout_polished's loop on the instances that left the pass, scatter).  All three return controls, states and
+sequences.  Also the share of instances that fell back, the histogram of first_unverified and the mean rounds per
+step.  One JSON line per case; medians of --reps event-timed calls after --warmup untimed ones.
+usage: bench_rollout_compact.py [--reps 20] [--warmup 3] [--out FILE]"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+
+from trajectory_controller_amd import MpcSolver
+from trajectory_controller_amd.synth import compact_inputs
+
+CASES = ((262144, 4, 20), (65536, 10, 50), (262144, 20, 10), (16384, 40, 10))   # (n, H, steps)
+
+
+def timed(fn, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return float(np.median(ms)), float(np.min(ms))
+
+
+def expanded(p, H, v, dy, dphi):
+    """the general form of the compact instances, as mpc_compact (autograd.py) builds it"""
+    n = v.numel()
+    f64 = dict(dtype=torch.float64, device=v.device)
+    T, l = torch.tensor(p.step_size, **f64), torch.tensor(p.wheelbase, **f64)   # (a Python divisor is multiplied by its reciprocal)
+    Tv = T * v
+    one, zero = torch.ones(n, **f64), torch.zeros(n, **f64)
+    rows = lambda *x: torch.tensor(x, **f64)[:, None].expand(len(x), n).contiguous()
+    return [torch.stack([one, Tv, zero, one]), torch.stack([zero, Tv, Tv / l, -Tv / l]),
+            torch.zeros(2, n, **f64), rows(p.weight_y, p.weight_phi),
+            rows(p.weight_steering_front, p.weight_steering_rear), rows(*p.lower), rows(*p.upper),
+            torch.zeros(2, n, **f64), torch.stack([dy, dphi]).repeat(H, 1).contiguous()]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--tol", type=float, default=1e-9)
+    ap.add_argument("--max-rounds", type=int, default=16)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    lines = []
+    for n, H, S in CASES:
+        v, dy, dphi = (torch.from_numpy(a).cuda() for a in compact_inputs(H, n))
+        pol = dict(tol=args.tol, max_rounds=args.max_rounds)
+        with MpcSolver(horizon=H) as s:
+            gen = expanded(s.params, H, v, dy, dphi)
+            rec = dict(horizon=H, steps=S, n=n, **pol)
+            for fallback in ("none", "solve"):
+                rec[f"rollout_newton_{fallback}_ms"], rec[f"rollout_newton_{fallback}_min_ms"] = timed(
+                    lambda: s.rollout_newton(S, *gen, inputs=2, fallback=fallback, want_status=False, **pol),
+                    args.reps, args.warmup)
+                rec[f"compact_{fallback}_ms"], rec[f"compact_{fallback}_min_ms"] = timed(
+                    lambda: s.rollout_compact_exact(S, v, dy, dphi, fallback=fallback, want_status=False, **pol),
+                    args.reps, args.warmup)
+                rec[f"newton_over_compact_{fallback}"] = rec[f"rollout_newton_{fallback}_ms"] / rec[f"compact_{fallback}_ms"]
+
+            c, x, q, st, first = s.rollout_compact_exact(S, v, dy, dphi, fallback="none", **pol)
+            torch.cuda.synchronize()
+            rec["compact_none_flags"] = s.last_flags
+            ref = s.rollout_newton(S, *gen, inputs=2, fallback="none", **pol)
+            torch.cuda.synchronize()
+            rec["same_bits_as_rollout_newton"] = bool(torch.equal(c.view(torch.int64), ref[0].view(torch.int64))
+                                                      and torch.equal(first, ref[5]))
+            ok = st >= 0
+            rec["fell_back"] = int((first < S).sum())
+            rec["fell_back_share"] = float((first < S).double().mean())
+            rec["first_unverified_histogram"] = torch.bincount(first, minlength=S + 1).tolist()
+            rec["mean_rounds_per_step"] = [round(float(st[k][ok[k]].double().mean()), 3) for k in range(S)]
+            _, _, _, st2, _ = s.rollout_compact_exact(S, v, dy, dphi, fallback="solve", **pol)
+            torch.cuda.synchronize()
+            rec["compact_solve_flags"] = s.last_flags
+            rec["verified_share_after_fallback"] = float((st2 >= 0).double().mean())
+        line = json.dumps(rec)
+        print(line, flush=True)
+        lines.append(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

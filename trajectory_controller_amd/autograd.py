@@ -1,7 +1,9 @@
 """torch autograd over the batched general-form solve: `mpc_general` and the reference controller's `mpc_compact`,
 and over the closed loop: `mpc_rollout` (forward MpcSolver.rollout_record, or rollout_polished with polish=True;
 backward tpc_mpc_rollout_backward); and `mpc_compact_exact`, the reference controller with shared or per-instance
-parameters on the exact compact solve and its own backward kernel (no general form on either side).
+parameters on the exact compact solve and its own backward kernel (no general form on either side); and
+`mpc_rollout_compact`, the reference controller's closed loop (forward tpc_mpc_rollout_compact_exact, no general form;
+backward tpc_mpc_rollout_backward on the expansion, built in the backward only; no forward mode).
 
 Forward is MpcSolver.solve_batch_general from a fresh controller (zero controls); backward is
 tpc_mpc_solve_batch_general_backward on torch's current stream (include/tpc_mpc.h gives the definition of the
@@ -261,6 +263,116 @@ def mpc_compact(solver, v, delta_y, delta_phi, weights, step_size=0.1, wheelbase
     u = mpc_general(solver, A, B, torch.zeros(2, n, **f64), w[0:2], w[2:4], rows(lower, 2), rows(upper, 2),
                     torch.zeros(2, n, **f64), targets, polish=polish, **over)
     return u[0], u[1]
+
+
+class _MpcRolloutCompact(torch.autograd.Function):
+    """mpc_rollout_compact: forward tpc_mpc_rollout_compact_exact, backward tpc_mpc_rollout_backward on the expansion"""
+    BY_VALUE = ("weight_y", "weight_phi", "weight_steering_front", "weight_steering_rear", "step_size", "wheelbase",
+                "lower", "upper")
+
+    @staticmethod
+    def forward(ctx, solver, steps, over, polish, v, delta_y, delta_phi, x0, weights, step_size, wheelbase, lower,
+                upper):
+        tol, rounds = polish
+        ins = [t.detach().contiguous() for t in (v, delta_y, delta_phi)]
+        start = None if x0 is None else x0.detach().contiguous()
+        controls, states, sequences, _, _ = solver.rollout_compact_exact(steps, *ins, start, tol=tol, max_rounds=rounds,
+                                                                         want_status=False, **over)
+        ctx.solver, ctx.steps, ctx.over = solver, steps, over
+        ctx.params = [None if t is None else t.detach() for t in (weights, step_size, wheelbase, lower, upper)]
+        ctx.has_x0 = start is not None
+        ctx.save_for_backward(*ins, states, sequences, *(() if start is None else (start,)))
+        return controls, states
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_controls, grad_states):
+        v, delta_y, delta_phi, states, sequences, *rest = ctx.saved_tensors
+        need = ctx.needs_input_grad[4:]      # v, delta_y, delta_phi, x0, then PARAMS
+        if not any(need):
+            return (None,) * 13
+        solver, over = ctx.solver, ctx.over
+        p = solver._params(**over)
+        H, n = p.horizon, v.numel()
+        f64 = dict(dtype=torch.float64, device=v.device)
+        defaults = ([p.weight_y, p.weight_phi, p.weight_steering_front, p.weight_steering_rear], p.step_size,
+                    p.wheelbase, list(p.lower), list(p.upper))
+        with torch.enable_grad():
+            # the leaves: the call's own inputs, and the parameters' values as the forward passed them
+            leaves = [t.detach().requires_grad_(on) for t, on in zip((v, delta_y, delta_phi), need[:3])]
+            leaves.append(rest[0].detach().requires_grad_(need[3]) if ctx.has_x0 else None)
+            for t, d, on in zip(ctx.params, defaults, need[4:]):
+                leaves.append(torch.as_tensor(d if t is None else t, **f64).detach().requires_grad_(on))
+            lv, ly, lp, lx, w, T, l, lo, hi = leaves
+            # mpc_compact's expansion, operation for operation
+            Tv = T * lv
+            one, zero = torch.ones(n, **f64), torch.zeros(n, **f64)
+            rows = lambda x: x[:, None].expand(x.shape[0], n)
+            arr = {"A": torch.stack([one, Tv, zero, one]), "B": torch.stack([zero, Tv, Tv / l, -Tv / l]),
+                   "C": torch.zeros(2, n, **f64), "Q": rows(w[0:2]), "R": rows(w[2:4]), "lower": rows(lo),
+                   "upper": rows(hi), "x0": torch.zeros(2, n, **f64) if lx is None else lx,
+                   "targets": torch.stack([ly, lp]).repeat(H, 1)}
+            want = tuple(k for k, t in arr.items() if t.requires_grad)
+            # (the general-form entry reads none of the compact model's ten values, two of which share its arguments' names)
+            over = {k: x for k, x in over.items() if k not in _MpcRolloutCompact.BY_VALUE}
+            g = solver.rollout_backward(ctx.steps, *[t.detach().contiguous() for t in arr.values()], None,
+                                        sequences=sequences, states=states,
+                                        grad_controls=None if grad_controls is None else grad_controls.contiguous(),
+                                        grad_states=None if grad_states is None else grad_states.contiguous(),
+                                        inputs=2, want=want, want_flags=False, **over)
+            on = [t for t in leaves if t is not None and t.requires_grad]
+            got = iter(torch.autograd.grad([arr[k] for k in want], on, [g[k] for k in want], allow_unused=True))
+        out = [next(got) if t is not None and t.requires_grad else None for t in leaves]
+        for i, t in enumerate(ctx.params):     # onto the given parameter tensors
+            if out[4 + i] is not None:
+                out[4 + i] = out[4 + i].to(device=t.device, dtype=t.dtype).reshape(t.shape)
+        return (None, None, None, None) + tuple(out)
+
+
+def mpc_rollout_compact(solver, steps, v, delta_y, delta_phi, weights=None, step_size=None, wheelbase=None,
+                        lower=None, upper=None, x0=None, polish=(1e-9, 16), **over):
+    """The reference controller's closed loop as a differentiable function: mpcControllerTobi's model rolled forward
+    `steps` steps, every step the verified optimum, the target (delta_y, delta_phi) held.  Returns
+    (controls [steps*2, n], states [steps*2, n]).  What a tuner wants: weights fitted to one-step steering
+    (mpc_compact_exact) say nothing about how the loop behaves; weights fitted through this function do.
+
+    The forward is MpcSolver.rollout_compact_exact (tpc_mpc_rollout_compact_exact: three doubles in per instance, all
+    steps in one launch, no general form; the instances the Newton rounds do not verify run the polished loop) with
+    polish = (tol, max_rounds).  v, delta_y, delta_phi are CUDA fp64 tensors [n], x0 a CUDA fp64 tensor [2, n] or None
+    (zeros).  The shared parameters are tensors `weights` [4] (weight_y, weight_phi, weight_steering_front,
+    weight_steering_rear), `step_size` [], `wheelbase` [], `lower` [2] and `upper` [2] on any device, None taking the
+    solver's own value (with `over`'s overrides); their values go into tpc_mpc_params by value, as in
+    mpc_compact_exact.
+    The backward is the existing tpc_mpc_rollout_backward on the expanded arrays at the recorded sequences and states:
+    mpc_compact's torch expansion (A = [1, Tv; 0, 1], B = [0, Tv; Tv/l, -Tv/l], ...) is built in the backward only, and
+    its chain rule carries the gradient to v, delta_y, delta_phi, x0 and every given parameter that requires grad; only
+    the expanded arrays that depend on such an input are differentiated.  A fused compact backward kernel, which would
+    not materialise the general form there either, is the follow-up.  Once-differentiable; no forward mode."""
+    for t in (v, delta_y, delta_phi) + (() if x0 is None else (x0,)):
+        if not (t.is_cuda and t.dtype == torch.float64):
+            raise ValueError("mpc_rollout_compact takes CUDA fp64 tensors v, delta_y, delta_phi and x0")
+    n = v.numel()
+    if x0 is not None and tuple(x0.shape) != (2, n):
+        raise ValueError(f"x0 must have shape [2, {n}]")
+    over = dict(over)
+    given = []
+    for name, t, shape in (("weights", weights, (4,)), ("step_size", step_size, ()), ("wheelbase", wheelbase, ()),
+                           ("lower", lower, (2,)), ("upper", upper, (2,))):
+        if t is None:
+            given.append(None)
+            continue
+        t = t if torch.is_tensor(t) else torch.as_tensor(t, dtype=torch.float64)
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} must have shape {list(shape)}")
+        val = t.detach().to(device="cpu", dtype=torch.float64).tolist()
+        if name == "weights":
+            over.update(weight_y=val[0], weight_phi=val[1], weight_steering_front=val[2], weight_steering_rear=val[3])
+        else:
+            over[name] = tuple(val) if shape else val
+        given.append(t)
+    tol, rounds = polish
+    return _MpcRolloutCompact.apply(solver, int(steps), over, (float(tol), int(rounds)), v, delta_y, delta_phi, x0,
+                                    *given)
 
 
 class CompactWarmStart:

@@ -48,7 +48,8 @@ EXPORTS = ("tpc_mpc_default_params", "tpc_mpc_create", "tpc_mpc_destroy", "tpc_m
            "tpc_mpc_rollout_plant_backward", "tpc_mpc_rollout_plant_forward",
            "tpc_mpc_solve_batch_compact_exact", "tpc_mpc_solve_batch_compact_exact_backward",
            "tpc_mpc_solve_batch_compact_exact_rows", "tpc_mpc_solve_batch_compact_exact_rows_backward",
-           "tpc_mpc_solve_batch_compact_exact_from", "tpc_mpc_solve_batch_compact_exact_forward")
+           "tpc_mpc_solve_batch_compact_exact_from", "tpc_mpc_solve_batch_compact_exact_forward",
+           "tpc_mpc_rollout_compact_exact")
 # the shared parameters of tpc_mpc_solve_batch_compact_exact_backward, in the order of its dparams / dparams_rows -- and
 # of the rows of params_rows that the _rows entries take
 COMPACT_PARAM_NAMES = ("weight_y", "weight_phi", "weight_steering_front", "weight_steering_rear", "step_size",
@@ -215,6 +216,8 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.tpc_mpc_solve_batch_compact_exact_forward.argtypes = [vp, C.POINTER(Params), C.c_int64, vp, vp, vp, vp, vp, vp,
                                                               C.POINTER(CompactTangents), vp, vp, vp, u32p, C.c_int,
                                                               vp]
+    lib.tpc_mpc_rollout_compact_exact.argtypes = [vp, C.POINTER(Params), C.c_int64, vp, vp, vp, vp, C.c_int32,
+                                                  C.POINTER(Polish), C.c_int32, vp, vp, vp, vp, u32p, C.c_int, vp]
     lib.tpc_mpc_rollout_backward.argtypes = [vp, C.POINTER(Params), C.POINTER(GeneralIO), C.c_int32, vp,
                                              C.POINTER(RolloutGrad), u32p, C.c_int, vp]
     lib.tpc_mpc_solve_batch_general_forward.argtypes = [vp, C.POINTER(Params), C.POINTER(GeneralIO), vp,

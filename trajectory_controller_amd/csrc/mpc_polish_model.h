@@ -54,6 +54,18 @@ TPC_GRAD_HD constexpr int slots(int I) { return grad::slots(I) + I; }
 
 TPC_GRAD_HD double clampd(double u, double lo, double hi) { return u < lo ? lo : (u > hi ? hi : u); }
 
+// For the closed loops that run every step of an instance in one lane (mpc_rollout_newton.hip, mpc_compact_loop_model.h):
+// the step loop must cost no registers beyond one step's.  Without this the compiler hoists every array's per-lane
+// address (base + k, two VGPRs each, some forty of them in the general form) out of the loop and the kernel loses half
+// its occupancy.  An instance index the optimiser cannot see through is re-made per step, so the addresses are formed
+// where used.
+TPC_GRAD_HD int64_t per_step(int64_t k) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(k));
+#endif
+    return k;
+}
+
 // The rounds, on the working copy the caller has put in slots 4 + I + j.  tg_at(t, c) is component c of step t's target.
 // Returns the round at which res <= tol, with that res in res_out and the verified sequence in the working copy; -1 when
 // a df overflowed or max_rounds were used up (res_out is left alone).  res_in is round 0's residual either way.

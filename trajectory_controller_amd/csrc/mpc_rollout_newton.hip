@@ -18,15 +18,7 @@ namespace tpc {
 
 namespace {
 
-// The step loop must cost no registers beyond one step's: without this the compiler hoists every array's per-lane
-// address (base + k, two VGPRs each, some forty of them) out of the loop and the kernel loses half its occupancy.
-// An instance index the optimiser cannot see through is re-made per step, so the addresses are formed where used.
-TPC_GRAD_HD int64_t per_step(int64_t k) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("" : "+v"(k));
-#endif
-    return k;
-}
+using polish::per_step;
 
 // One instance, every step.  Returns the flags of the step it stopped at (0: verified at every step) and that step in
 // *first.  Rows of the per-step outputs from *first on are cleared: status -1, everything else 0, and so is the

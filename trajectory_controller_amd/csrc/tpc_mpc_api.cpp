@@ -12,6 +12,7 @@
 #include "mpc_polish_model.h"
 #include "mpc_rollout_newton.h"
 #include "mpc_newton_compact.h"
+#include "mpc_compact_loop.h"
 #include "mpc_compact_grad.h"
 #include "mpc_compact_tangent.h"
 #include "mpc_tangent_model.h"
@@ -2049,6 +2050,166 @@ int tpc_mpc_solve_batch_compact_exact_from(tpc_mpc_handle h, const tpc_mpc_param
                                            int32_t* fell_back, uint32_t* flags_out, int mem, void* stream) {
     return compact_exact_impl(h, p, n, v, delta_y, delta_phi, params_rows != nullptr, params_rows, true, start, q,
                               fallback, steering_front, steering_rear, sequence_out, fell_back, flags_out, mem, stream);
+}
+
+// The compact closed loop (include/tpc_mpc.h): phase 1 is ONE launch for the whole loop, three (+ 2) rows in and the
+// per-step rows out (mpc_compact_loop.hip); with TPC_MPC_NEWTON_FALLBACK_SOLVE the instances it stopped are gathered
+// and expanded to the general form on the device, run through rollout_impl's polished mode from step 0 and scattered
+// back (rollout_newton_move).  One 4-byte read-back (the fallback's count) sits between the phases; a host-only handle
+// runs phase 1 on the calling thread.  The Newton working set holds the queue (h->newton) and the compact batch
+// (h->newton_fb), rebuilt by every call; HOST arrays are staged in h->stage (stage_in / stage_out), which the fallback
+// -- called with TPC_MPC_DEVICE -- does not touch.
+int tpc_mpc_rollout_compact_exact(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t n, const void* v,
+                                  const void* delta_y, const void* delta_phi, const void* x0, int32_t steps,
+                                  const tpc_mpc_polish* q, int32_t fallback, void* controls_out, void* states_out,
+                                  void* sequences_out, int32_t* first_unverified, uint32_t* flags_out, int mem,
+                                  void* stream) {
+    return guarded(h, [&]() -> int {
+        int rc = check_common(h, p, true);
+        if (rc) return rc;
+        if (p->dtype != TPC_MPC_F64) return fp64_only(h, "tpc_mpc_rollout_compact_exact");
+        rc = check_compact_model(h, p);
+        if (rc) return rc;
+        rc = check_batch(h, n, mem);
+        if (!rc) rc = check_polish(h, q);
+        if (!rc) rc = check_fallback(h, fallback);
+        if (!rc) rc = check_steps(h, steps);
+        if (rc) return rc;
+        const bool solve = fallback == TPC_MPC_NEWTON_FALLBACK_SOLVE;
+        rc = check_host_only_newton(h, solve, mem);
+        if (rc) return rc;
+        if (n == 0 || steps == 0) { if (flags_out) *flags_out = 0; return TPC_MPC_OK; }
+        if (!v || !delta_y || !delta_phi || !controls_out) return fail(h, TPC_MPC_ERR_BAD_ARG, "null batch pointer");
+        const int H = p->horizon;
+        const int64_t S = steps;
+
+        cloop::Args a;
+        std::memset(&a, 0, sizeof(a));
+        a.c.n = n;
+        bind_compact_model(&a.c, p);
+        a.c.tol = q->tol; a.c.max_rounds = q->max_rounds;
+        a.c.raise_not_polished = solve ? 0 : 1;
+        a.steps = steps;
+        // the call's arrays, every one with the leading dimension n in the caller's memory
+        enum { kV, kDy, kDphi, kX0, kCtrl, kStates, kSeq, kRin, kRout, kStatus, kFirst, kCount };
+        StagedArray t[kCount] = {staged(v, kStageIn, 1, n), staged(delta_y, kStageIn, 1, n), staged(delta_phi, kStageIn, 1, n),
+                                 staged(x0, kStageIn, 2, n), staged(controls_out, kStageOut, S * 2, n),
+                                 staged(states_out, kStageOut, S * 2, n), staged(sequences_out, kStageOut, S * H * 2, n),
+                                 staged(q->residual_in, kStageOut, S, n), staged(q->residual_out, kStageOut, S, n),
+                                 staged(q->status, kStageOut, S, n, 4), staged(first_unverified, kStageOut, 1, n, 4)};
+        // what the kernels take: the caller's arrays (DEVICE, or a host-only handle) or the slots of HOST arrays
+        auto bind = [&](int64_t ld) {
+            a.c.v = (const double*)t[kV].dev; a.c.dy = (const double*)t[kDy].dev; a.c.dphi = (const double*)t[kDphi].dev;
+            a.x0 = (const double*)t[kX0].dev;
+            a.controls = (double*)t[kCtrl].dev; a.states = (double*)t[kStates].dev; a.sequences = (double*)t[kSeq].dev;
+            a.res_in = (double*)t[kRin].dev; a.res_out = (double*)t[kRout].dev;
+            a.status = (int32_t*)t[kStatus].dev; a.first = (int32_t*)t[kFirst].dev;
+            a.ld_x0 = a.ld_out = ld;
+        };
+
+        if (h->host_only) {   // on the calling thread, straight from and into the caller's arrays
+            bind(n);
+            const uint32_t f = compact_loop_host(H, a);
+            if (flags_out) *flags_out = f;
+            return TPC_MPC_OK;
+        }
+
+        HIP_TRY(h, hipSetDevice(h->device));
+        hipStream_t s = (hipStream_t)stream;
+        StreamOrderScope order(h, s);
+        rc = order.begin();
+        if (rc) return rc;
+        const bool host = mem == TPC_MPC_HOST;
+        // the working set: the queue and two words ([0] the fallback's count, [1] phase 1's flags)
+        const int64_t o_words = stage_ld(n) * 4;
+        rc = ensure(h, &h->newton, &h->newton_bytes, o_words + 256);
+        if (rc) return rc;
+        if (!compact_loop_in_registers(H)) {
+            rc = ensure(h, &h->grad_ws, &h->grad_ws_bytes, pad256(polish_scratch_bytes(2, H, n)));
+            if (rc) return rc;
+        }
+        char* w = (char*)h->newton;
+        int32_t* d_idx = (int32_t*)w;
+        uint32_t* d_words = (uint32_t*)(w + o_words);
+        HIP_TRY(h, hipMemsetAsync(d_words, 0, 8, s));
+        if (host) {
+            rc = stage_in(h, t, kCount, n, s);
+            if (rc) return rc;
+        }
+        const int64_t ld = host ? stage_ld(n) : n;
+        bind(ld);
+        a.c.fb_index = solve ? d_idx : nullptr;
+        a.c.fb_count = d_words;
+        hipError_t e = compact_loop(H, a, h->grad_ws, d_words + 1, s);
+        if (e != hipSuccess) return hip_fail(h, e, "kernel launch");
+
+        uint32_t count = 0;
+        if (solve) {
+            HIP_TRY(h, hipMemcpyAsync(&count, d_words, sizeof(count), hipMemcpyDeviceToHost, s));
+            HIP_TRY(h, hipStreamSynchronize(s));
+        }
+        if (count > 0) {
+            // the compact batch, leading dimension ldc: the general form of the queued instances, then every output
+            // of the polished loop that the caller asked for
+            const int64_t cnt = count, ldc = (cnt + 63) / 64 * 64;
+            int64_t r_total = 0;
+            auto take = [&](bool on, int64_t r) { const int64_t at = r_total; if (on) r_total += r; return on ? at : -1; };
+            const int64_t r_model = take(true, 20 + 2 * H), r_ctrl = take(true, S * 2);
+            const int64_t r_states = take(a.states != nullptr, S * 2), r_seq = take(a.sequences != nullptr, S * H * 2);
+            const int64_t r_rin = take(a.res_in != nullptr, S), r_rout = take(a.res_out != nullptr, S);
+            const int64_t o_i32 = r_total * ldc * 8;   // the int32 rows behind the fp64 ones: status
+            rc = ensure(h, &h->newton_fb, &h->newton_fb_bytes, o_i32 + S * ldc * 4);
+            if (rc) return rc;
+            char* fb = (char*)h->newton_fb;
+            auto fat = [&](int64_t r) -> double* { return r < 0 ? nullptr : (double*)(fb + r * ldc * 8); };
+            int32_t* f_status = a.status ? (int32_t*)(fb + o_i32) : nullptr;
+            int64_t r = r_model;
+            auto rowf = [&](int64_t rows) { double* at = fat(r); r += rows; return at; };
+            CompactLoopBatch b;
+            std::memset(&b, 0, sizeof(b));
+            b.count = cnt; b.ld = ldc; b.index = d_idx; b.H = H;
+            b.A = rowf(4); b.B = rowf(4); b.C = rowf(2); b.Q = rowf(2); b.R = rowf(2); b.lo = rowf(2); b.hi = rowf(2);
+            b.x0 = rowf(2); b.targets = rowf(2 * H);
+            e = compact_loop_gather(a, b, s);
+            if (e != hipSuccess) return hip_fail(h, e, "gather launch");
+
+            tpc_mpc_general_io io2;
+            std::memset(&io2, 0, sizeof(io2));
+            io2.inputs = 2; io2.n = cnt; io2.ld = ldc;
+            io2.A = b.A; io2.B = b.B; io2.C = b.C; io2.Q = b.Q; io2.R = b.R; io2.lower = b.lo; io2.upper = b.hi;
+            io2.x0 = b.x0; io2.targets = b.targets;
+            tpc_mpc_polish q2 = *q;
+            q2.status = f_status; q2.residual_in = fat(r_rin); q2.residual_out = fat(r_rout);
+            // its flags stay in the handle's word (no flags_out: no synchronisation); phase 1's are merged in below
+            rc = rollout_impl(h, p, &io2, steps, nullptr, fat(r_ctrl), fat(r_states), nullptr, fat(r_seq), false, true,
+                              &q2, nullptr, TPC_MPC_DEVICE, stream);
+            if (rc) return rc;
+
+            NewtonMove sc;
+            std::memset(&sc, 0, sizeof(sc));
+            sc.count = cnt; sc.index = d_idx;
+            sc.set[sc.sets++] = NewtonRows{fat(r_ctrl), a.controls, S * 2, ldc, ld, 8};
+            if (a.states) sc.set[sc.sets++] = NewtonRows{fat(r_states), a.states, S * 2, ldc, ld, 8};
+            if (a.sequences) sc.set[sc.sets++] = NewtonRows{fat(r_seq), a.sequences, S * H * 2, ldc, ld, 8};
+            if (a.res_in) sc.set[sc.sets++] = NewtonRows{fat(r_rin), a.res_in, S, ldc, ld, 8};
+            if (a.res_out) sc.set[sc.sets++] = NewtonRows{fat(r_rout), a.res_out, S, ldc, ld, 8};
+            if (a.status) sc.set[sc.sets++] = NewtonRows{f_status, a.status, S, ldc, ld, 4};
+            e = rollout_newton_move(sc, true, s);
+            if (e != hipSuccess) return hip_fail(h, e, "scatter launch");
+        } else {
+            HIP_TRY(h, hipMemsetAsync(h->ws_words + 1, 0, sizeof(uint32_t), s));
+        }
+        e = rollout_newton_merge_flags(h->ws_words + 1, d_words + 1, s);
+        if (e != hipSuccess) return hip_fail(h, e, "flag merge launch");
+
+        if (host) {
+            rc = stage_out(h, t, kCount, n, s);
+            if (rc) return rc;
+        }
+        rc = order.end();
+        if (rc) return rc;
+        return finish_flags(h, flags_out, s);
+    });
 }
 
 // The backward pass of the exact compact solve: one launch of the adjoint sweep on the model built from v

@@ -653,6 +653,42 @@ class MpcSolver:
         out = (c_out, s_out, q_out, status, i_out)
         return out + (first[0],) if newton else out
 
+    def rollout_compact_exact(self, steps: int, v, delta_y, delta_phi, x0=None, tol: float = 1e-9,
+                              max_rounds: int = 16, fallback: str = "solve", want_states: bool = True,
+                              want_sequences: bool = True, want_status: bool = True, residuals=None, **over):
+        """The reference controller rolled forward `steps` steps on its own model, every step the verified optimum
+        (tpc_mpc_rollout_compact_exact), fp64 only: rollout_newton on the model solve_batch_compact_exact builds from
+        (v, delta_y, delta_phi) -- the target stays (delta_y, delta_phi) at every step -- without the general form:
+        three vectors [n] in (and x0 [2, n], None = zeros), all steps of an instance in one lane, one launch.
+        fallback="solve": the instances the Newton rounds stopped are expanded on the device, run from step 0 through
+        rollout_polished's loop and written back; fallback="none": their rows from the stop on are status -1 and zeros
+        and last_flags carries FLAG_NOT_POLISHED (the only mode of a host-only solver, device=None).  Arrays as in
+        solve_batch_compact_exact (numpy: HOST memory, CUDA tensors: DEVICE memory on the current stream).  Returns
+        (controls[steps*2, n], states[steps*2, n] | None, sequences[steps*H*2, n] | None, status[steps, n] | None,
+        first_unverified[n] | None): rollout_newton's rows on the expanded arrays, bit for bit for an instance carried
+        to the end; status holds the Newton rounds of each (step, instance) and first_unverified (int32) the step
+        phase 1 stopped at, `steps` for an instance it carried through -- both None with want_status=False, which with
+        fallback="none" also leaves last_flags at 0 and keeps a DEVICE call asynchronous.  residuals: optionally a pair
+        of fp64 arrays [steps, n] of the inputs' kind that receive residual_in and residual_out of every (step,
+        instance).  sequences and states are what rollout_backward takes on the expanded arrays (autograd:
+        mpc_rollout_compact)."""
+        p = self._params(**over)
+        H, S = p.horizon, int(steps)
+        ar = Arrays(v)
+        vectors = ar.read_rows((v, delta_y, delta_phi), None, "length")
+        c_out = ar.new(S * 2)
+        s_out = ar.new(S * 2) if want_states else None
+        q_out = ar.new(S * H * 2) if want_sequences else None
+        status = ar.new(S, dtype=_I32) if want_status else None
+        first = ar.new(dtype=_I32) if want_status else None
+        rin, rout = residuals if residuals is not None else (None, None)
+        q = capi.Polish(tol=float(tol), max_rounds=int(max_rounds), reserved=0, status=ar.addr(status),
+                        residual_in=ar.update(rin, S), residual_out=ar.update(rout, S))
+        self._run(self._lib.tpc_mpc_rollout_compact_exact, p, ar, ar.n, *vectors, ar.read(x0, 2), S, C.byref(q),
+                  capi.NEWTON_FALLBACKS[fallback], ar.addr(c_out), ar.addr(s_out), ar.addr(q_out), ar.addr(first),
+                  want_flags=want_status or fallback != "none")
+        return c_out, s_out, q_out, status, first
+
     ROLLOUT_GRAD_NAMES = GRAD_NAMES[:-1] + ("new_last_targets", "kkt_residual")
     PLANT_GRAD_NAMES = ("Ap", "Bp", "Cp", "disturbance")
 
