@@ -769,8 +769,9 @@ int tpc_mpc_solve_batch_compact_exact_forward(tpc_mpc_handle h, const tpc_mpc_pa
  * A host-only handle (TPC_MPC_DEVICE_NONE) runs FALLBACK_NONE on the calling thread with the kernel's bits (HOST memory
  * only); with FALLBACK_SOLVE it returns TPC_MPC_ERR_NO_DEVICE, after the argument checks above.
  * Not part of this entry: per-instance parameter rows, a caller-given start or controller state in and out, a separate
- * plant or disturbance, a backward or forward-mode kernel of its own (differentiate with tpc_mpc_rollout_backward /
- * tpc_mpc_rollout_forward on the expanded arrays at the recorded sequences and states), fp32. */
+ * plant or disturbance, a forward-mode kernel of its own (differentiate forward with tpc_mpc_rollout_forward on the
+ * expanded arrays at the recorded sequences and states), fp32.  Its backward pass is
+ * tpc_mpc_rollout_compact_exact_backward below. */
 int tpc_mpc_rollout_compact_exact(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t n, const void* v,
                                   const void* delta_y, const void* delta_phi, const void* x0 /* optional [2], ld n */,
                                   int32_t steps, const tpc_mpc_polish* q, int32_t fallback,
@@ -778,6 +779,75 @@ int tpc_mpc_rollout_compact_exact(tpc_mpc_handle h, const tpc_mpc_params* p, int
                                   void* sequences_out /* optional [steps*H*2] */,
                                   int32_t* first_unverified /* optional [n] */, uint32_t* flags_out, int mem,
                                   void* stream);
+
+/* The incoming gradient and the outputs of tpc_mpc_rollout_compact_exact_backward, fp64, SoA with leading dimension n.
+ * The ten shared parameters are indexed as in tpc_mpc_compact_grad. */
+typedef struct tpc_mpc_compact_loop_grad {
+    const void *grad_controls;   /* optional [steps*2], ld n: dL/dcontrols_out; NULL = zero */
+    const void *grad_states;     /* optional [steps*2], ld n: dL/dstates_out;   NULL = zero */
+    void *dv, *ddelta_y, *ddelta_phi;   /* optional outputs [n] */
+    void *dx0;                   /* optional output [2], ld n (allowed with x0 == NULL: the gradient at the zero start) */
+    void *dparams_rows;          /* optional output [10], ld n */
+    void *dparams;               /* optional output [10]: the batch sum */
+    void *kkt_residual;          /* optional output [n] */
+} tpc_mpc_compact_loop_grad;
+
+/* No reference counterpart.  The backward pass of tpc_mpc_rollout_compact_exact: for n instances that share p's
+ * weights, step_size, wheelbase and bounds, the gradient of a loss L(controls_out, states_out) with respect to v,
+ * delta_y, delta_phi, x0 and those ten shared parameters, taken at the recorded `sequences` and `states` of that call,
+ * without the general form ever being written.
+ *   Definition.  Instance k has the expanded model of tpc_mpc_rollout_compact_exact (T = p->step_size, l = p->wheelbase,
+ *   Tv = T * v: A = [1, Tv; 0, 1], B = [0, Tv; Tv/l, -Tv/l], C = 0, every target (delta_y, delta_phi) at every step) and
+ *   the start x_0 = column k of x0, or (+0.0, +0.0) when x0 is NULL.  The reverse sweep of tpc_mpc_rollout_backward
+ *   (csrc/mpc_grad_model.h, rollout_instance<2>, operation for operation, new_last_targets = NULL) runs on that model.
+ *   With lambda = 0 and the sums s = 0, for k = steps-1 down to 0, absent gradient arrays counting as +0.0:
+ *     mu      = lambda + grad_states[k]
+ *     s      += the plant terms of x_{k+1} = A x_k + B u0_k + C (dA += mu x_k', dB += mu u0_k', dC += mu), u0_k = row 0
+ *               of sequences[k]
+ *     g0[j]   = fma(B[0][j], mu0, fma(B[1][j], mu1, grad_controls[k*2+j]))
+ *     qp_step<2>, unchanged, at x_k, U_k = sequences[k] and g = g0 on row 0, 0.0 elsewhere; it adds to s and hands over
+ *               dL/dtarget_t = (a_t, b_t) with t from H-1 down to 0.  x_k is x_0 for k = 0, else the recorded
+ *               states[k-1]: the state is never recomputed
+ *     lambda  = A' mu + dL/dx_k of that solve
+ *   Then, every operation rounded on its own:
+ *     S = s.A01 + s.B0[1]      D = s.B1[0] - s.B1[1]      Tv = T * v
+ *     dv         = T * S + (T / l) * D
+ *     ddelta_y   = the sum of every a_t, added to 0.0 one by one in the order they arrive (k descending, t descending
+ *                  inside a step); ddelta_phi likewise with b_t
+ *     dx0        = lambda after step 0
+ *     rows[0..3] = s.Q0, s.Q1, s.R[0], s.R[1]
+ *     rows[4]    = v * S + (v / l) * D                               (step_size)
+ *     rows[5]    = -((Tv / l) / l) * D                               (wheelbase)
+ *     rows[6..9] = s.lo[0], s.lo[1], s.hi[0], s.hi[1]
+ *     kkt_residual = s.kkt, the maximum over the steps
+ *   dv, dx0, rows and kkt_residual equal, up to the sign of a zero, tpc_mpc_rollout_backward on the expanded arrays
+ *   pushed through the same lines; ddelta_y / ddelta_phi are that entry's dtargets rows summed in another order.
+ *   dparams[c] is the sum of rows[c] over the contributing instances.
+ *   Excluded instances.  A negative entry anywhere in the instance's column of `status` (nobody should differentiate
+ *   the zeros that stand in for an unverified step; it raises no flag of its own, and the sweep still runs, so a NaN
+ *   speed still raises its flag); a non-finite v, target, x0, recorded state or sequence, incoming gradient or model
+ *   value (TPC_MPC_FLAG_NONFINITE); a model that breaks dlib's requires clause (TPC_MPC_FLAG_BAD_MODEL).  An excluded
+ *   instance gets 0.0 in every per-instance output and adds nothing to dparams.
+ *   Method.  One lane per instance (csrc/mpc_compact_loop_grad.hip); lambda, the sums and the two target sums stay in
+ *   registers over the steps, one step's values live in the handle's gradient workspace and are reused by every step,
+ *   at horizons 4 and 5 in registers.  dparams is summed as tpc_mpc_solve_batch_compact_exact_backward sums it -- no
+ *   floating-point atomics, the same bytes on every call; the order depends on n and is not the ascending-k order.
+ * p is validated as tpc_mpc_solve_batch_compact validates it.  v, delta_y, delta_phi [n], sequences ([steps*H*2]) and
+ * states ([steps*2]) as tpc_mpc_rollout_compact_exact returned them are required; x0 ([2]) and status (int32 [steps],
+ * q->status of that call) are optional; every output of g is optional, and with none the call only sets the flags.
+ * fp64 only, horizons 1..64.  A null g, null sequences or states, steps < 0 or a dtype other than TPC_MPC_F64 return
+ * TPC_MPC_ERR_BAD_ARG.  n == 0 or steps == 0 returns TPC_MPC_OK with flags 0 and writes zeros to dparams.  HOST arrays
+ * are staged; with DEVICE memory and flags_out == NULL the call is asynchronous on `stream`.  A host-only handle
+ * (TPC_MPC_DEVICE_NONE) runs HOST batches on the calling thread with the kernel's per-instance bits, its dparams summed
+ * in ascending k, and returns TPC_MPC_ERR_NO_DEVICE for DEVICE memory.
+ * Not part of this entry: forward mode, per-instance parameter rows, a separate plant or disturbance, fp32. */
+int tpc_mpc_rollout_compact_exact_backward(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t n, const void* v,
+                                           const void* delta_y, const void* delta_phi,
+                                           const void* x0 /* optional [2], ld n */, int32_t steps,
+                                           const void* sequences /* [steps*H*2] */, const void* states /* [steps*2] */,
+                                           const int32_t* status /* optional [steps], ld n */,
+                                           const tpc_mpc_compact_loop_grad* g, uint32_t* flags_out, int mem,
+                                           void* stream);
 
 /* Inputs and outputs of tpc_mpc_rollout_backward, SoA with the io's leading dimension ld:
  *   sequences[steps*H*I]  the recorded sequences, as tpc_mpc_rollout_record returns them (required)

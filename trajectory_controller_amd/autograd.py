@@ -3,7 +3,8 @@ and over the closed loop: `mpc_rollout` (forward MpcSolver.rollout_record, or ro
 backward tpc_mpc_rollout_backward); and `mpc_compact_exact`, the reference controller with shared or per-instance
 parameters on the exact compact solve and its own backward kernel (no general form on either side); and
 `mpc_rollout_compact`, the reference controller's closed loop (forward tpc_mpc_rollout_compact_exact, no general form;
-backward tpc_mpc_rollout_backward on the expansion, built in the backward only; no forward mode).
+backward tpc_mpc_rollout_backward on the expansion, built in the backward only, or with backward="fused" one call of
+tpc_mpc_rollout_compact_exact_backward, no general form either; no forward mode).
 
 Forward is MpcSolver.solve_batch_general from a fresh controller (zero controls); backward is
 tpc_mpc_solve_batch_general_backward on torch's current stream (include/tpc_mpc.h gives the definition of the
@@ -266,16 +267,20 @@ def mpc_compact(solver, v, delta_y, delta_phi, weights, step_size=0.1, wheelbase
 
 
 class _MpcRolloutCompact(torch.autograd.Function):
-    """mpc_rollout_compact: forward tpc_mpc_rollout_compact_exact, backward tpc_mpc_rollout_backward on the expansion"""
+    """mpc_rollout_compact: forward tpc_mpc_rollout_compact_exact; backward tpc_mpc_rollout_backward on the expansion
+    ("expanded") or one call of tpc_mpc_rollout_compact_exact_backward ("fused")"""
+    PARAMS = ("weights", "step_size", "wheelbase", "lower", "upper")
+    SLICES = {"weights": slice(0, 4), "step_size": 4, "wheelbase": 5, "lower": slice(6, 8), "upper": slice(8, 10)}
     BY_VALUE = ("weight_y", "weight_phi", "weight_steering_front", "weight_steering_rear", "step_size", "wheelbase",
                 "lower", "upper")
 
     @staticmethod
     def forward(ctx, solver, steps, over, polish, v, delta_y, delta_phi, x0, weights, step_size, wheelbase, lower,
                 upper):
-        tol, rounds = polish
+        tol, rounds, fused = polish
         ins = [t.detach().contiguous() for t in (v, delta_y, delta_phi)]
         start = None if x0 is None else x0.detach().contiguous()
+        ctx.fused = fused
         controls, states, sequences, _, _ = solver.rollout_compact_exact(steps, *ins, start, tol=tol, max_rounds=rounds,
                                                                          want_status=False, **over)
         ctx.solver, ctx.steps, ctx.over = solver, steps, over
@@ -292,6 +297,24 @@ class _MpcRolloutCompact(torch.autograd.Function):
         if not any(need):
             return (None,) * 13
         solver, over = ctx.solver, ctx.over
+        if ctx.fused:
+            # one call: only the outputs someone needs; no status, so both routes differentiate the same instances
+            want = tuple(k for k, on in zip(("v", "delta_y", "delta_phi", "x0"), need[:4]) if on)
+            if any(need[4:]):
+                want += ("params",)
+            g = solver.rollout_compact_exact_backward(
+                ctx.steps, v, delta_y, delta_phi, rest[0] if ctx.has_x0 else None, sequences=sequences, states=states,
+                grad_controls=None if grad_controls is None else grad_controls.contiguous(),
+                grad_states=None if grad_states is None else grad_states.contiguous(), want=want, want_flags=False,
+                **over)
+            out = [g.get("v"), g.get("delta_y"), g.get("delta_phi"), g.get("x0")]
+            for name, t, on in zip(_MpcRolloutCompact.PARAMS, ctx.params, need[4:]):   # onto the given parameter tensors
+                if not on:
+                    out.append(None)
+                    continue
+                d = g["params"][_MpcRolloutCompact.SLICES[name]]
+                out.append(d.to(device=t.device, dtype=t.dtype).reshape(t.shape))
+            return (None, None, None, None) + tuple(out)
         p = solver._params(**over)
         H, n = p.horizon, v.numel()
         f64 = dict(dtype=torch.float64, device=v.device)
@@ -330,7 +353,7 @@ class _MpcRolloutCompact(torch.autograd.Function):
 
 
 def mpc_rollout_compact(solver, steps, v, delta_y, delta_phi, weights=None, step_size=None, wheelbase=None,
-                        lower=None, upper=None, x0=None, polish=(1e-9, 16), **over):
+                        lower=None, upper=None, x0=None, polish=(1e-9, 16), backward="expanded", **over):
     """The reference controller's closed loop as a differentiable function: mpcControllerTobi's model rolled forward
     `steps` steps, every step the verified optimum, the target (delta_y, delta_phi) held.  Returns
     (controls [steps*2, n], states [steps*2, n]).  What a tuner wants: weights fitted to one-step steering
@@ -343,11 +366,19 @@ def mpc_rollout_compact(solver, steps, v, delta_y, delta_phi, weights=None, step
     weight_steering_rear), `step_size` [], `wheelbase` [], `lower` [2] and `upper` [2] on any device, None taking the
     solver's own value (with `over`'s overrides); their values go into tpc_mpc_params by value, as in
     mpc_compact_exact.
-    The backward is the existing tpc_mpc_rollout_backward on the expanded arrays at the recorded sequences and states:
-    mpc_compact's torch expansion (A = [1, Tv; 0, 1], B = [0, Tv; Tv/l, -Tv/l], ...) is built in the backward only, and
-    its chain rule carries the gradient to v, delta_y, delta_phi, x0 and every given parameter that requires grad; only
-    the expanded arrays that depend on such an input are differentiated.  A fused compact backward kernel, which would
-    not materialise the general form there either, is the follow-up.  Once-differentiable; no forward mode."""
+    backward="expanded" (the default): tpc_mpc_rollout_backward on the expanded arrays at the recorded sequences and
+    states: mpc_compact's torch expansion (A = [1, Tv; 0, 1], B = [0, Tv; Tv/l, -Tv/l], ...) is built in the backward
+    only, and its chain rule carries the gradient to v, delta_y, delta_phi, x0 and every given parameter that requires
+    grad; only the expanded arrays that depend on such an input are differentiated.  Its gradients equal mpc_rollout's
+    torch graph on the expansion bit for bit.
+    backward="fused": one call of tpc_mpc_rollout_compact_exact_backward (MpcSolver.rollout_compact_exact_backward) on
+    torch's current stream, which does not materialise the general form either: the reverse sweep over the steps on the
+    model built from v, the chain rule folded in the kernel, the shared parameters' gradient summed over the batch on
+    the device in a fixed order and sliced onto the given parameter tensors, x0's gradient from dx0; only the outputs
+    someone needs are requested.  The same gradients to rounding (the sums over the batch and over the targets are
+    taken in another order).  Once-differentiable; no forward mode."""
+    if backward not in ("expanded", "fused"):
+        raise ValueError(f'backward must be "expanded" or "fused", got {backward!r}')
     for t in (v, delta_y, delta_phi) + (() if x0 is None else (x0,)):
         if not (t.is_cuda and t.dtype == torch.float64):
             raise ValueError("mpc_rollout_compact takes CUDA fp64 tensors v, delta_y, delta_phi and x0")
@@ -371,8 +402,8 @@ def mpc_rollout_compact(solver, steps, v, delta_y, delta_phi, weights=None, step
             over[name] = tuple(val) if shape else val
         given.append(t)
     tol, rounds = polish
-    return _MpcRolloutCompact.apply(solver, int(steps), over, (float(tol), int(rounds)), v, delta_y, delta_phi, x0,
-                                    *given)
+    return _MpcRolloutCompact.apply(solver, int(steps), over, (float(tol), int(rounds), backward == "fused"), v,
+                                    delta_y, delta_phi, x0, *given)
 
 
 class CompactWarmStart:

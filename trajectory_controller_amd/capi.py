@@ -49,7 +49,7 @@ EXPORTS = ("tpc_mpc_default_params", "tpc_mpc_create", "tpc_mpc_destroy", "tpc_m
            "tpc_mpc_solve_batch_compact_exact", "tpc_mpc_solve_batch_compact_exact_backward",
            "tpc_mpc_solve_batch_compact_exact_rows", "tpc_mpc_solve_batch_compact_exact_rows_backward",
            "tpc_mpc_solve_batch_compact_exact_from", "tpc_mpc_solve_batch_compact_exact_forward",
-           "tpc_mpc_rollout_compact_exact")
+           "tpc_mpc_rollout_compact_exact", "tpc_mpc_rollout_compact_exact_backward")
 # the shared parameters of tpc_mpc_solve_batch_compact_exact_backward, in the order of its dparams / dparams_rows -- and
 # of the rows of params_rows that the _rows entries take
 COMPACT_PARAM_NAMES = ("weight_y", "weight_phi", "weight_steering_front", "weight_steering_rear", "step_size",
@@ -88,6 +88,13 @@ class CompactGrad(C.Structure):
     """struct tpc_mpc_compact_grad"""
     _fields_ = [("grad_front", C.c_void_p), ("grad_rear", C.c_void_p), ("grad_sequence", C.c_void_p),
                 ("dv", C.c_void_p), ("ddelta_y", C.c_void_p), ("ddelta_phi", C.c_void_p),
+                ("dparams_rows", C.c_void_p), ("dparams", C.c_void_p), ("kkt_residual", C.c_void_p)]
+
+
+class CompactLoopGrad(C.Structure):
+    """struct tpc_mpc_compact_loop_grad"""
+    _fields_ = [("grad_controls", C.c_void_p), ("grad_states", C.c_void_p), ("dv", C.c_void_p),
+                ("ddelta_y", C.c_void_p), ("ddelta_phi", C.c_void_p), ("dx0", C.c_void_p),
                 ("dparams_rows", C.c_void_p), ("dparams", C.c_void_p), ("kkt_residual", C.c_void_p)]
 
 
@@ -218,6 +225,8 @@ def load_library(path: str | None = None) -> C.CDLL:
                                                               vp]
     lib.tpc_mpc_rollout_compact_exact.argtypes = [vp, C.POINTER(Params), C.c_int64, vp, vp, vp, vp, C.c_int32,
                                                   C.POINTER(Polish), C.c_int32, vp, vp, vp, vp, u32p, C.c_int, vp]
+    lib.tpc_mpc_rollout_compact_exact_backward.argtypes = [vp, C.POINTER(Params), C.c_int64, vp, vp, vp, vp, C.c_int32,
+                                                           vp, vp, vp, C.POINTER(CompactLoopGrad), u32p, C.c_int, vp]
     lib.tpc_mpc_rollout_backward.argtypes = [vp, C.POINTER(Params), C.POINTER(GeneralIO), C.c_int32, vp,
                                              C.POINTER(RolloutGrad), u32p, C.c_int, vp]
     lib.tpc_mpc_solve_batch_general_forward.argtypes = [vp, C.POINTER(Params), C.POINTER(GeneralIO), vp,

@@ -9,10 +9,12 @@
 //                                       registers -- no workspace memory is touched
 // The gradients of the ten shared parameters are summed over the batch without floating-point atomics, in an order that
 // depends on n alone: a fixed butterfly over the lanes of a wavefront, the block's wavefronts in order through LDS, one
-// partial row per block with plain stores, and compact_grad_reduce_kernel (one block) over the blocks in a fixed order.
+// partial row per block with plain stores (block_partials, mpc_compact_reduce.h: shared with the compact closed loop's
+// backward pass), and compact_grad_reduce_kernel (one block) over the blocks in a fixed order.
 // Every partial a call reads is one that call wrote.  Explicit fma() only (-ffp-contract=off): device and host path give
 // the same per-instance bits.
 #include "mpc_compact_grad.h"
+#include "mpc_compact_reduce.h"
 
 #include <type_traits>
 #include <vector>
@@ -24,28 +26,7 @@ namespace {
 constexpr int kP = cgrad::kParams;
 constexpr int kReduceBlock = 256;
 
-// the block's sum of every lane's row -> partials[c * gridDim.x + blockIdx.x]; every lane of the block calls it
-__device__ __forceinline__ void block_partials(double (&row)[kP], double* partials) {
-    __shared__ double lds[4][kP];   // a block is at most 4 wavefronts (rollout_grad_block)
-#pragma unroll
-    for (int c = 0; c < kP; ++c) {
-        double x = row[c];
-#pragma unroll
-        for (int mask = 32; mask >= 1; mask >>= 1) x = x + __shfl_xor(x, mask);   // a + b == b + a: every lane the same
-        row[c] = x;
-    }
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0)
-#pragma unroll
-        for (int c = 0; c < kP; ++c) lds[wave][c] = row[c];
-    __syncthreads();
-    if (threadIdx.x < kP) {
-        const int waves = blockDim.x >> 6;
-        double x = lds[0][threadIdx.x];
-        for (int w = 1; w < waves; ++w) x = x + lds[w][threadIdx.x];
-        partials[(int64_t)threadIdx.x * gridDim.x + blockIdx.x] = x;
-    }
-}
+static_assert(kP == kCompactParams, "block_partials (mpc_compact_reduce.h) sums rows of cgrad::kParams");
 
 // partials == null: no reduction, a lane past the batch leaves at once
 template <int HC, bool ROWS = false>
@@ -130,7 +111,11 @@ hipError_t compact_grad(int H, const cgrad::Args& a, void* ws, double* partials,
     else launch(std::false_type{});
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || !dparams) return e;
-    hipLaunchKernelGGL(compact_grad_reduce_kernel, dim3(1), dim3(kReduceBlock), 0, s, part, (int)grid, dparams);
+    return compact_grad_reduce(part, (int)grid, dparams, s);
+}
+
+hipError_t compact_grad_reduce(const double* partials, int blocks, double* dparams, hipStream_t s) {
+    hipLaunchKernelGGL(compact_grad_reduce_kernel, dim3(1), dim3(kReduceBlock), 0, s, partials, blocks, dparams);
     return hipGetLastError();
 }
 

@@ -14,6 +14,7 @@
 #include "mpc_newton_compact.h"
 #include "mpc_compact_loop.h"
 #include "mpc_compact_grad.h"
+#include "mpc_compact_loop_grad.h"
 #include "mpc_compact_tangent.h"
 #include "mpc_tangent_model.h"
 
@@ -2305,6 +2306,82 @@ int tpc_mpc_solve_batch_compact_exact_rows_backward(tpc_mpc_handle h, const tpc_
                                                     uint32_t* flags_out, int mem, void* stream) {
     return compact_exact_backward_impl(h, p, n, v, delta_y, delta_phi, true, params_rows, sequence, status, g,
                                        flags_out, mem, stream);
+}
+
+// The backward pass of the compact closed loop: one launch of the reverse sweep over the steps on the model built from v
+// (mpc_compact_loop_grad.hip), and with dparams the single-block launch that sums the blocks' partial rows
+// (compact_grad_reduce).  One step's workspace (none at the register kernels' horizons) and the partial rows live in the
+// gradient workspace; a one-launch entry like the single solve's backward pass (staged_run).
+int tpc_mpc_rollout_compact_exact_backward(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t n, const void* v,
+                                           const void* delta_y, const void* delta_phi, const void* x0, int32_t steps,
+                                           const void* sequences, const void* states, const int32_t* status,
+                                           const tpc_mpc_compact_loop_grad* g, uint32_t* flags_out, int mem,
+                                           void* stream) {
+    return guarded(h, [&]() -> int {
+        int rc = check_common(h, p, true);
+        if (rc) return rc;
+        if (p->dtype != TPC_MPC_F64) return fp64_only(h, "tpc_mpc_rollout_compact_exact_backward");
+        rc = check_compact_model(h, p);
+        if (rc) return rc;
+        rc = check_batch(h, n, mem);
+        if (rc) return rc;
+        if (!g) return fail(h, TPC_MPC_ERR_BAD_ARG, "null gradient struct");
+        rc = check_steps(h, steps);
+        if (rc) return rc;
+        if (h->host_only && mem == TPC_MPC_DEVICE)
+            return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): the backward pass takes HOST memory only");
+        const bool host = mem == TPC_MPC_HOST;
+        constexpr int kP = cloopgrad::kParams;
+        if (n == 0 || steps == 0) {
+            if (g->dparams) {
+                if (host) {
+                    std::memset(g->dparams, 0, kP * 8);
+                } else {
+                    HIP_TRY(h, hipSetDevice(h->device));
+                    HIP_TRY(h, hipMemsetAsync(g->dparams, 0, kP * 8, (hipStream_t)stream));
+                }
+            }
+            if (flags_out) *flags_out = 0;
+            return TPC_MPC_OK;
+        }
+        if (!v || !delta_y || !delta_phi) return fail(h, TPC_MPC_ERR_BAD_ARG, "null batch pointer");
+        if (!sequences || !states) return fail(h, TPC_MPC_ERR_BAD_ARG, "null sequences / states");
+        const int H = p->horizon;
+        const int64_t S = steps;
+        // the arrays in order: 9 inputs (x0, status -- int32 -- and the upstream gradients may be null), then 7 outputs;
+        // dparams is one row of kP sums, not one element per instance
+        constexpr int kIn = 9, kOut = 7;
+        const void* src[kIn] = {v, delta_y, delta_phi, x0, sequences, states, status, g->grad_controls, g->grad_states};
+        void* dst[kOut] = {g->dv, g->ddelta_y, g->ddelta_phi, g->dx0, g->dparams_rows, g->kkt_residual, g->dparams};
+        const int64_t comps[kIn + kOut] = {1, 1, 1, 2, S * H * 2, S * 2, S, S * 2, S * 2, 1, 1, 1, 2, kP, 1, 1};
+        int width[kIn + kOut] = {0};
+        width[6] = 4;
+        int64_t elems[kIn + kOut] = {0};
+        elems[kIn + 6] = kP;
+        StagedExtra x;
+        x.width = width;
+        x.elems = elems;
+        // the gradient workspace: one step's slots, then the blocks' partial rows
+        const int64_t ws_b = pad256(cloop_grad_scratch_bytes(H, n));
+        const int64_t part_b = g->dparams ? pad256(kP * cloop_grad_blocks(n) * 8) : 0;
+        return staged_run(h, n, n, mem, stream, flags_out, ws_b + part_b, src, dst, comps,
+                          [&](int64_t ld, const void* const* in, void* const* out, hipStream_t s, uint32_t* hf) {
+                              cloopgrad::Args a;
+                              std::memset(&a, 0, sizeof(a));
+                              a.n = n; a.ld = ld; a.steps = steps;
+                              bind_compact_model(&a, p);
+                              a.v = (const double*)in[0]; a.dy = (const double*)in[1]; a.dphi = (const double*)in[2];
+                              a.x0 = (const double*)in[3]; a.seq = (const double*)in[4];
+                              a.states = (const double*)in[5]; a.status = (const int32_t*)in[6];
+                              a.gu = (const double*)in[7]; a.gx = (const double*)in[8];
+                              a.dv = (double*)out[0]; a.ddy = (double*)out[1]; a.ddphi = (double*)out[2];
+                              a.dx0 = (double*)out[3]; a.rows = (double*)out[4]; a.kkt = (double*)out[5];
+                              if (hf) { *hf = cloop_grad_host(H, a, (double*)out[6]); return hipSuccess; }
+                              double* partials = out[6] ? (double*)((char*)h->grad_ws + ws_b) : nullptr;
+                              return cloop_grad(H, a, h->grad_ws, partials, (double*)out[6], h->ws_words + 1, s);
+                          },
+                          x);
+    });
 }
 
 // The forward mode of the exact compact solve: one launch, one lane per (direction, instance), of the tangent sweep on

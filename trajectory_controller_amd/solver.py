@@ -670,8 +670,8 @@ class MpcSolver:
         phase 1 stopped at, `steps` for an instance it carried through -- both None with want_status=False, which with
         fallback="none" also leaves last_flags at 0 and keeps a DEVICE call asynchronous.  residuals: optionally a pair
         of fp64 arrays [steps, n] of the inputs' kind that receive residual_in and residual_out of every (step,
-        instance).  sequences and states are what rollout_backward takes on the expanded arrays (autograd:
-        mpc_rollout_compact)."""
+        instance).  sequences and states are what rollout_compact_exact_backward takes, and rollout_backward on the
+        expanded arrays (autograd: mpc_rollout_compact)."""
         p = self._params(**over)
         H, S = p.horizon, int(steps)
         ar = Arrays(v)
@@ -688,6 +688,45 @@ class MpcSolver:
                   capi.NEWTON_FALLBACKS[fallback], ar.addr(c_out), ar.addr(s_out), ar.addr(q_out), ar.addr(first),
                   want_flags=want_status or fallback != "none")
         return c_out, s_out, q_out, status, first
+
+    COMPACT_LOOP_GRAD_NAMES = ("v", "delta_y", "delta_phi", "x0", "params", "params_rows", "kkt_residual")
+
+    def rollout_compact_exact_backward(self, steps: int, v, delta_y, delta_phi, x0=None, *, sequences, states,
+                                       status=None, grad_controls=None, grad_states=None,
+                                       want=("v", "delta_y", "delta_phi", "x0", "params"), want_flags: bool = True,
+                                       **over):
+        """Backward pass of rollout_compact_exact (tpc_mpc_rollout_compact_exact_backward), fp64 only: the gradient
+        of a loss of the loop's controls and states, taken at what rollout_compact_exact returned (`sequences`
+        [steps*H*2, n], `states` [steps*2, n]) -- one launch over all steps, no general form.
+
+        Arrays as in rollout_compact_exact (numpy: HOST memory, CUDA tensors: DEVICE memory on the current stream):
+        v, delta_y, delta_phi [n], x0 [2, n] or None (zeros), `status` (int32 [steps, n], optional: an instance with a
+        negative status at any step is excluded).  grad_controls / grad_states [steps*2, n] are dL/d(controls) /
+        dL/d(states) (None: zero).  Returns a dict keyed by `want`: "v", "delta_y", "delta_phi" [n], "x0" [2, n] (also
+        without an x0: the gradient at the zero start), "params" [10] (the gradient of the shared parameters in the
+        order of COMPACT_PARAM_NAMES, summed over the batch on the device in a fixed order, the same bytes on every
+        call), "params_rows" [10, n] (per instance) and "kkt_residual" [n] (max over the steps).  Excluded instances
+        (negative status, non-finite data: last_flags) get zeros and add nothing to "params"; want_flags=False leaves
+        last_flags at 0 and keeps a DEVICE call asynchronous."""
+        p = self._params(**over)
+        H, S = p.horizon, int(steps)
+        unknown = set(want) - set(self.COMPACT_LOOP_GRAD_NAMES)
+        if unknown:
+            raise ValueError(f"unknown gradient names {sorted(unknown)}")
+        ar = Arrays(v)
+        NP = len(COMPACT_PARAM_NAMES)
+        rows = {"params_rows": NP, "x0": 2}
+        out = {k: ar.new(NP, per_instance=False) if k == "params" else ar.new(rows[k]) if k in rows else ar.new()
+               for k in self.COMPACT_LOOP_GRAD_NAMES if k in want}
+        to = {k: ar.addr(a) for k, a in out.items()}
+        g = capi.CompactLoopGrad(grad_controls=ar.read(grad_controls, S * 2), grad_states=ar.read(grad_states, S * 2),
+                                 dv=to.get("v"), ddelta_y=to.get("delta_y"), ddelta_phi=to.get("delta_phi"),
+                                 dx0=to.get("x0"), dparams_rows=to.get("params_rows"), dparams=to.get("params"),
+                                 kkt_residual=to.get("kkt_residual"))
+        self._run(self._lib.tpc_mpc_rollout_compact_exact_backward, p, ar, ar.n, ar.read(v), ar.read(delta_y),
+                  ar.read(delta_phi), ar.read(x0, 2), S, ar.read(sequences, S * H * 2), ar.read(states, S * 2),
+                  ar.read(status, S, dtype=_I32), C.byref(g), want_flags=want_flags)
+        return out
 
     ROLLOUT_GRAD_NAMES = GRAD_NAMES[:-1] + ("new_last_targets", "kkt_residual")
     PLANT_GRAD_NAMES = ("Ap", "Bp", "Cp", "disturbance")
