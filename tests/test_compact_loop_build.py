@@ -4,7 +4,7 @@ and no dynamic stack, and at most 256 VGPRs and AGPRs -- the register kernels (h
 keep the whole step loop in registers, and the step loop of none costs registers beyond one step's (DESIGN.md section
 24).  The movers (gather-expand, and the row mover shared with tpc_mpc_rollout_newton) use no private memory either.
 
-Measured on this code: 141 VGPRs at H = 4, 157 at H = 5, 84 for the workspace kernel, 46 for gather-expand."""
+Measured on this code: 141 VGPRs at H = 4, 157 at H = 5, 84 for the workspace kernel, 40 for gather-expand."""
 import os
 
 import pytest

@@ -137,6 +137,14 @@ def test_everybody_falls_back_without_rounds(H, n):
     assert fell.all() and np.all(got["first"] == 0)
 
 
+# ... and from HOST arrays: the staged slots go through gather, the polished loop and scatter with every instance queued
+@pytest.mark.parametrize("n", [1, 64, 65])
+@pytest.mark.parametrize("H", [4, 7])
+def test_everybody_falls_back_without_rounds_from_host_arrays(H, n):
+    got, fell, _ = _check_fallback(H, 3, n, "default", False, rounds=0, bad=False)
+    assert fell.all() and np.all(got["first"] == 0)
+
+
 def test_auto_fallback_agrees_with_the_lane_fallback():
     H, S, n = 10, 10, 4096
     v, dy, dphi, x0, invalid = _inputs(H, n, True)

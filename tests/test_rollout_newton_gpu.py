@@ -254,11 +254,13 @@ def test_nobody_falls_back(device):
     assert a[9].tobytes() == a[8].tobytes() == a[2][(S - 1) * H * I:].tobytes()
 
 
+@pytest.mark.parametrize("n", [1, 64, 65, 150])
 @pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
-def test_everybody_falls_back(device):
+def test_everybody_falls_back(device, n):
     """max_rounds = 0 with a cold start: nothing verifies at step 0, so FALLBACK_SOLVE is rollout_polished on the whole
-    batch, bit for bit, and FALLBACK_NONE is status -1 and zeros throughout."""
-    I, H, S, n = 2, 10, 4, 150
+    batch, bit for bit, and FALLBACK_NONE is status -1 and zeros throughout.  n: a single live lane, a full wavefront,
+    one instance past it (the compact batch's leading dimension steps from 64 to 128), and more than two."""
+    I, H, S = 2, 10, 4
     th, nlt = inputs("general", I, H, S, n=n)
     ins, nl = soa_inputs(th, nlt, n)
     with MpcSolver(horizon=H, device=0, algo="lane") as s:

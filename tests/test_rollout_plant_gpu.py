@@ -113,6 +113,16 @@ def test_fallback_equals_the_polished_plant_loop(I, H, algo):
         assert (all_fb[5] == 0).all()
         for i in range(5):
             assert same_bits(all_fb[i], pol0[i])
+        # ... and at a single live lane, a full wavefront, and one instance past it (the compact batch's leading
+        # dimension steps from 64 to 128)
+        for m in (1, 64, 65):
+            ins, nl, (plant, dist) = _case(I, H, S, m)
+            pol0 = s.rollout_polished(S, *ins, nl, inputs=I, tol=TOL, max_rounds=0, want_iters=True, plant=plant,
+                                      disturbance=dist)
+            all_fb, _ = _newton(s, I, S, ins, nl, plant, dist, fallback="solve", max_rounds=0)
+            assert (all_fb[5] == 0).all(), m
+            for i in range(5):
+                assert same_bits(all_fb[i], pol0[i]), m
 
 
 def _composed(s, I, H, S, ins, nlt, plant, dist, polished, **over):

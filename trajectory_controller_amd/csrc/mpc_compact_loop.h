@@ -4,19 +4,14 @@
 
 #include "mpc_internal.h"
 #include "mpc_compact_loop_model.h"
+#include "mpc_newton_fallback.h"
 
 namespace tpc {
 
-// The fallback's compact batch: instance index[j] of the call <-> column j, leading dimension ld.  Gather-expand
-// writes the general form of those instances -- the model as cexact::build_model makes it, the call's x0 (zeros without
-// one) and H copies of the target -- for the polished loop (rollout_impl), which starts from no carried controls
-// itself; its per-step rows go back through rollout_newton_move.
-struct CompactLoopBatch {
-    int64_t count, ld;
-    const int32_t* index;
-    int H;
-    double *A, *B, *C, *Q, *R, *lo, *hi, *x0, *targets;
-};
+// The fallback's compact batch.  Gather-expand writes the general form of the queued instances -- the model as
+// cexact::build_model makes it, the call's x0 (zeros without one) and H copies of the target -- for the polished loop
+// (rollout_impl), which starts from no carried controls itself; its per-step rows go back through rollout_newton_move.
+using CompactLoopBatch = FallbackBatch;
 
 // true: a kernel with the horizon at compile time and the whole loop in registers serves H
 bool compact_loop_in_registers(int H);

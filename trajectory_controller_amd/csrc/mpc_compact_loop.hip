@@ -7,10 +7,10 @@
 //   compact_loop_reg_kernel<HC>   the reference's horizons 4 and 5: the horizon at compile time, every loop over it
 //                                 unrolled, the per-step values in an array of the lane's own that the compiler keeps
 //                                 in registers -- the whole loop touches no workspace memory
-// The instances phase 1 stopped as "not verified" are collected for the fallback (one atomicAdd per wavefront, as
-// mpc_newton_compact.hip); gather-expand writes their general form, x0 included, into a compact batch for the polished
-// loop, whose rows rollout_newton_move scatters back.  Explicit fma() only (-ffp-contract=off): device and host path
-// give the same bits, and both equal tpc_mpc_rollout_newton on the expanded arrays.
+// The instances phase 1 stopped as "not verified" are queued for the fallback (mpc_newton_fallback.h); gather-expand
+// writes their general form, x0 included, into a compact batch for the polished loop, whose rows rollout_newton_move
+// scatters back (the two phases: newton_two_phase, tpc_mpc_api.cpp).  Explicit fma() only (-ffp-contract=off): device
+// and host path give the same bits, and both equal tpc_mpc_rollout_newton on the expanded arrays.
 #include "mpc_compact_loop.h"
 
 #include <vector>
@@ -22,18 +22,10 @@ namespace {
 // What a lane does with its instance's result: first_unverified, the flags and its place in the fallback's queue
 __device__ __forceinline__ void loop_finish(const cloop::Args& a, int64_t k, uint32_t f, int32_t first, uint32_t* flags) {
     if (a.first) a.first[k] = first;
-    const uint32_t raise = a.c.raise_not_polished ? f : (f & ~0x8u);
+    const cexact::Args& c = a.c;   // the single solve's arguments hold the queue
+    const uint32_t raise = raised_flags(c.raise_not_polished, f);
     if (raise) atomicOr(flags, raise);
-    if (!a.c.fb_index) return;
-    // the fallback's queue: not verified, and nothing else wrong with the instance
-    const bool fb = f == 0x8u;
-    const unsigned long long m = __ballot(fb);
-    if (!m) return;
-    const int lane = __lane_id(), leader = __ffsll((long long)m) - 1;
-    uint32_t base = 0;
-    if (lane == leader) base = atomicAdd(a.c.fb_count, (uint32_t)__popcll(m));
-    base = __shfl(base, leader);
-    if (fb) a.c.fb_index[base + __popcll(m & ((1ull << lane) - 1ull))] = (int32_t)k;
+    fallback_enqueue(c.fb_index, c.fb_count, k, f);
 }
 
 __global__ __launch_bounds__(256) void compact_loop_ws_kernel(cloop::Args a, int H, double* ws, uint32_t* flags) {
@@ -57,17 +49,9 @@ __global__ __launch_bounds__(256) void compact_loop_reg_kernel(cloop::Args a, ui
 __global__ __launch_bounds__(256) void compact_loop_gather_kernel(cloop::Args a, CompactLoopBatch b) {
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= b.count) return;
-    const int64_t k = b.index[j], ld = b.ld;
+    const int64_t k = b.index[j];
     const grad::Model m = cexact::build_model(a.c, a.c.v[k]);
-    const double tg0 = a.c.dy[k], tg1 = a.c.dphi[k];
-    auto out = [&](double* base, int c, double x) { base[(int64_t)c * ld + j] = x; };
-    out(b.A, 0, m.a00); out(b.A, 1, m.a01); out(b.A, 2, m.a10); out(b.A, 3, m.a11);
-    out(b.B, 0, m.b0[0]); out(b.B, 1, m.b0[1]); out(b.B, 2, m.b1[0]); out(b.B, 3, m.b1[1]);
-    out(b.C, 0, m.c0); out(b.C, 1, m.c1);
-    out(b.Q, 0, m.q0); out(b.Q, 1, m.q1);
-    out(b.x0, 0, a.x0 ? a.x0[k] : 0.0); out(b.x0, 1, a.x0 ? a.x0[a.ld_x0 + k] : 0.0);
-    for (int c = 0; c < 2; ++c) { out(b.R, c, m.r[c]); out(b.lo, c, m.lo[c]); out(b.hi, c, m.hi[c]); }
-    for (int t = 0; t < b.H; ++t) { out(b.targets, 2 * t, tg0); out(b.targets, 2 * t + 1, tg1); }
+    expand_general(m, a.c.dy[k], a.c.dphi[k], a.x0 ? a.x0[k] : 0.0, a.x0 ? a.x0[a.ld_x0 + k] : 0.0, b, j);
 }
 
 }  // namespace
@@ -95,7 +79,7 @@ uint32_t compact_loop_host(int H, const cloop::Args& a) {
         int32_t first;
         const uint32_t f = cloop::loop_instance<0>(a, H, k, ws.data(), 1, &first);
         if (a.first) a.first[k] = first;
-        flags |= a.c.raise_not_polished ? f : (f & ~0x8u);
+        flags |= raised_flags(a.c.raise_not_polished, f);
     }
     return flags;
 }

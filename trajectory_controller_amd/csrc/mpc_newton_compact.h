@@ -4,18 +4,16 @@
 
 #include "mpc_internal.h"
 #include "mpc_newton_compact_model.h"
+#include "mpc_newton_fallback.h"
 
 namespace tpc {
 
-// The fallback's compact batch: instance index[j] of the call <-> column j, leading dimension ld.  Gather-expand
-// writes the general form of those instances (the model as cexact::build_model makes it, x0 = 0, H copies of the
+// The fallback's compact batch (FallbackBatch) and what the solve and the polish return for it.  Gather-expand writes
+// the general form of the queued instances (the model as cexact::build_model makes it, x0 = 0, H copies of the
 // target, zero controls); scatter reads what the solve and the polish left and writes the call's outputs (src's
 // output pointers, null where the caller gave none) with fell_back = 1.
-struct CompactExactBatch {
-    int64_t count, ld;
-    const int32_t* index;
-    int H;
-    double *A, *B, *C, *Q, *R, *lo, *hi, *x0, *targets, *controls, *u0, *res_in, *res_out;
+struct CompactExactBatch : FallbackBatch {
+    double *controls, *u0, *res_in, *res_out;
     int32_t* status;
 };
 

@@ -11,10 +11,11 @@
 // starts from its column of Args::start (one pass: load, clamp, track finiteness; a non-finite column is rewritten with
 // the cold start).  Each of the twelve instantiations is a kernel of its own: the cold entries' code objects do not
 // depend on the warm ones.
-// The instances phase 1 could not verify are collected for the fallback (one atomicAdd per wavefront, as
-// mpc_rollout_newton.hip); gather-expand writes their general form into a compact batch for tpc_mpc_solve_batch_general
-// and tpc_mpc_polish_batch_general, scatter brings the results back.  Explicit fma() only (-ffp-contract=off): device and
-// host path give the same bits, and both equal tpc_mpc_polish_batch_general on the expanded arrays.
+// The instances phase 1 could not verify are queued for the fallback (mpc_newton_fallback.h); gather-expand writes
+// their general form into a compact batch for tpc_mpc_solve_batch_general and tpc_mpc_polish_batch_general, scatter
+// brings the results back (the two phases: newton_two_phase, tpc_mpc_api.cpp).  Explicit fma() only
+// (-ffp-contract=off): device and host path give the same bits, and both equal tpc_mpc_polish_batch_general on the
+// expanded arrays.
 #include "mpc_newton_compact.h"
 
 #include <type_traits>
@@ -26,18 +27,9 @@ namespace {
 
 // What a lane does with its instance's result: the flags and its place in the fallback's queue
 __device__ __forceinline__ void exact_finish(const cexact::Args& a, int64_t k, uint32_t f, uint32_t* flags) {
-    const uint32_t raise = a.raise_not_polished ? f : (f & ~0x8u);
+    const uint32_t raise = raised_flags(a.raise_not_polished, f);
     if (raise) atomicOr(flags, raise);
-    if (!a.fb_index) return;
-    // the fallback's queue: not verified, and nothing else wrong with the instance
-    const bool fb = f == 0x8u;
-    const unsigned long long m = __ballot(fb);
-    if (!m) return;
-    const int lane = __lane_id(), leader = __ffsll((long long)m) - 1;
-    uint32_t base = 0;
-    if (lane == leader) base = atomicAdd(a.fb_count, (uint32_t)__popcll(m));
-    base = __shfl(base, leader);
-    if (fb) a.fb_index[base + __popcll(m & ((1ull << lane) - 1ull))] = (int32_t)k;
+    fallback_enqueue(a.fb_index, a.fb_count, k, f);
 }
 
 template <bool ROWS, bool WARM>
@@ -70,22 +62,12 @@ void with_entry(const cexact::Args& a, F f) {
 __global__ __launch_bounds__(256) void compact_exact_gather_kernel(cexact::Args a, CompactExactBatch b) {
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= b.count) return;
-    const int64_t k = b.index[j], ld = b.ld;
+    const int64_t k = b.index[j];
     // a.params != null (uniform over the launch): the rows entry, the instance's own ten values
     const grad::Model m = a.params ? cexact::build_model(cexact::instance_params<true>(a, k), a.v[k])
                                    : cexact::build_model(a, a.v[k]);
-    const double tg0 = a.dy[k], tg1 = a.dphi[k];
-    auto out = [&](double* base, int c, double x) { base[(int64_t)c * ld + j] = x; };
-    out(b.A, 0, m.a00); out(b.A, 1, m.a01); out(b.A, 2, m.a10); out(b.A, 3, m.a11);
-    out(b.B, 0, m.b0[0]); out(b.B, 1, m.b0[1]); out(b.B, 2, m.b1[0]); out(b.B, 3, m.b1[1]);
-    out(b.C, 0, m.c0); out(b.C, 1, m.c1);
-    out(b.Q, 0, m.q0); out(b.Q, 1, m.q1);
-    out(b.x0, 0, 0.0); out(b.x0, 1, 0.0);
-    for (int c = 0; c < 2; ++c) { out(b.R, c, m.r[c]); out(b.lo, c, m.lo[c]); out(b.hi, c, m.hi[c]); }
-    for (int t = 0; t < b.H; ++t) {
-        out(b.targets, 2 * t, tg0); out(b.targets, 2 * t + 1, tg1);
-        out(b.controls, 2 * t, 0.0); out(b.controls, 2 * t + 1, 0.0);
-    }
+    expand_general(m, a.dy[k], a.dphi[k], 0.0, 0.0, b, j);
+    for (int c = 0; c < 2 * b.H; ++c) b.controls[(int64_t)c * b.ld + j] = 0.0;
 }
 
 __global__ __launch_bounds__(256) void compact_exact_scatter_kernel(cexact::Args a, CompactExactBatch b) {
@@ -130,7 +112,7 @@ uint32_t compact_exact_host(int H, const cexact::Args& a) {
         constexpr bool R = decltype(rows)::value, W = decltype(warm)::value;
         for (int64_t k = 0; k < a.n; ++k) {
             const uint32_t f = cexact::exact_instance<0, R, W>(a, H, k, ws.data(), 1);
-            flags |= a.raise_not_polished ? f : (f & ~0x8u);
+            flags |= raised_flags(a.raise_not_polished, f);
         }
     });
     return flags;

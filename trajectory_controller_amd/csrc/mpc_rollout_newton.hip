@@ -7,9 +7,11 @@
 // polish_instance reads its start from (its working copy in the workspace is rebuilt from it at every call).
 // Explicit fma() only (-ffp-contract=off), so a verified step equals tpc_mpc_polish_batch_general on the shifted
 // sequence followed by rollout_step_kernel bit for bit, on the device and on the host path below.
-// The instances that stopped with "not polished" are collected for the fallback (one atomicAdd per wavefront); two
-// small kernels move their rows into and out of the compact batch tpc_mpc_rollout_polished's loop then runs.
+// The instances that stopped with "not polished" are queued for the fallback (mpc_newton_fallback.h); two small kernels
+// move their rows into and out of the compact batch that tpc_mpc_rollout_polished's loop then runs.  How the two phases
+// fit together is said once, at newton_two_phase (tpc_mpc_api.cpp).
 #include "mpc_rollout_newton.h"
+#include "mpc_newton_fallback.h"
 #include "mpc_rollout_step.h"
 
 #include <vector>
@@ -86,21 +88,12 @@ TPC_GRAD_HD uint32_t newton_instance(const NewtonArgs& a, int64_t k, double* ws0
 }
 
 // What a lane does with its instance's result: first_unverified, the flags, and its place in the fallback's queue
-// (one atomicAdd per wavefront).  Shared by the two kernels below.
+// (mpc_newton_fallback.h).  Shared by the two kernels below.
 __device__ __forceinline__ void newton_finish(const NewtonArgs& a, int64_t k, uint32_t f, int32_t first, uint32_t* flags) {
     a.first_unverified[k] = first;
-    const uint32_t raise = a.raise_not_polished ? f : (f & ~0x8u);
+    const uint32_t raise = raised_flags(a.raise_not_polished, f);
     if (raise) atomicOr(flags, raise);
-    if (!a.fb_index) return;
-    // the fallback's queue: not polished, and nothing else wrong with the instance
-    const bool fb = f == 0x8u;
-    const unsigned long long m = __ballot(fb);
-    if (!m) return;
-    const int lane = __lane_id(), leader = __ffsll((long long)m) - 1;
-    uint32_t base = 0;
-    if (lane == leader) base = atomicAdd(a.fb_count, (uint32_t)__popcll(m));
-    base = __shfl(base, leader);
-    if (fb) a.fb_index[base + __popcll(m & ((1ull << lane) - 1ull))] = (int32_t)k;
+    fallback_enqueue(a.fb_index, a.fb_count, k, f);
 }
 
 template <int I>
@@ -181,7 +174,7 @@ uint32_t rollout_newton_host(int I, const NewtonArgs& a) {
         else
             f = I == 2 ? newton_instance<2>(a, k, ws.data(), 1, &first) : newton_instance<1>(a, k, ws.data(), 1, &first);
         a.first_unverified[k] = first;
-        flags |= a.raise_not_polished ? f : (f & ~0x8u);
+        flags |= raised_flags(a.raise_not_polished, f);
     }
     return flags;
 }

@@ -517,6 +517,25 @@ int check_host_only_newton(tpc_mpc_context* h, bool solve, int mem) {
         return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): HOST memory only");
     return TPC_MPC_OK;
 }
+// ... and of a one-launch pass ("backward pass", "forward pass", "polish"): DEVICE memory
+int check_host_only_pass(tpc_mpc_context* h, int mem, const char* pass) {
+    if (h->host_only && mem == TPC_MPC_DEVICE)
+        return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): the %s takes HOST memory only", pass);
+    return TPC_MPC_OK;
+}
+// what a compact backward pass returns for an empty batch (or no steps): zero shared-parameter gradients, in `mem`
+int zero_dparams(tpc_mpc_context* h, void* dparams, int count, uint32_t* flags_out, int mem, void* stream) {
+    if (dparams) {
+        if (mem == TPC_MPC_HOST) {
+            std::memset(dparams, 0, (size_t)count * 8);
+        } else {
+            HIP_TRY(h, hipSetDevice(h->device));
+            HIP_TRY(h, hipMemsetAsync(dparams, 0, (size_t)count * 8, (hipStream_t)stream));
+        }
+    }
+    if (flags_out) *flags_out = 0;
+    return TPC_MPC_OK;
+}
 // the ten model values of the compact form into the Args of the exact solve or its backward pass
 template <class Args> void bind_compact_model(Args* a, const tpc_mpc_params* p) {
     a->T = p->step_size; a->l = p->wheelbase; a->q0 = p->weight_y; a->q1 = p->weight_phi;
@@ -1045,11 +1064,161 @@ StepArrays step_arrays(const tpc_mpc_general_io* io, int H, int64_t S, int es, c
     g.t[kStepRout] = staged(q ? q->residual_out : nullptr, kStageOut, S, ld, 8);
     return g;
 }
-// HOST arrays only: the slots, the inputs copied in
-int stage_steps(tpc_mpc_context* h, StepArrays* g, int64_t n, hipStream_t s) {
+// HOST arrays only: the slots' leading dimensions, and with stage_steps the slots and the inputs copied in
+void staged_step_lds(StepArrays* g, int64_t n) {
     g->ld_nlt = g->ld_out = stage_ld(n);
     if (g->t[kStepDist].ptr) g->ld_d = stage_ld(n);
+}
+int stage_steps(tpc_mpc_context* h, StepArrays* g, int64_t n, hipStream_t s) {
+    staged_step_lds(g, n);
     return stage_in(h, g->t, kStepCount, n, s);
+}
+
+// ---- The two phases of the Newton-first entries, once ----
+// tpc_mpc_rollout_newton / _plant, tpc_mpc_solve_batch_compact_exact (_rows, _from) and tpc_mpc_rollout_compact_exact
+// are this frame around what is their own.  Phase 1 is ONE launch that verifies most instances.  With
+// TPC_MPC_NEWTON_FALLBACK_SOLVE its lanes queue the instances they could not verify (mpc_newton_fallback.h); one 4-byte
+// read-back of the queue's length and a synchronise -- the only ones, and only in that mode -- sit between the phases.
+// The queued instances are gathered into a compact batch (h->newton_fb, leading dimension ldc: the count rounded up to
+// a wavefront), run through the general path and scattered back.  What holds the two together, for every entry:
+//   - h->newton is the entry's own working set (ws_bytes), then the queue ([stage_ld(n)] int32) and two words: [0] the
+//     queue's length, [1] phase 1's flags.  Phase 1 gets the queue only with FALLBACK_SOLVE: fb_index is null otherwise,
+//     nothing is queued and "not polished" is raised instead (raised_flags).
+//   - every general entry the fallback calls resets the handle's flag word (h->ws_words + 1).  So phase 1 raises its
+//     flags in word [1], and they are merged into the handle's word after the fallback -- or after that word is zeroed,
+//     when nothing fell back.
+//   - the fallback calls those entries with TPC_MPC_DEVICE and no flags_out: no staging, no synchronise.  So nothing
+//     writes h->stage between phase 1 and the copies back, and the HOST arrays staged there (t) outlive the fallback.
+// A host-only handle never gets here: the entries run phase 1 on the calling thread before anything touches HIP.
+struct NewtonPhase {
+    char* ws;             // h->newton: ws_bytes of the entry's own
+    int32_t* fb_index;    // the queue (in no particular order); null without FALLBACK_SOLVE
+    uint32_t* fb_count;   // word [0]
+    uint32_t* flags;      // word [1]
+    hipStream_t s;
+    bool staged;          // HOST arrays: t[c].dev are slots with the leading dimension stage_ld(n)
+};
+inline int newton_nothing(const NewtonPhase&) { return TPC_MPC_OK; }
+// grad_bytes: what h->grad_ws must hold (0: not grown).  t[count]: the call's arrays, staged when mem is HOST.
+// On the stream, in this order: fill(f) -- the entry's own working set; the words zeroed; the staging copies;
+// phase1(f), the launch; [the read-back]; fallback(f, count, ldc), or the handle's flag word zeroed; the flag merge;
+// back(f) -- copies back that are no staged arrays; the staged copies back and their synchronise; the stream order's
+// event; the flags.
+template <class Fill, class Phase1, class Fallback, class Back>
+int newton_two_phase(tpc_mpc_context* h, int64_t n, bool solve, int mem, void* stream, uint32_t* flags_out,
+                     int64_t ws_bytes, int64_t grad_bytes, StagedArray* t, int count, Fill fill, Phase1 phase1,
+                     Fallback fallback, Back back) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    StreamOrderScope order(h, s);
+    int rc = order.begin();
+    if (rc) return rc;
+    const bool host = mem == TPC_MPC_HOST;
+    const int64_t o_words = ws_bytes + stage_ld(n) * 4;
+    rc = ensure(h, &h->newton, &h->newton_bytes, o_words + 256);
+    if (!rc && grad_bytes > 0) rc = ensure(h, &h->grad_ws, &h->grad_ws_bytes, pad256(grad_bytes));
+    if (rc) return rc;
+    char* w = (char*)h->newton;
+    uint32_t* d_words = (uint32_t*)(w + o_words);
+    const NewtonPhase f{w, solve ? (int32_t*)(w + ws_bytes) : nullptr, d_words, d_words + 1, s, host};
+    rc = fill(f);
+    if (rc) return rc;
+    HIP_TRY(h, hipMemsetAsync(d_words, 0, 8, s));
+    if (host) {
+        rc = stage_in(h, t, count, n, s);
+        if (rc) return rc;
+    }
+    hipError_t e = phase1(f);
+    if (e != hipSuccess) return hip_fail(h, e, "kernel launch");
+
+    uint32_t queued = 0;
+    if (solve) {
+        HIP_TRY(h, hipMemcpyAsync(&queued, d_words, sizeof(queued), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+    }
+    if (queued > 0) {
+        rc = fallback(f, (int64_t)queued, stage_ld(queued));
+        if (rc) return rc;
+    } else {
+        HIP_TRY(h, hipMemsetAsync(h->ws_words + 1, 0, sizeof(uint32_t), s));
+    }
+    e = rollout_newton_merge_flags(h->ws_words + 1, f.flags, s);
+    if (e != hipSuccess) return hip_fail(h, e, "flag merge launch");
+
+    rc = back(f);
+    if (!rc && host) rc = stage_out(h, t, count, n, s);
+    if (!rc) rc = order.end();
+    if (rc) return rc;
+    return finish_flags(h, flags_out, s);
+}
+
+// Rows of the compact batch in h->newton_fb, leading dimension ldc: fp64 rows first, in the order taken, the int32 rows
+// (iters, status) behind them.  take() before reserve(), at() / at32() after.
+struct FallbackRows {
+    int64_t ldc, total = 0;
+    char* fb = nullptr;
+    explicit FallbackRows(int64_t ld) : ldc(ld) {}
+    // an array of `rows` fp64 rows: its first row, or -1 when it is not there (it then takes none)
+    int64_t take(bool there, int64_t rows) { const int64_t at = total; if (there) total += rows; return there ? at : -1; }
+    // grows h->newton_fb to the fp64 rows taken and rows32 int32 rows
+    int reserve(tpc_mpc_context* h, int64_t rows32) {
+        const int rc = ensure(h, &h->newton_fb, &h->newton_fb_bytes, total * ldc * 8 + rows32 * ldc * 4);
+        fb = (char*)h->newton_fb;
+        return rc;
+    }
+    double* at(int64_t row) const { return row < 0 ? nullptr : (double*)(fb + row * ldc * 8); }
+    int32_t* at32(bool there, int64_t row32) const { return there ? (int32_t*)(fb + total * ldc * 8 + row32 * ldc * 4) : nullptr; }
+};
+
+// The general form of `count` queued instances from the batch's rows: the nine model arrays at row[0..8], the io's order
+tpc_mpc_general_io fallback_io(const FallbackRows& L, int I, int64_t count, const int64_t* row) {
+    tpc_mpc_general_io io{};
+    io.inputs = I; io.n = count; io.ld = L.ldc;
+    io.A = L.at(row[0]); io.B = L.at(row[1]); io.C = L.at(row[2]); io.Q = L.at(row[3]); io.R = L.at(row[4]);
+    io.lower = L.at(row[5]); io.upper = L.at(row[6]); io.x0 = L.at(row[7]); io.targets = L.at(row[8]);
+    return io;
+}
+// ... of the compact entries (I = 2): the 20 + 2H model rows from `first` on, as the gather-expand kernels' batch and
+// as the io
+constexpr int64_t compact_model_rows(int H) { return 20 + 2 * (int64_t)H; }
+tpc_mpc_general_io fallback_compact_model(const FallbackRows& L, int64_t first, int H, int64_t count,
+                                          const int32_t* index, FallbackBatch* b) {
+    const int64_t comps[9] = {4, 4, 2, 2, 2, 2, 2, 2, 2 * (int64_t)H};
+    int64_t row[9];
+    for (int c = 0; c < 9; ++c) { row[c] = first; first += comps[c]; }
+    const tpc_mpc_general_io io = fallback_io(L, 2, count, row);
+    b->count = count; b->ld = L.ldc; b->index = index; b->H = H;
+    b->A = (double*)io.A; b->B = (double*)io.B; b->C = (double*)io.C; b->Q = (double*)io.Q; b->R = (double*)io.R;
+    b->lo = (double*)io.lower; b->hi = (double*)io.upper; b->x0 = (double*)io.x0; b->targets = (double*)io.targets;
+    return io;
+}
+
+// The per-step outputs of a polished loop (null: not asked for): the caller's, or their rows in the compact batch
+struct StepOutputs {
+    void *ctrl, *states, *seq, *rin, *rout;
+    int32_t *iters, *status;
+};
+// their rows in the compact batch, taken for those of `d` that are there (controls always are) ...
+struct StepRows { int64_t ctrl, states, seq, rin, rout; };
+StepRows take_step_rows(FallbackRows* L, const StepOutputs& d, int I, int H, int64_t S) {
+    const int64_t ctrl = L->take(true, S * I), states = L->take(d.states, S * 2), seq = L->take(d.seq, S * H * I);
+    return StepRows{ctrl, states, seq, L->take(d.rin, S), L->take(d.rout, S)};
+}
+// ... as pointers, once the batch is reserved; the int32 rows: iters (`with_iters`: S rows, there or not), then status
+StepOutputs step_outputs_at(const FallbackRows& L, const StepRows& r, const StepOutputs& d, int64_t S, bool with_iters) {
+    return StepOutputs{L.at(r.ctrl), L.at(r.states), L.at(r.seq), L.at(r.rin), L.at(r.rout),
+                       L.at32(with_iters && d.iters, 0), L.at32(d.status, with_iters ? S : 0)};
+}
+// ... and the table that scatters them from the compact batch (f, ldc) to the caller's (d, ld_out)
+NewtonMove step_scatter(int64_t count, const int32_t* index, const StepOutputs& f, const StepOutputs& d, int I, int H,
+                        int64_t S, int64_t ldc, int64_t ld_out) {
+    NewtonMove sc{count, index, 0, {}};
+    auto add = [&](const void* src, void* dst, int64_t rows, int bytes) {
+        if (dst) sc.set[sc.sets++] = NewtonRows{src, dst, rows, ldc, ld_out, bytes};
+    };
+    add(f.ctrl, d.ctrl, S * I, 8); add(f.states, d.states, S * 2, 8); add(f.seq, d.seq, S * H * I, 8);
+    add(f.rin, d.rin, S, 8); add(f.rout, d.rout, S, 8); add(f.iters, d.iters, S, 4); add(f.status, d.status, S, 4);
+    return sc;
 }
 
 // tpc_mpc_solve_batch_compact's arrays as a staging table: v, dy, dphi in, front and rear out in the solve's
@@ -1386,8 +1555,8 @@ int tpc_mpc_solve_batch_general_backward(tpc_mpc_handle h, const tpc_mpc_params*
         rc = check_general_io(h, io, mem);
         if (rc) return rc;
         if (!g) return fail(h, TPC_MPC_ERR_BAD_ARG, "null gradient struct");
-        if (h->host_only && mem == TPC_MPC_DEVICE)
-            return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): the backward pass takes HOST memory only");
+        rc = check_host_only_pass(h, mem, "backward pass");
+        if (rc) return rc;
         if (io->n == 0) { if (flags_out) *flags_out = 0; return TPC_MPC_OK; }
         rc = check_model(h, io);
         if (rc) return rc;
@@ -1427,8 +1596,8 @@ int tpc_mpc_polish_batch_general(tpc_mpc_handle h, const tpc_mpc_params* p, cons
         if (rc) return rc;
         rc = check_polish(h, q);
         if (rc) return rc;
-        if (h->host_only && mem == TPC_MPC_DEVICE)
-            return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): the polish takes HOST memory only");
+        rc = check_host_only_pass(h, mem, "polish");
+        if (rc) return rc;
         if (io->n == 0) { if (flags_out) *flags_out = 0; return TPC_MPC_OK; }
         rc = check_model(h, io);
         if (rc) return rc;
@@ -1630,10 +1799,9 @@ int tpc_mpc_rollout_record(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_
                         false, nullptr, flags_out, mem, stream);
 }
 
-// The Newton-first closed loop (include/tpc_mpc.h): phase 1 is ONE launch for the whole loop (mpc_rollout_newton.hip);
-// with TPC_MPC_NEWTON_FALLBACK_SOLVE the instances it could not verify are gathered into a compact batch, run through
-// rollout_impl's polished mode from step 0 and scattered back.  One 4-byte read-back (the fallback's count) sits between
-// the phases; a host-only handle runs phase 1 on the calling thread.
+// The Newton-first closed loop (include/tpc_mpc.h) on newton_two_phase: phase 1 is ONE launch for the whole loop
+// (mpc_rollout_newton.hip); the fallback is rollout_impl's polished mode from step 0 on the gathered rows of the
+// working set.  A host-only handle runs phase 1 on the calling thread.
 // (plant: tpc_mpc_rollout_plant, which has checked it; null: tpc_mpc_rollout_newton)
 static int rollout_newton_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_mpc_general_io* io, int32_t steps,
                                const void* new_last_targets, const tpc_mpc_polish* q, int32_t fallback,
@@ -1717,145 +1885,94 @@ static int rollout_newton_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const 
             return TPC_MPC_OK;
         }
 
-        HIP_TRY(h, hipSetDevice(h->device));
-        hipStream_t s = (hipStream_t)stream;
-        StreamOrderScope order(h, s);
-        rc = order.begin();
-        if (rc) return rc;
         const bool host = mem == TPC_MPC_HOST;
         const hipMemcpyKind in_kind = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
         const hipMemcpyKind out_kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-        const int64_t ldw = (n + 63) / 64 * 64;
-        const int64_t o_fu = (rows_in + rows_work) * ldw * 8, o_idx = o_fu + ldw * 4, o_words = o_idx + ldw * 4;
-        rc = ensure(h, &h->newton, &h->newton_bytes, o_words + 256);
-        if (rc) return rc;
-        rc = ensure(h, &h->grad_ws, &h->grad_ws_bytes, pad256(polish_scratch_bytes(I, H, n)));
-        if (rc) return rc;
-        char* w = (char*)h->newton;
-        for (int c = 0; c < 14; ++c) {
-            if (comps[c] == 0) continue;
-            if (src[c]) HIP_TRY(h, copy_rows(w + row[c] * ldw * 8, ldw * 8, src[c], ld * 8, n * 8, comps[c], in_kind, s));
-            else HIP_TRY(h, hipMemsetAsync(w + row[c] * ldw * 8, 0, (size_t)(comps[c] * ldw * 8), s));
-        }
-        HIP_TRY(h, hipMemcpyAsync(w + rows_in * ldw * 8, w + row[7] * ldw * 8, (size_t)(rows_work * ldw * 8),
-                                  hipMemcpyDeviceToDevice, s));
-        int32_t* d_fu = (int32_t*)(w + o_fu);
-        int32_t* d_idx = (int32_t*)(w + o_idx);
-        uint32_t* d_words = (uint32_t*)(w + o_words);   // [0] the fallback's count, [1] phase 1's flags
-        HIP_TRY(h, hipMemsetAsync(d_words, 0, 8, s));
-
+        const int64_t ldw = stage_ld(n), S = steps;
+        const int64_t o_fu = (rows_in + rows_work) * ldw * 8;   // first_unverified's row; the frame's queue follows it
         // the per-step arrays: the kernels take the caller's DEVICE arrays, or the slots of HOST arrays
         StepArrays g = step_arrays(io, H, steps, 8, new_last_targets, plant, controls_out, states_out, iters_out,
                                    sequences_out, q);
-        if (host) {
-            rc = stage_steps(h, &g, n, s);
-            if (rc) return rc;
-        }
-        const void *d_nlt = g.at(kStepNlt), *d_dist = g.at(kStepDist);
-        void *d_ctrl = g.at(kStepCtrl), *d_states = g.at(kStepStates), *d_seq = g.at(kStepSeq);
-        void *d_rin = g.at(kStepRin), *d_rout = g.at(kStepRout);
-        int32_t *d_iters = g.at<int32_t>(kStepIters), *d_status = g.at<int32_t>(kStepStatus);
-        const int64_t ld_nlt = g.ld_nlt, ld_out = g.ld_out, ld_dist = g.ld_d;
+        StepOutputs out{};                               // ... as phase 1 binds them
+        char *d_cfinal = nullptr, *d_vfinal = nullptr;   // the last step's sequence: controls out, and v out
+        return newton_two_phase(
+            h, n, solve, mem, stream, flags_out, o_fu + ldw * 4, polish_scratch_bytes(I, H, n), g.t, kStepCount,
+            [&](const NewtonPhase& f) -> int {   // the working set
+                char* w = f.ws;
+                for (int c = 0; c < 14; ++c) {
+                    if (comps[c] == 0) continue;
+                    if (src[c]) HIP_TRY(h, copy_rows(w + row[c] * ldw * 8, ldw * 8, src[c], ld * 8, n * 8, comps[c], in_kind, f.s));
+                    else HIP_TRY(h, hipMemsetAsync(w + row[c] * ldw * 8, 0, (size_t)(comps[c] * ldw * 8), f.s));
+                }
+                HIP_TRY(h, hipMemcpyAsync(w + rows_in * ldw * 8, w + row[7] * ldw * 8, (size_t)(rows_work * ldw * 8),
+                                          hipMemcpyDeviceToDevice, f.s));
+                return TPC_MPC_OK;
+            },
+            [&](const NewtonPhase& f) {   // phase 1
+                if (f.staged) staged_step_lds(&g, n);
+                out = StepOutputs{g.at(kStepCtrl), g.at(kStepStates), g.at(kStepSeq), g.at(kStepRin), g.at(kStepRout),
+                                  g.at<int32_t>(kStepIters), g.at<int32_t>(kStepStatus)};
+                bind(f.ws, ldw);
+                a.r.ld_out = g.ld_out; a.r.ld_nlt = g.ld_nlt;
+                a.r.new_last_targets = g.at(kStepNlt);
+                a.r.disturbance = g.at(kStepDist); a.r.ld_d = g.ld_d;
+                a.r.controls_out = out.ctrl; a.r.states_out = out.states; a.r.iters_out = out.iters;
+                a.r.sequences_out = out.seq;
+                a.p.status = out.status; a.p.res_in = (double*)out.rin; a.p.res_out = (double*)out.rout;
+                a.first_unverified = (int32_t*)(f.ws + o_fu);
+                a.fb_index = f.fb_index; a.fb_count = f.fb_count;
+                d_cfinal = d_vfinal = f.ws + (rows_in + 2 + 2 * H) * ldw * 8;
+                return rollout_newton(I, a, h->grad_ws, f.flags, f.s);
+            },
+            [&](const NewtonPhase& f, int64_t cnt, int64_t ldc) -> int {   // the fallback: the polished loop from step 0
+                // the compact batch: the rows_in rows of the working set, new_last_targets, every output of the
+                // polished loop, the disturbance
+                const void *d_nlt = g.at(kStepNlt), *d_dist = g.at(kStepDist);
+                FallbackRows L(ldc);
+                L.take(true, rows_in);
+                const int64_t r_nlt = L.take(d_nlt != nullptr, S * 2);
+                const StepRows r_out = take_step_rows(&L, out, I, H, S);
+                const int64_t r_dist = L.take(d_dist != nullptr, S * 2);
+                int rc = L.reserve(h, 2 * S);
+                if (rc) return rc;
+                const StepOutputs fo = step_outputs_at(L, r_out, out, S, true);
 
-        bind(w, ldw);
-        a.r.ld_out = ld_out; a.r.ld_nlt = ld_nlt;
-        a.r.new_last_targets = d_nlt;
-        a.r.disturbance = d_dist; a.r.ld_d = ld_dist;
-        a.r.controls_out = d_ctrl; a.r.states_out = d_states; a.r.iters_out = d_iters; a.r.sequences_out = d_seq;
-        a.p.status = d_status; a.p.res_in = (double*)d_rin; a.p.res_out = (double*)d_rout;
-        a.first_unverified = d_fu;
-        a.fb_index = solve ? d_idx : nullptr;
-        a.fb_count = d_words;
-        hipError_t e = rollout_newton(I, a, h->grad_ws, d_words + 1, s);
-        if (e != hipSuccess) return hip_fail(h, e, "kernel launch");
+                NewtonMove gm{cnt, f.fb_index, 0, {}};
+                gm.set[gm.sets++] = NewtonRows{f.ws, L.fb, rows_in, ldw, ldc, 8};
+                if (d_nlt) gm.set[gm.sets++] = NewtonRows{d_nlt, L.at(r_nlt), S * 2, g.ld_nlt, ldc, 8};
+                if (d_dist) gm.set[gm.sets++] = NewtonRows{d_dist, L.at(r_dist), S * 2, g.ld_d, ldc, 8};
+                hipError_t e = rollout_newton_move(gm, false, f.s);
+                if (e != hipSuccess) return hip_fail(h, e, "gather launch");
 
-        uint32_t count = 0;
-        if (solve) {
-            HIP_TRY(h, hipMemcpyAsync(&count, d_words, sizeof(count), hipMemcpyDeviceToHost, s));
-            HIP_TRY(h, hipStreamSynchronize(s));
-        }
-        char* d_cfinal = w + (rows_in + 2 + 2 * H) * ldw * 8;   // the last step's sequence: controls out, and v out
-        char* d_vfinal = d_cfinal;
-        if (count > 0) {
-            // the compact batch, leading dimension ldc: the rows_in rows of the working set, new_last_targets, then
-            // every output of the polished loop
-            const int64_t cnt = count, ldc = (cnt + 63) / 64 * 64, S = steps;
-            int64_t r_total = rows_in;
-            auto take = [&](bool on, int64_t r) { const int64_t at = r_total; if (on) r_total += r; return on ? at : -1; };
-            const int64_t r_nlt = take(d_nlt != nullptr, S * 2), r_ctrl = take(true, S * I);
-            const int64_t r_states = take(d_states != nullptr, S * 2), r_seq = take(d_seq != nullptr, S * H * I);
-            const int64_t r_rin = take(d_rin != nullptr, S), r_rout = take(d_rout != nullptr, S);
-            const int64_t r_dist = take(d_dist != nullptr, S * 2);
-            const int64_t o_i32 = r_total * ldc * 8;   // int32 rows behind the fp64 ones: iters, status
-            rc = ensure(h, &h->newton_fb, &h->newton_fb_bytes, o_i32 + 2 * S * ldc * 4);
-            if (rc) return rc;
-            char* fb = (char*)h->newton_fb;
-            auto fat = [&](int64_t r) -> char* { return r < 0 ? nullptr : fb + r * ldc * 8; };
-            int32_t* f_iters = d_iters ? (int32_t*)(fb + o_i32) : nullptr;
-            int32_t* f_status = d_status ? (int32_t*)(fb + o_i32 + S * ldc * 4) : nullptr;
+                tpc_mpc_general_io io2 = fallback_io(L, I, cnt, row);
+                io2.controls_inout = L.at(row[9]); io2.v_inout = L.at(row[10]);
+                tpc_mpc_polish q2 = *q;
+                q2.status = fo.status; q2.residual_in = fo.rin; q2.residual_out = fo.rout;
+                // ... against the same plant: its gathered arrays and disturbance rows
+                tpc_mpc_plant plant2{};
+                if (plant_abc) { plant2.A = L.at(row[11]); plant2.B = L.at(row[12]); plant2.C = L.at(row[13]); }
+                plant2.disturbance = L.at(r_dist); plant2.ld_d = ldc;
+                rc = rollout_impl(h, p, &io2, steps, L.at(r_nlt), fo.ctrl, fo.states, fo.iters, fo.seq, false, true, &q2,
+                                  nullptr, TPC_MPC_DEVICE, stream, a.plant ? &plant2 : nullptr);
+                if (rc) return rc;
 
-            NewtonMove g;
-            std::memset(&g, 0, sizeof(g));
-            g.count = cnt; g.index = d_idx;
-            g.set[g.sets++] = NewtonRows{w, fb, rows_in, ldw, ldc, 8};
-            if (d_nlt) g.set[g.sets++] = NewtonRows{d_nlt, fat(r_nlt), S * 2, ld_nlt, ldc, 8};
-            if (d_dist) g.set[g.sets++] = NewtonRows{d_dist, fat(r_dist), S * 2, ld_dist, ldc, 8};
-            e = rollout_newton_move(g, false, s);
-            if (e != hipSuccess) return hip_fail(h, e, "gather launch");
-
-            tpc_mpc_general_io io2;
-            std::memset(&io2, 0, sizeof(io2));
-            io2.inputs = I; io2.n = cnt; io2.ld = ldc;
-            io2.A = fat(row[0]); io2.B = fat(row[1]); io2.C = fat(row[2]); io2.Q = fat(row[3]); io2.R = fat(row[4]);
-            io2.lower = fat(row[5]); io2.upper = fat(row[6]); io2.x0 = fat(row[7]); io2.targets = fat(row[8]);
-            io2.controls_inout = fat(row[9]); io2.v_inout = fat(row[10]);
-            tpc_mpc_polish q2 = *q;
-            q2.status = f_status; q2.residual_in = fat(r_rin); q2.residual_out = fat(r_rout);
-            // its flags stay in the handle's word (no flags_out: no synchronisation); phase 1's are merged in below
-            // ... against the same plant: its gathered arrays and disturbance rows
-            tpc_mpc_plant plant2;
-            std::memset(&plant2, 0, sizeof(plant2));
-            if (plant_abc) { plant2.A = fat(row[11]); plant2.B = fat(row[12]); plant2.C = fat(row[13]); }
-            plant2.disturbance = fat(r_dist); plant2.ld_d = ldc;
-            rc = rollout_impl(h, p, &io2, steps, fat(r_nlt), fat(r_ctrl), fat(r_states), f_iters, fat(r_seq), false, true,
-                              &q2, nullptr, TPC_MPC_DEVICE, stream, a.plant ? &plant2 : nullptr);
-            if (rc) return rc;
-
-            if (io->v_inout) {   // v out: the sequence for a Newton-only instance, the polished loop's v for the others
-                d_vfinal = w + row[10] * ldw * 8;
-                HIP_TRY(h, hipMemcpyAsync(d_vfinal, d_cfinal, (size_t)((int64_t)H * I * ldw * 8), hipMemcpyDeviceToDevice, s));
-            }
-            NewtonMove sc;
-            std::memset(&sc, 0, sizeof(sc));
-            sc.count = cnt; sc.index = d_idx;
-            sc.set[sc.sets++] = NewtonRows{fat(r_ctrl), d_ctrl, S * I, ldc, ld_out, 8};
-            if (d_states) sc.set[sc.sets++] = NewtonRows{fat(r_states), d_states, S * 2, ldc, ld_out, 8};
-            if (d_seq) sc.set[sc.sets++] = NewtonRows{fat(r_seq), d_seq, S * H * I, ldc, ld_out, 8};
-            if (d_rin) sc.set[sc.sets++] = NewtonRows{fat(r_rin), d_rin, S, ldc, ld_out, 8};
-            if (d_rout) sc.set[sc.sets++] = NewtonRows{fat(r_rout), d_rout, S, ldc, ld_out, 8};
-            if (d_iters) sc.set[sc.sets++] = NewtonRows{f_iters, d_iters, S, ldc, ld_out, 4};
-            if (d_status) sc.set[sc.sets++] = NewtonRows{f_status, d_status, S, ldc, ld_out, 4};
-            sc.set[sc.sets++] = NewtonRows{fat(row[9]), d_cfinal, (int64_t)H * I, ldc, ldw, 8};
-            if (io->v_inout) sc.set[sc.sets++] = NewtonRows{fat(row[10]), d_vfinal, (int64_t)H * I, ldc, ldw, 8};
-            e = rollout_newton_move(sc, true, s);
-            if (e != hipSuccess) return hip_fail(h, e, "scatter launch");
-        } else {
-            HIP_TRY(h, hipMemsetAsync(h->ws_words + 1, 0, sizeof(uint32_t), s));
-        }
-        e = rollout_newton_merge_flags(h->ws_words + 1, d_words + 1, s);
-        if (e != hipSuccess) return hip_fail(h, e, "flag merge launch");
-
-        // controller state and first_unverified back to the caller
-        if (io->controls_inout) HIP_TRY(h, copy_rows(io->controls_inout, ld * 8, d_cfinal, ldw * 8, n * 8, H * I, out_kind, s));
-        if (io->v_inout) HIP_TRY(h, copy_rows(io->v_inout, ld * 8, d_vfinal, ldw * 8, n * 8, H * I, out_kind, s));
-        if (first_unverified) HIP_TRY(h, hipMemcpyAsync(first_unverified, d_fu, (size_t)n * 4, out_kind, s));
-        if (host) {
-            rc = stage_out(h, g.t, kStepCount, n, s);
-            if (rc) return rc;
-        }
-        rc = order.end();
-        if (rc) return rc;
-        return finish_flags(h, flags_out, s);
+                if (io->v_inout) {   // v out: the sequence for a Newton-only instance, the polished loop's v for the others
+                    d_vfinal = f.ws + row[10] * ldw * 8;
+                    HIP_TRY(h, hipMemcpyAsync(d_vfinal, d_cfinal, (size_t)((int64_t)H * I * ldw * 8), hipMemcpyDeviceToDevice, f.s));
+                }
+                NewtonMove sc = step_scatter(cnt, f.fb_index, fo, out, I, H, S, ldc, g.ld_out);
+                sc.set[sc.sets++] = NewtonRows{L.at(row[9]), d_cfinal, (int64_t)H * I, ldc, ldw, 8};
+                if (io->v_inout) sc.set[sc.sets++] = NewtonRows{L.at(row[10]), d_vfinal, (int64_t)H * I, ldc, ldw, 8};
+                e = rollout_newton_move(sc, true, f.s);
+                if (e != hipSuccess) return hip_fail(h, e, "scatter launch");
+                return TPC_MPC_OK;
+            },
+            [&](const NewtonPhase& f) -> int {   // controller state and first_unverified back to the caller
+                if (io->controls_inout) HIP_TRY(h, copy_rows(io->controls_inout, ld * 8, d_cfinal, ldw * 8, n * 8, H * I, out_kind, f.s));
+                if (io->v_inout) HIP_TRY(h, copy_rows(io->v_inout, ld * 8, d_vfinal, ldw * 8, n * 8, H * I, out_kind, f.s));
+                if (first_unverified) HIP_TRY(h, hipMemcpyAsync(first_unverified, f.ws + o_fu, (size_t)n * 4, out_kind, f.s));
+                return TPC_MPC_OK;
+            });
     });
 }
 
@@ -1867,12 +1984,10 @@ int tpc_mpc_rollout_newton(tpc_mpc_handle h, const tpc_mpc_params* p, const tpc_
                                sequences_out, first_unverified, flags_out, mem, stream, nullptr);
 }
 
-// The exact compact solve (include/tpc_mpc.h): phase 1 is ONE launch, three rows in and two (+2H) out
-// (mpc_newton_compact.hip); with TPC_MPC_NEWTON_FALLBACK_SOLVE the instances it could not verify are gathered and
-// expanded to the general form on the device, run through tpc_mpc_solve_batch_general and tpc_mpc_polish_batch_general
-// and scattered back.  One 4-byte read-back (the fallback's count) sits between the phases; a host-only handle runs
-// phase 1 on the calling thread.  The Newton working set of tpc_mpc_rollout_newton holds the queue and the compact
-// batch; HOST arrays are staged in h->stage (stage_in / stage_out).
+// The exact compact solve (include/tpc_mpc.h) on newton_two_phase: phase 1 is ONE launch, three rows in and two (+2H)
+// out (mpc_newton_compact.hip); the fallback expands the queued instances to the general form on the device and runs
+// tpc_mpc_solve_batch_general and tpc_mpc_polish_batch_general on them.  A host-only handle runs phase 1 on the calling
+// thread.
 // `rows`: tpc_mpc_solve_batch_compact_exact_rows -- the ten model values per instance from params_rows ([10], ld n, in
 // `mem` like v), p's own neither read nor checked.
 // `warm`: tpc_mpc_solve_batch_compact_exact_from -- phase 1 starts from `start` ([H*2], ld n, in `mem`) on the warm
@@ -1939,91 +2054,44 @@ static int compact_exact_impl(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t
             return TPC_MPC_OK;
         }
 
-        HIP_TRY(h, hipSetDevice(h->device));
-        hipStream_t s = (hipStream_t)stream;
-        StreamOrderScope order(h, s);
-        rc = order.begin();
-        if (rc) return rc;
-        const bool host = mem == TPC_MPC_HOST;
-        // the working set: the queue and two words ([0] the fallback's count, [1] phase 1's flags); HOST arrays are
-        // staged in h->stage, which nothing writes between phase 1 and the copies back (the fallback's entries are
-        // called with TPC_MPC_DEVICE)
-        const int64_t o_words = stage_ld(n) * 4;
-        rc = ensure(h, &h->newton, &h->newton_bytes, o_words + 256);
-        if (rc) return rc;
-        if (!compact_exact_in_registers(H)) {
-            rc = ensure(h, &h->grad_ws, &h->grad_ws_bytes, pad256(polish_scratch_bytes(2, H, n)));
-            if (rc) return rc;
-        }
-        char* w = (char*)h->newton;
-        int32_t* d_idx = (int32_t*)w;
-        uint32_t* d_words = (uint32_t*)(w + o_words);
-        HIP_TRY(h, hipMemsetAsync(d_words, 0, 8, s));
-        if (host) {
-            rc = stage_in(h, t, kCount, n, s);
-            if (rc) return rc;
-        }
-        bind(host ? stage_ld(n) : n);
-        a.fb_index = solve ? d_idx : nullptr;
-        a.fb_count = d_words;
-        hipError_t e = compact_exact(H, a, h->grad_ws, d_words + 1, s);
-        if (e != hipSuccess) return hip_fail(h, e, "kernel launch");
+        return newton_two_phase(
+            h, n, solve, mem, stream, flags_out, 0, compact_exact_in_registers(H) ? 0 : polish_scratch_bytes(2, H, n), t,
+            kCount, newton_nothing,
+            [&](const NewtonPhase& f) {   // phase 1
+                bind(f.staged ? stage_ld(n) : n);
+                a.fb_index = f.fb_index; a.fb_count = f.fb_count;
+                return compact_exact(H, a, h->grad_ws, f.flags, f.s);
+            },
+            [&](const NewtonPhase& f, int64_t cnt, int64_t ldc) -> int {   // the fallback: the solve, then the polish
+                // the compact batch: the general form of the queued instances, then what the solve and the polish
+                // return for them
+                FallbackRows L(ldc);
+                const int64_t r_model = L.take(true, compact_model_rows(H)), r_ctrl = L.take(true, 2 * H);
+                const int64_t r_u0 = L.take(true, 2), r_rin = L.take(true, 1), r_rout = L.take(true, 1);
+                int rc = L.reserve(h, 1);
+                if (rc) return rc;
+                CompactExactBatch b{};
+                tpc_mpc_general_io io2 = fallback_compact_model(L, r_model, H, cnt, f.fb_index, &b);
+                b.controls = L.at(r_ctrl); b.u0 = L.at(r_u0); b.res_in = L.at(r_rin); b.res_out = L.at(r_rout);
+                b.status = L.at32(true, 0);
+                hipError_t e = compact_exact_gather(a, b, f.s);
+                if (e != hipSuccess) return hip_fail(h, e, "gather launch");
 
-        uint32_t count = 0;
-        if (solve) {
-            HIP_TRY(h, hipMemcpyAsync(&count, d_words, sizeof(count), hipMemcpyDeviceToHost, s));
-            HIP_TRY(h, hipStreamSynchronize(s));
-        }
-        if (count > 0) {
-            // the compact batch, leading dimension ldc: the general form of the queued instances, then what the solve
-            // and the polish return for them
-            const int64_t cnt = count, ldc = (cnt + 63) / 64 * 64;
-            const int64_t rows_fb = 20 + 2 * H + 2 * H + 2 + 2;
-            rc = ensure(h, &h->newton_fb, &h->newton_fb_bytes, rows_fb * ldc * 8 + ldc * 4);
-            if (rc) return rc;
-            char* fb = (char*)h->newton_fb;
-            int64_t r = 0;
-            auto rowf = [&](int64_t rows) { double* at = (double*)(fb + r * ldc * 8); r += rows; return at; };
-            CompactExactBatch b;
-            std::memset(&b, 0, sizeof(b));
-            b.count = cnt; b.ld = ldc; b.index = d_idx; b.H = H;
-            b.A = rowf(4); b.B = rowf(4); b.C = rowf(2); b.Q = rowf(2); b.R = rowf(2); b.lo = rowf(2); b.hi = rowf(2);
-            b.x0 = rowf(2); b.targets = rowf(2 * H); b.controls = rowf(2 * H); b.u0 = rowf(2);
-            b.res_in = rowf(1); b.res_out = rowf(1);
-            b.status = (int32_t*)(fb + rows_fb * ldc * 8);
-            e = compact_exact_gather(a, b, s);
-            if (e != hipSuccess) return hip_fail(h, e, "gather launch");
-
-            tpc_mpc_general_io io2;
-            std::memset(&io2, 0, sizeof(io2));
-            io2.inputs = 2; io2.n = cnt; io2.ld = ldc;
-            io2.A = b.A; io2.B = b.B; io2.C = b.C; io2.Q = b.Q; io2.R = b.R; io2.lower = b.lo; io2.upper = b.hi;
-            io2.x0 = b.x0; io2.targets = b.targets; io2.controls_inout = b.controls; io2.u0 = b.u0;
-            tpc_mpc_polish q2 = *q;
-            q2.status = b.status; q2.residual_in = b.res_in; q2.residual_out = b.res_out;
-            // no flags_out: no synchronisation; each entry resets the handle's flag word, so the solve's flags join
-            // phase 1's before the polish runs, and all of them join the polish's below
-            rc = tpc_mpc_solve_batch_general(h, p, &io2, nullptr, TPC_MPC_DEVICE, stream);
-            if (rc) return rc;
-            e = rollout_newton_merge_flags(d_words + 1, h->ws_words + 1, s);
-            if (e != hipSuccess) return hip_fail(h, e, "flag merge launch");
-            rc = tpc_mpc_polish_batch_general(h, p, &io2, &q2, nullptr, TPC_MPC_DEVICE, stream);
-            if (rc) return rc;
-            e = compact_exact_scatter(a, b, s);
-            if (e != hipSuccess) return hip_fail(h, e, "scatter launch");
-        } else {
-            HIP_TRY(h, hipMemsetAsync(h->ws_words + 1, 0, sizeof(uint32_t), s));
-        }
-        e = rollout_newton_merge_flags(h->ws_words + 1, d_words + 1, s);
-        if (e != hipSuccess) return hip_fail(h, e, "flag merge launch");
-
-        if (host) {
-            rc = stage_out(h, t, kCount, n, s);
-            if (rc) return rc;
-        }
-        rc = order.end();
-        if (rc) return rc;
-        return finish_flags(h, flags_out, s);
+                io2.controls_inout = b.controls; io2.u0 = b.u0;
+                tpc_mpc_polish q2 = *q;
+                q2.status = b.status; q2.residual_in = b.res_in; q2.residual_out = b.res_out;
+                // the polish resets the handle's flag word like the solve: the solve's flags join phase 1's first
+                rc = tpc_mpc_solve_batch_general(h, p, &io2, nullptr, TPC_MPC_DEVICE, stream);
+                if (rc) return rc;
+                e = rollout_newton_merge_flags(f.flags, h->ws_words + 1, f.s);
+                if (e != hipSuccess) return hip_fail(h, e, "flag merge launch");
+                rc = tpc_mpc_polish_batch_general(h, p, &io2, &q2, nullptr, TPC_MPC_DEVICE, stream);
+                if (rc) return rc;
+                e = compact_exact_scatter(a, b, f.s);
+                if (e != hipSuccess) return hip_fail(h, e, "scatter launch");
+                return TPC_MPC_OK;
+            },
+            newton_nothing);
     });
 }
 
@@ -2053,13 +2121,10 @@ int tpc_mpc_solve_batch_compact_exact_from(tpc_mpc_handle h, const tpc_mpc_param
                               fallback, steering_front, steering_rear, sequence_out, fell_back, flags_out, mem, stream);
 }
 
-// The compact closed loop (include/tpc_mpc.h): phase 1 is ONE launch for the whole loop, three (+ 2) rows in and the
-// per-step rows out (mpc_compact_loop.hip); with TPC_MPC_NEWTON_FALLBACK_SOLVE the instances it stopped are gathered
-// and expanded to the general form on the device, run through rollout_impl's polished mode from step 0 and scattered
-// back (rollout_newton_move).  One 4-byte read-back (the fallback's count) sits between the phases; a host-only handle
-// runs phase 1 on the calling thread.  The Newton working set holds the queue (h->newton) and the compact batch
-// (h->newton_fb), rebuilt by every call; HOST arrays are staged in h->stage (stage_in / stage_out), which the fallback
-// -- called with TPC_MPC_DEVICE -- does not touch.
+// The compact closed loop (include/tpc_mpc.h) on newton_two_phase: phase 1 is ONE launch for the whole loop, three
+// (+ 2) rows in and the per-step rows out (mpc_compact_loop.hip); the fallback expands the queued instances to the
+// general form on the device and runs rollout_impl's polished mode from step 0 on them, whose rows
+// rollout_newton_move scatters back.  A host-only handle runs phase 1 on the calling thread.
 int tpc_mpc_rollout_compact_exact(tpc_mpc_handle h, const tpc_mpc_params* p, int64_t n, const void* v,
                                   const void* delta_y, const void* delta_phi, const void* x0, int32_t steps,
                                   const tpc_mpc_polish* q, int32_t fallback, void* controls_out, void* states_out,
@@ -2115,101 +2180,42 @@ int tpc_mpc_rollout_compact_exact(tpc_mpc_handle h, const tpc_mpc_params* p, int
             return TPC_MPC_OK;
         }
 
-        HIP_TRY(h, hipSetDevice(h->device));
-        hipStream_t s = (hipStream_t)stream;
-        StreamOrderScope order(h, s);
-        rc = order.begin();
-        if (rc) return rc;
-        const bool host = mem == TPC_MPC_HOST;
-        // the working set: the queue and two words ([0] the fallback's count, [1] phase 1's flags)
-        const int64_t o_words = stage_ld(n) * 4;
-        rc = ensure(h, &h->newton, &h->newton_bytes, o_words + 256);
-        if (rc) return rc;
-        if (!compact_loop_in_registers(H)) {
-            rc = ensure(h, &h->grad_ws, &h->grad_ws_bytes, pad256(polish_scratch_bytes(2, H, n)));
-            if (rc) return rc;
-        }
-        char* w = (char*)h->newton;
-        int32_t* d_idx = (int32_t*)w;
-        uint32_t* d_words = (uint32_t*)(w + o_words);
-        HIP_TRY(h, hipMemsetAsync(d_words, 0, 8, s));
-        if (host) {
-            rc = stage_in(h, t, kCount, n, s);
-            if (rc) return rc;
-        }
-        const int64_t ld = host ? stage_ld(n) : n;
-        bind(ld);
-        a.c.fb_index = solve ? d_idx : nullptr;
-        a.c.fb_count = d_words;
-        hipError_t e = compact_loop(H, a, h->grad_ws, d_words + 1, s);
-        if (e != hipSuccess) return hip_fail(h, e, "kernel launch");
+        int64_t ld = n;       // ... of the arrays the kernels take, and those as the polished loop's outputs
+        StepOutputs out{};
+        return newton_two_phase(
+            h, n, solve, mem, stream, flags_out, 0, compact_loop_in_registers(H) ? 0 : polish_scratch_bytes(2, H, n), t,
+            kCount, newton_nothing,
+            [&](const NewtonPhase& f) {   // phase 1
+                if (f.staged) ld = stage_ld(n);
+                bind(ld);
+                out = StepOutputs{a.controls, a.states, a.sequences, a.res_in, a.res_out, nullptr, a.status};
+                a.c.fb_index = f.fb_index; a.c.fb_count = f.fb_count;
+                return compact_loop(H, a, h->grad_ws, f.flags, f.s);
+            },
+            [&](const NewtonPhase& f, int64_t cnt, int64_t ldc) -> int {   // the fallback: the polished loop from step 0
+                // the compact batch: the general form of the queued instances, then every output of the polished
+                // loop that the caller asked for
+                FallbackRows L(ldc);
+                const int64_t r_model = L.take(true, compact_model_rows(H));
+                const StepRows r_out = take_step_rows(&L, out, 2, H, S);
+                int rc = L.reserve(h, S);
+                if (rc) return rc;
+                const StepOutputs fo = step_outputs_at(L, r_out, out, S, false);
+                CompactLoopBatch b{};
+                const tpc_mpc_general_io io2 = fallback_compact_model(L, r_model, H, cnt, f.fb_index, &b);
+                hipError_t e = compact_loop_gather(a, b, f.s);
+                if (e != hipSuccess) return hip_fail(h, e, "gather launch");
 
-        uint32_t count = 0;
-        if (solve) {
-            HIP_TRY(h, hipMemcpyAsync(&count, d_words, sizeof(count), hipMemcpyDeviceToHost, s));
-            HIP_TRY(h, hipStreamSynchronize(s));
-        }
-        if (count > 0) {
-            // the compact batch, leading dimension ldc: the general form of the queued instances, then every output
-            // of the polished loop that the caller asked for
-            const int64_t cnt = count, ldc = (cnt + 63) / 64 * 64;
-            int64_t r_total = 0;
-            auto take = [&](bool on, int64_t r) { const int64_t at = r_total; if (on) r_total += r; return on ? at : -1; };
-            const int64_t r_model = take(true, 20 + 2 * H), r_ctrl = take(true, S * 2);
-            const int64_t r_states = take(a.states != nullptr, S * 2), r_seq = take(a.sequences != nullptr, S * H * 2);
-            const int64_t r_rin = take(a.res_in != nullptr, S), r_rout = take(a.res_out != nullptr, S);
-            const int64_t o_i32 = r_total * ldc * 8;   // the int32 rows behind the fp64 ones: status
-            rc = ensure(h, &h->newton_fb, &h->newton_fb_bytes, o_i32 + S * ldc * 4);
-            if (rc) return rc;
-            char* fb = (char*)h->newton_fb;
-            auto fat = [&](int64_t r) -> double* { return r < 0 ? nullptr : (double*)(fb + r * ldc * 8); };
-            int32_t* f_status = a.status ? (int32_t*)(fb + o_i32) : nullptr;
-            int64_t r = r_model;
-            auto rowf = [&](int64_t rows) { double* at = fat(r); r += rows; return at; };
-            CompactLoopBatch b;
-            std::memset(&b, 0, sizeof(b));
-            b.count = cnt; b.ld = ldc; b.index = d_idx; b.H = H;
-            b.A = rowf(4); b.B = rowf(4); b.C = rowf(2); b.Q = rowf(2); b.R = rowf(2); b.lo = rowf(2); b.hi = rowf(2);
-            b.x0 = rowf(2); b.targets = rowf(2 * H);
-            e = compact_loop_gather(a, b, s);
-            if (e != hipSuccess) return hip_fail(h, e, "gather launch");
-
-            tpc_mpc_general_io io2;
-            std::memset(&io2, 0, sizeof(io2));
-            io2.inputs = 2; io2.n = cnt; io2.ld = ldc;
-            io2.A = b.A; io2.B = b.B; io2.C = b.C; io2.Q = b.Q; io2.R = b.R; io2.lower = b.lo; io2.upper = b.hi;
-            io2.x0 = b.x0; io2.targets = b.targets;
-            tpc_mpc_polish q2 = *q;
-            q2.status = f_status; q2.residual_in = fat(r_rin); q2.residual_out = fat(r_rout);
-            // its flags stay in the handle's word (no flags_out: no synchronisation); phase 1's are merged in below
-            rc = rollout_impl(h, p, &io2, steps, nullptr, fat(r_ctrl), fat(r_states), nullptr, fat(r_seq), false, true,
-                              &q2, nullptr, TPC_MPC_DEVICE, stream);
-            if (rc) return rc;
-
-            NewtonMove sc;
-            std::memset(&sc, 0, sizeof(sc));
-            sc.count = cnt; sc.index = d_idx;
-            sc.set[sc.sets++] = NewtonRows{fat(r_ctrl), a.controls, S * 2, ldc, ld, 8};
-            if (a.states) sc.set[sc.sets++] = NewtonRows{fat(r_states), a.states, S * 2, ldc, ld, 8};
-            if (a.sequences) sc.set[sc.sets++] = NewtonRows{fat(r_seq), a.sequences, S * H * 2, ldc, ld, 8};
-            if (a.res_in) sc.set[sc.sets++] = NewtonRows{fat(r_rin), a.res_in, S, ldc, ld, 8};
-            if (a.res_out) sc.set[sc.sets++] = NewtonRows{fat(r_rout), a.res_out, S, ldc, ld, 8};
-            if (a.status) sc.set[sc.sets++] = NewtonRows{f_status, a.status, S, ldc, ld, 4};
-            e = rollout_newton_move(sc, true, s);
-            if (e != hipSuccess) return hip_fail(h, e, "scatter launch");
-        } else {
-            HIP_TRY(h, hipMemsetAsync(h->ws_words + 1, 0, sizeof(uint32_t), s));
-        }
-        e = rollout_newton_merge_flags(h->ws_words + 1, d_words + 1, s);
-        if (e != hipSuccess) return hip_fail(h, e, "flag merge launch");
-
-        if (host) {
-            rc = stage_out(h, t, kCount, n, s);
-            if (rc) return rc;
-        }
-        rc = order.end();
-        if (rc) return rc;
-        return finish_flags(h, flags_out, s);
+                tpc_mpc_polish q2 = *q;
+                q2.status = fo.status; q2.residual_in = fo.rin; q2.residual_out = fo.rout;
+                rc = rollout_impl(h, p, &io2, steps, nullptr, fo.ctrl, fo.states, nullptr, fo.seq, false, true, &q2,
+                                  nullptr, TPC_MPC_DEVICE, stream);
+                if (rc) return rc;
+                e = rollout_newton_move(step_scatter(cnt, f.fb_index, fo, out, 2, H, S, ldc, ld), true, f.s);
+                if (e != hipSuccess) return hip_fail(h, e, "scatter launch");
+                return TPC_MPC_OK;
+            },
+            newton_nothing);
     });
 }
 
@@ -2235,22 +2241,10 @@ static int compact_exact_backward_impl(tpc_mpc_handle h, const tpc_mpc_params* p
         rc = check_batch(h, n, mem);
         if (rc) return rc;
         if (!g) return fail(h, TPC_MPC_ERR_BAD_ARG, "null gradient struct");
-        if (h->host_only && mem == TPC_MPC_DEVICE)
-            return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): the backward pass takes HOST memory only");
-        const bool host = mem == TPC_MPC_HOST;
+        rc = check_host_only_pass(h, mem, "backward pass");
+        if (rc) return rc;
         constexpr int kP = cgrad::kParams;
-        if (n == 0) {
-            if (g->dparams) {
-                if (host) {
-                    std::memset(g->dparams, 0, kP * 8);
-                } else {
-                    HIP_TRY(h, hipSetDevice(h->device));
-                    HIP_TRY(h, hipMemsetAsync(g->dparams, 0, kP * 8, (hipStream_t)stream));
-                }
-            }
-            if (flags_out) *flags_out = 0;
-            return TPC_MPC_OK;
-        }
+        if (n == 0) return zero_dparams(h, g->dparams, kP, flags_out, mem, stream);
         if (!v || !delta_y || !delta_phi) return fail(h, TPC_MPC_ERR_BAD_ARG, "null batch pointer");
         if (!sequence) return fail(h, TPC_MPC_ERR_BAD_ARG, "null sequence");
         if (rows && !params_rows) return fail(h, TPC_MPC_ERR_BAD_ARG, "null params_rows");
@@ -2328,22 +2322,10 @@ int tpc_mpc_rollout_compact_exact_backward(tpc_mpc_handle h, const tpc_mpc_param
         if (!g) return fail(h, TPC_MPC_ERR_BAD_ARG, "null gradient struct");
         rc = check_steps(h, steps);
         if (rc) return rc;
-        if (h->host_only && mem == TPC_MPC_DEVICE)
-            return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): the backward pass takes HOST memory only");
-        const bool host = mem == TPC_MPC_HOST;
+        rc = check_host_only_pass(h, mem, "backward pass");
+        if (rc) return rc;
         constexpr int kP = cloopgrad::kParams;
-        if (n == 0 || steps == 0) {
-            if (g->dparams) {
-                if (host) {
-                    std::memset(g->dparams, 0, kP * 8);
-                } else {
-                    HIP_TRY(h, hipSetDevice(h->device));
-                    HIP_TRY(h, hipMemsetAsync(g->dparams, 0, kP * 8, (hipStream_t)stream));
-                }
-            }
-            if (flags_out) *flags_out = 0;
-            return TPC_MPC_OK;
-        }
+        if (n == 0 || steps == 0) return zero_dparams(h, g->dparams, kP, flags_out, mem, stream);
         if (!v || !delta_y || !delta_phi) return fail(h, TPC_MPC_ERR_BAD_ARG, "null batch pointer");
         if (!sequences || !states) return fail(h, TPC_MPC_ERR_BAD_ARG, "null sequences / states");
         const int H = p->horizon;
@@ -2411,8 +2393,8 @@ int tpc_mpc_solve_batch_compact_exact_forward(tpc_mpc_handle h, const tpc_mpc_pa
             return fail(h, TPC_MPC_ERR_BAD_ARG, "tparams is the shared parameters' tangent: with params_rows give tparams_rows");
         if (!rows && t->tparams_rows) return fail(h, TPC_MPC_ERR_BAD_ARG, "tparams_rows needs params_rows");
         if (!tfront && !trear && !tsequence) return fail(h, TPC_MPC_ERR_BAD_ARG, "no output asked for");
-        if (h->host_only && mem == TPC_MPC_DEVICE)
-            return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): the forward pass takes HOST memory only");
+        rc = check_host_only_pass(h, mem, "forward pass");
+        if (rc) return rc;
         if (n == 0) { if (flags_out) *flags_out = 0; return TPC_MPC_OK; }
         if (!v || !delta_y || !delta_phi) return fail(h, TPC_MPC_ERR_BAD_ARG, "null batch pointer");
         if (!sequence) return fail(h, TPC_MPC_ERR_BAD_ARG, "null sequence");
@@ -2513,8 +2495,8 @@ static int rollout_backward_impl(tpc_mpc_handle h, const tpc_mpc_params* p, cons
         if (rc) return rc;
         if (g->dnew_last_targets && !new_last_targets)
             return fail(h, TPC_MPC_ERR_BAD_ARG, "dnew_last_targets asked for without new_last_targets");
-        if (h->host_only && mem == TPC_MPC_DEVICE)
-            return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): the backward pass takes HOST memory only");
+        rc = check_host_only_pass(h, mem, "backward pass");
+        if (rc) return rc;
         if (io->n == 0 || steps == 0) { if (flags_out) *flags_out = 0; return TPC_MPC_OK; }
         rc = check_model(h, io);
         if (rc) return rc;
@@ -2600,8 +2582,8 @@ int tpc_mpc_solve_batch_general_forward(tpc_mpc_handle h, const tpc_mpc_params* 
         if (!t) return fail(h, TPC_MPC_ERR_BAD_ARG, "null tangent struct");
         if (t->directions < 1 || (int64_t)t->directions * io->n > 0x7fffffffll)
             return fail(h, TPC_MPC_ERR_BAD_ARG, "need directions >= 1 and directions * n < 2^31");
-        if (h->host_only && mem == TPC_MPC_DEVICE)
-            return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): the forward pass takes HOST memory only");
+        rc = check_host_only_pass(h, mem, "forward pass");
+        if (rc) return rc;
         if (io->n == 0) { if (flags_out) *flags_out = 0; return TPC_MPC_OK; }
         rc = check_model(h, io);
         if (rc) return rc;
@@ -2660,8 +2642,8 @@ static int rollout_forward_impl(tpc_mpc_handle h, const tpc_mpc_params* p, const
             return fail(h, TPC_MPC_ERR_BAD_ARG, "need directions >= 1 and directions * n < 2^31");
         if (t->tnew_last_targets && !new_last_targets)
             return fail(h, TPC_MPC_ERR_BAD_ARG, "tnew_last_targets given without new_last_targets");
-        if (h->host_only && mem == TPC_MPC_DEVICE)
-            return fail(h, TPC_MPC_ERR_NO_DEVICE, "host-only handle (TPC_MPC_DEVICE_NONE): the forward pass takes HOST memory only");
+        rc = check_host_only_pass(h, mem, "forward pass");
+        if (rc) return rc;
         if (io->n == 0 || steps == 0) { if (flags_out) *flags_out = 0; return TPC_MPC_OK; }
         rc = check_model(h, io);
         if (rc) return rc;
