@@ -12,7 +12,10 @@ instance is kept if it is verified at every step at the base point and at both p
 delta_y, delta_phi, the four weights, step_size, wheelbase and both components of x0) with the active set of every
 step's sequence unchanged there.  The forward alone (no call of the entry under test) keeps 256 of 256 at (H, S) =
 (4, 6), default, and 244 of 256 at (10, 4), weights; the test asks for 200 and for 240 (the count kept minus a few).
-The bound is 1e-5 norm-wise, the project's bound for its derivative entries; measured worst 8.8e-9 (step_size)."""
+The bound is 1e-5 norm-wise, the project's bound for its derivative entries; measured worst 8.8e-9 (step_size).
+Off the default vehicle (tests/model/vehicles.py, speeds of both signs and none zero, since the steps divide by
+sign(v)): neg_l and neg_T at (4, 6) and (10, 4), asym and rear_cheap at (5, 5).  The forward alone keeps 254, 243, 256,
+249, 253 and 255 of 256; each cell asks for 0.9 of its count, rounded down.  Measured worst 1.3e-8 (neg_T, (10, 4))."""
 import ctypes as C
 import itertools
 import os
@@ -23,6 +26,7 @@ import pytest
 from tests.model import compact_grad_common as cg
 from tests.model import compact_loop_common as cl
 from tests.model import compact_loop_grad_common as lg
+from tests.model import compact_loop_paths as cp
 from tests.model.compact_loop_grad_common import ALL, EXACT, PER_INSTANCE, VARIANTS, bits
 from trajectory_controller_amd import COMPACT_PARAM_NAMES, MpcSolver, capi
 from trajectory_controller_amd.synth import compact_inputs
@@ -73,17 +77,26 @@ def _step(x):
     return np.where(ax > 0.1, 1e-6 * np.maximum(1.0, ax), 1e-4 * ax)
 
 
-FD_CASES = [(4, 6, "default", 200), (10, 4, "weights", 240)]
+# a name of compact_exact_common.VARIANTS runs on compact_inputs (v > 0); any other is a vehicle of tests/model/vehicles.py
+# on that module's mixed-sign speeds, with v[3] = 0 replaced (compact_loop_paths.case(nonzero=True): the steps divide by
+# sign(v)); their `least` is 0.9 of what the forward alone keeps, rounded down
+FD_CASES = [(4, 6, "default", 200), (10, 4, "weights", 240), (4, 6, "neg_l", 228), (10, 4, "neg_l", 218),
+            (4, 6, "neg_T", 230), (10, 4, "neg_T", 224), (5, 5, "asym", 227), (5, 5, "rear_cheap", 229)]
 
 
 @pytest.mark.parametrize("H,S,variant,least", FD_CASES)
 def test_finite_differences_of_the_forward_entry(H, S, variant, least):
     n = 256
-    v, dy, dphi = compact_inputs(H, n)
-    x0 = cl.start_states(H, n)
+    if variant in VARIANTS:
+        v, dy, dphi = compact_inputs(H, n)
+        x0, model = cl.start_states(H, n), VARIANTS[variant]
+    else:
+        cs = cp.case(variant, H, n, S, nonzero=True)
+        v, dy, dphi, x0, model = cs.v, cs.dy, cs.dphi, cs.x0, cs.kw
+        assert (v > 0).any() and (v < 0).any() and np.all(v != 0)
     c = np.random.default_rng(5 + H).standard_normal((2 * S, n))
     names = COMPACT_PARAM_NAMES[:6]
-    with MpcSolver(horizon=H, device=None, **VARIANTS[variant]) as s:
+    with MpcSolver(horizon=H, device=None, **model) as s:
         p0 = s.params
         lo, hi = np.array(p0.lower)[:, None], np.array(p0.upper)[:, None]
 
