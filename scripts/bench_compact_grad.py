@@ -16,7 +16,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
-from trajectory_controller_amd import MpcSolver, mpc_compact, mpc_compact_exact
+from trajectory_controller_amd import MpcSolver, compact_general_form, mpc_compact, mpc_compact_exact
+from trajectory_controller_amd.autograd import _param_defaults
 from trajectory_controller_amd.synth import compact_inputs
 
 SHAPES = ((262144, 4), (262144, 10), (262144, 20), (16384, 40))   # (n, H)
@@ -35,19 +36,6 @@ def timed(fn, reps, warmup):
         b.synchronize()
         ms.append(a.elapsed_time(b))
     return float(np.median(ms)), float(np.min(ms))
-
-
-def expanded(p, H, v, dy, dphi):
-    """the general form as mpc_compact builds it, on the device: A B C Q R lower upper x0 targets"""
-    n = v.numel()
-    f64 = dict(dtype=torch.float64, device=v.device)
-    Tv = p.step_size * v
-    one, zero = torch.ones(n, **f64), torch.zeros(n, **f64)
-    rows = lambda *x: torch.tensor(x, **f64)[:, None].expand(len(x), n).contiguous()
-    return [torch.stack([one, Tv, zero, one]), torch.stack([zero, Tv, Tv / p.wheelbase, -Tv / p.wheelbase]),
-            torch.zeros(2, n, **f64), rows(p.weight_y, p.weight_phi),
-            rows(p.weight_steering_front, p.weight_steering_rear), rows(*p.lower), rows(*p.upper),
-            torch.zeros(2, n, **f64), torch.stack([dy, dphi]).repeat(H, 1).contiguous()]
 
 
 def main():
@@ -102,7 +90,7 @@ def main():
             rec["compact_backward_all_outputs_ms"], _ = timed(
                 lambda: s.solve_batch_compact_exact_backward(vd, yd, pd, seq, gf, gr, status=st, want=want,
                                                              want_flags=False), args.reps, args.warmup)
-            ins = expanded(p, H, vd, yd, pd)
+            ins = [t.contiguous() for t in compact_general_form(vd, yd, pd, *_param_defaults(p), H).values()]
             g = torch.zeros_like(seq)
             g[0], g[1] = gf, gr
             rec["general_backward_ms"], _ = timed(

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from trajectory_controller_amd import MpcSolver
+from trajectory_controller_amd.autograd import _param_defaults, compact_general_form
 from trajectory_controller_amd.synth import compact_inputs
 
 SHAPES = ((262144, 4), (262144, 10), (262144, 20), (16384, 40))   # (n, H)
@@ -46,19 +47,6 @@ def shared_rows(p, n, device):
     col = [p.weight_y, p.weight_phi, p.weight_steering_front, p.weight_steering_rear, p.step_size, p.wheelbase,
            p.lower[0], p.lower[1], p.upper[0], p.upper[1]]
     return torch.tensor(col, dtype=torch.float64, device=device)[:, None].expand(10, n).contiguous()
-
-
-def expanded(p, H, v, dy, dphi):
-    """the general form as mpc_compact builds it, on the device: A B C Q R lower upper x0 targets"""
-    n = v.numel()
-    f64 = dict(dtype=torch.float64, device=v.device)
-    Tv = p.step_size * v
-    one, zero = torch.ones(n, **f64), torch.zeros(n, **f64)
-    rows = lambda *x: torch.tensor(x, **f64)[:, None].expand(len(x), n).contiguous()
-    return [torch.stack([one, Tv, zero, one]), torch.stack([zero, Tv, Tv / p.wheelbase, -Tv / p.wheelbase]),
-            torch.zeros(2, n, **f64), rows(p.weight_y, p.weight_phi),
-            rows(p.weight_steering_front, p.weight_steering_rear), rows(*p.lower), rows(*p.upper),
-            torch.zeros(2, n, **f64), torch.stack([dy, dphi]).repeat(H, 1).contiguous()]
 
 
 def expanded_tangents(p, v, tp):
@@ -87,8 +75,9 @@ def main():
             p = s.params
             _, _, seq, st, _ = s.solve_batch_compact_exact(v, dy, dphi, want_sequence=True)
             rec = dict(horizon=H, n=n, excluded=int((st < 0).sum()), reps=args.reps)
-            ins = expanded(p, H, v, dy, dphi)
-            rec["expand_model_ms"] = timed(lambda: expanded(p, H, v, dy, dphi), args.reps, args.warmup)
+            expand = lambda: [t.contiguous() for t in compact_general_form(v, dy, dphi, *_param_defaults(p), H).values()]
+            ins = expand()
+            rec["expand_model_ms"] = timed(expand, args.reps, args.warmup)
             eye = torch.eye(10, dtype=torch.float64, device=v.device)
             for K in KS:
                 tp = eye[:K].contiguous()

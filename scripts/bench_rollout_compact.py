@@ -15,7 +15,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
-from trajectory_controller_amd import MpcSolver
+from trajectory_controller_amd import MpcSolver, compact_general_form
+from trajectory_controller_amd.autograd import _param_defaults
 from trajectory_controller_amd.synth import compact_inputs
 
 CASES = ((262144, 4, 20), (65536, 10, 50), (262144, 20, 10), (16384, 40, 10))   # (n, H, steps)
@@ -36,20 +37,6 @@ def timed(fn, reps, warmup):
     return float(np.median(ms)), float(np.min(ms))
 
 
-def expanded(p, H, v, dy, dphi):
-    """the general form of the compact instances, as mpc_compact (autograd.py) builds it"""
-    n = v.numel()
-    f64 = dict(dtype=torch.float64, device=v.device)
-    T, l = torch.tensor(p.step_size, **f64), torch.tensor(p.wheelbase, **f64)   # (a Python divisor is multiplied by its reciprocal)
-    Tv = T * v
-    one, zero = torch.ones(n, **f64), torch.zeros(n, **f64)
-    rows = lambda *x: torch.tensor(x, **f64)[:, None].expand(len(x), n).contiguous()
-    return [torch.stack([one, Tv, zero, one]), torch.stack([zero, Tv, Tv / l, -Tv / l]),
-            torch.zeros(2, n, **f64), rows(p.weight_y, p.weight_phi),
-            rows(p.weight_steering_front, p.weight_steering_rear), rows(*p.lower), rows(*p.upper),
-            torch.zeros(2, n, **f64), torch.stack([dy, dphi]).repeat(H, 1).contiguous()]
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -63,7 +50,7 @@ def main():
         v, dy, dphi = (torch.from_numpy(a).cuda() for a in compact_inputs(H, n))
         pol = dict(tol=args.tol, max_rounds=args.max_rounds)
         with MpcSolver(horizon=H) as s:
-            gen = expanded(s.params, H, v, dy, dphi)
+            gen = [t.contiguous() for t in compact_general_form(v, dy, dphi, *_param_defaults(s.params), H).values()]
             rec = dict(horizon=H, steps=S, n=n, **pol)
             for fallback in ("none", "solve"):
                 rec[f"rollout_newton_{fallback}_ms"], rec[f"rollout_newton_{fallback}_min_ms"] = timed(

@@ -17,8 +17,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
-from bench_rollout_compact import CASES, expanded, timed
-from trajectory_controller_amd import MpcSolver, mpc_rollout_compact
+from bench_rollout_compact import CASES, timed
+from trajectory_controller_amd import MpcSolver, compact_general_form, mpc_rollout_compact
+from trajectory_controller_amd.autograd import _param_defaults
 from trajectory_controller_amd.synth import compact_inputs
 
 ALL = ("v", "delta_y", "delta_phi", "x0", "params", "params_rows", "kkt_residual")
@@ -40,7 +41,7 @@ def main():
         rng = np.random.default_rng(3)
         with MpcSolver(horizon=H) as s:
             p = s.params
-            gen = expanded(p, H, v, dy, dphi)
+            gen = [t.contiguous() for t in compact_general_form(v, dy, dphi, *_param_defaults(p), H).values()]
             rec = dict(horizon=H, steps=S, n=n, **pol)
             c, x, q, st, first = s.rollout_compact_exact(S, v, dy, dphi, **pol)
             torch.cuda.synchronize()

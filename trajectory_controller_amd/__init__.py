@@ -11,8 +11,8 @@ oracle/ -- that directory is the checker used by tests/ and bench.py only.
 from .capi import (ALGO_AUTO, ALGO_GROUP, ALGO_LANE, ALGO_LANE_FMA, ALGO_WAVE, F32, F64, FLAG_BAD_MODEL, FLAG_MAX_ITER, FLAG_NONFINITE,
                    FLAG_NOT_POLISHED,                    TpcMpcError, default_params, load_library)
 from .solver import COMPACT_PARAM_NAMES, MpcSolver
-from .autograd import CompactWarmStart, mpc_compact, mpc_compact_exact, mpc_general, mpc_rollout, mpc_rollout_compact
+from .autograd import CompactWarmStart, compact_general_form, mpc_compact, mpc_compact_exact, mpc_general, mpc_rollout, mpc_rollout_compact
 
-__all__ = ["MpcSolver", "mpc_general", "mpc_compact", "mpc_compact_exact", "CompactWarmStart", "mpc_rollout", "mpc_rollout_compact", "COMPACT_PARAM_NAMES", "TpcMpcError", "default_params", "load_library", "ALGO_AUTO", "ALGO_WAVE",
+__all__ = ["MpcSolver", "mpc_general", "mpc_compact", "mpc_compact_exact", "CompactWarmStart", "mpc_rollout", "mpc_rollout_compact", "compact_general_form", "COMPACT_PARAM_NAMES", "TpcMpcError", "default_params", "load_library", "ALGO_AUTO", "ALGO_WAVE",
            "ALGO_LANE", "ALGO_LANE_FMA", "ALGO_GROUP", "F64", "F32", "FLAG_NONFINITE", "FLAG_MAX_ITER", "FLAG_BAD_MODEL",
            "FLAG_NOT_POLISHED"]

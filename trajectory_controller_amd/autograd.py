@@ -1,24 +1,36 @@
-"""torch autograd over the batched general-form solve: `mpc_general` and the reference controller's `mpc_compact`,
-and over the closed loop: `mpc_rollout` (forward MpcSolver.rollout_record, or rollout_polished with polish=True;
-backward tpc_mpc_rollout_backward); and `mpc_compact_exact`, the reference controller with shared or per-instance
-parameters on the exact compact solve and its own backward kernel (no general form on either side); and
-`mpc_rollout_compact`, the reference controller's closed loop (forward tpc_mpc_rollout_compact_exact, no general form;
-backward tpc_mpc_rollout_backward on the expansion, built in the backward only, or with backward="fused" one call of
-tpc_mpc_rollout_compact_exact_backward, no general form either; no forward mode).
+"""torch autograd over MpcSolver's batched entries.  Inputs are CUDA fp64 tensors, component-major
+(solve_batch_general's layout); every function is once-differentiable; forward mode is torch.autograd.forward_ad, one
+direction per dual level, taken at the same sequences the backward is taken at; torch.func transforms are not
+supported.  include/tpc_mpc.h defines the derivative: the active set is read off the solved sequence and the free
+components are differentiated through the stationarity condition on that set, so it is the gradient of the optimum when
+the sequence is the optimum -- dlib's default eps 0.01 leaves a loose one: pass polish=True (a Newton round or two onto
+the verified optimum, the cheap way) or a small eps (e.g. eps=1e-10).  Instances whose data are non-finite or break
+dlib's requires clause get zero gradients.  All launches go to torch's current stream.
 
-Forward is MpcSolver.solve_batch_general from a fresh controller (zero controls); backward is
-tpc_mpc_solve_batch_general_backward on torch's current stream (include/tpc_mpc.h gives the definition of the
-derivative: the active set is read off the returned controls, the free components are differentiated through the
-stationarity condition on that set).  The gradient is that of the optimum when the controls are the optimum: dlib's
-default eps 0.01 leaves a loose solution, so either pass polish=True (solve at eps 0.01, then a Newton round or two of
-tpc_mpc_polish_batch_general onto the verified optimum -- the cheap way) or a small eps (e.g. eps=1e-10).  Inputs are CUDA fp64
-tensors; both functions are once-differentiable.  Instances whose data are non-finite or break dlib's requires clause
-get zero gradients.
-
-Forward mode (torch.autograd.forward_ad) works on all four functions: the jvp of mpc_general / mpc_compact is
-tpc_mpc_solve_batch_general_forward, that of mpc_rollout tpc_mpc_rollout_forward, that of mpc_compact_exact
-tpc_mpc_solve_batch_compact_exact_forward (shared or per-instance parameters, no general form), one direction per
-dual level, at the same sequences the backward is taken at.  torch.func transforms are not supported.
+mpc_general          the solved sequence of n fresh controllers.
+    forward   MpcSolver.solve_batch_general from zero controls, then polish_batch_general with polish
+    backward  tpc_mpc_solve_batch_general_backward
+    jvp       tpc_mpc_solve_batch_general_forward
+    saved     the nine arrays and the controls
+mpc_compact          the reference controller, (front, rear): compact_general_form, then mpc_general.
+    forward, backward, jvp, saved: mpc_general's; torch's chain rule carries them through the expansion
+mpc_rollout          the closed loop of n fresh controllers, optionally against a separate plant.
+    forward   MpcSolver.rollout_record; rollout_polished with polish, rollout_newton with newton_first
+    backward  tpc_mpc_rollout_backward (tpc_mpc_rollout_plant_backward with a plant or a disturbance)
+    jvp       tpc_mpc_rollout_forward (tpc_mpc_rollout_plant_forward)
+    saved     the nine arrays, the five optional ones (None where not given), the states and every step's sequence
+mpc_compact_exact    the reference controller at the verified optimum, shared or per-instance parameters.
+    forward   MpcSolver.solve_batch_compact_exact (the rows entry with a per-instance parameter), no general form
+    backward  tpc_mpc_solve_batch_compact_exact_backward (_rows_backward)
+    jvp       tpc_mpc_solve_batch_compact_exact_forward
+    saved     v, delta_y, delta_phi, the [10, n] rows if any, the sequence and the status
+mpc_rollout_compact  the reference controller's closed loop, every step the verified optimum.
+    forward   MpcSolver.rollout_compact_exact, no general form
+    backward  "expanded": tpc_mpc_rollout_backward on compact_general_form, built in the backward only;
+              "fused": tpc_mpc_rollout_compact_exact_backward, no general form
+    jvp       none
+    saved     v, delta_y, delta_phi, the states, every step's sequence and x0 (None where not given)
+compact_general_form is the one place the reference controller's model is expanded to the general form.
 """
 from __future__ import annotations
 
@@ -28,6 +40,100 @@ import torch
 from torch.autograd.function import once_differentiable
 
 _ALPHA_MAX = 22.0 * math.pi / 180.0   # the reference module's steering bounds
+
+MODEL_NAMES = ("A", "B", "C", "Q", "R", "lower", "upper", "x0", "targets")       # solve_batch_general's order
+_ROLLOUT_NAMES = MODEL_NAMES + ("new_last_targets", "Ap", "Bp", "Cp", "disturbance")   # the last five optional
+_COMPACT_NAMES = ("v", "delta_y", "delta_phi")
+# the ten compact parameters as the five arguments that carry them: (name, shared shape, where in the ten), in the
+# order of COMPACT_PARAM_NAMES
+_COMPACT_PARAMS = (("weights", (4,), slice(0, 4)), ("step_size", (), 4), ("wheelbase", (), 5),
+                   ("lower", (2,), slice(6, 8)), ("upper", (2,), slice(8, 10)))
+_WEIGHT_KEYS = ("weight_y", "weight_phi", "weight_steering_front", "weight_steering_rear")
+_BY_VALUE = _WEIGHT_KEYS + ("step_size", "wheelbase", "lower", "upper")   # tpc_mpc_params' fields of the ten
+
+
+def _require_cuda_f64(message, *tensors):
+    for t in tensors:
+        if t is not None and not (t.is_cuda and t.dtype == torch.float64):
+            raise ValueError(message)
+
+
+def _polish(polish):
+    """(tol, max_rounds) of a polish argument that is on: True is (1e-9, 8)"""
+    return (1e-9, 8) if polish is True else tuple(polish)
+
+
+def _contiguous(g):
+    return None if g is None else g.contiguous()
+
+
+def _parse_params(over, params, n=None):
+    """The five parameter arguments (in _COMPACT_PARAMS' order, None: the solver's value) -> (over, given, rows): the
+    given ones as tensors, shapes checked.  rows: with n, whether the call is a per-instance one -- only a tensor one
+    dimension longer than the shared shape makes it one (`weights` [4] at n == 4 is shared); a parameter may then be
+    [..., n], a CUDA fp64 tensor.  Otherwise the values go into a copy of `over`, as tpc_mpc_params takes them."""
+    over, given = dict(over), []
+    rows = n is not None and any(torch.is_tensor(t) and t.dim() == len(shape) + 1
+                                 for (_, shape, _), t in zip(_COMPACT_PARAMS, params))
+    for (name, shape, _), t in zip(_COMPACT_PARAMS, params):
+        if t is not None:
+            t = t if torch.is_tensor(t) else torch.as_tensor(t, dtype=torch.float64)
+            if rows and tuple(t.shape) == shape + (n,):
+                _require_cuda_f64(f"per-instance {name} must be a CUDA fp64 tensor", t)
+            elif tuple(t.shape) != shape:
+                either = f" or {list(shape + (n,))}" if rows else ""
+                raise ValueError(f"{name} must have shape {list(shape)}{either}")
+            elif not rows:
+                val = t.detach().to(device="cpu", dtype=torch.float64).tolist()
+                if name == "weights":
+                    over.update(zip(_WEIGHT_KEYS, val))
+                else:
+                    over[name] = tuple(val) if shape else val
+        given.append(t)
+    return over, given, rows
+
+
+def _param_defaults(p):
+    """the solver's own values of the five (p: capi.Params), in _COMPACT_PARAMS' order"""
+    return [[getattr(p, k) for k in _WEIGHT_KEYS], p.step_size, p.wheelbase, list(p.lower), list(p.upper)]
+
+
+def _onto(d, t):
+    """a gradient as the given parameter tensor t wants it"""
+    return d.to(device=t.device, dtype=t.dtype).reshape(t.shape)
+
+
+def _scatter_params(g, given, need, per_instance=(False,) * 5):
+    """The five parameter gradients out of g["params"] [10] (a per-instance parameter: its own rows of
+    g["params_rows"] [10, n]), each onto its given tensor; None where none is needed."""
+    return [_onto(g["params_rows" if per else "params"][where], t) if on else None
+            for (_, _, where), t, on, per in zip(_COMPACT_PARAMS, given, need, per_instance)]
+
+
+def compact_general_form(v, delta_y, delta_phi, weights, step_size, wheelbase, lower, upper, horizon, x0=None):
+    """The reference controller's model (src/trajectory_point_follower.cpp:326-371) for the speeds v [n] in
+    solve_batch_general's form, built with torch ops so that gradients flow: a dict A = [1, Tv; 0, 1],
+    B = [0, Tv; Tv/l, -Tv/l], C = 0, Q = (weight_y, weight_phi), R = (weight_steering_front, weight_steering_rear),
+    lower, upper, x0 (zeros unless given [2, n]) and targets, (delta_y, delta_phi) at each of `horizon` steps.
+    `weights` is [4] or [4, n], `lower` / `upper` [2] or [2, n], T = step_size and l = wheelbase scalars or [n];
+    numbers and tensors alike become fp64 tensors on v's device first, never Python divisors, which torch multiplies
+    by their reciprocal: the last bit would differ."""
+    n = v.shape[-1]
+    f64 = dict(dtype=torch.float64, device=v.device)
+
+    def rows(x, k):
+        x = torch.as_tensor(x, **f64)
+        return (x[:, None] if x.dim() == 1 else x).expand(k, n)
+
+    T = torch.as_tensor(step_size, **f64)
+    l = torch.as_tensor(wheelbase, **f64)
+    Tv = T * v
+    one, zero = torch.ones(n, **f64), torch.zeros(n, **f64)
+    w = rows(weights, 4)
+    return {"A": torch.stack([one, Tv, zero, one]), "B": torch.stack([zero, Tv, Tv / l, -Tv / l]),
+            "C": torch.zeros(2, n, **f64), "Q": w[0:2], "R": w[2:4], "lower": rows(lower, 2), "upper": rows(upper, 2),
+            "x0": torch.zeros(2, n, **f64) if x0 is None else x0,
+            "targets": torch.stack([delta_y, delta_phi]).repeat(horizon, 1)}
 
 
 class _MpcGeneral(torch.autograd.Function):
@@ -39,7 +145,7 @@ class _MpcGeneral(torch.autograd.Function):
         controls = torch.zeros((H * I, A.shape[-1]), dtype=torch.float64, device=A.device)
         solver.solve_batch_general(*ins, controls=controls, inputs=I, **over)   # zeros shifted are zeros: a cold start
         if polish:   # onto the verified optimum where it is reached; the others keep the solver's sequence
-            tol, rounds = (1e-9, 8) if polish is True else polish
+            tol, rounds = _polish(polish)
             keys = {k: v for k, v in over.items() if k == "horizon"}
             solver.polish_batch_general(*ins, controls, tol=tol, max_rounds=rounds, want_status=False, inputs=I, **keys)
         ctx.solver, ctx.over, ctx.I = solver, over, I
@@ -50,8 +156,7 @@ class _MpcGeneral(torch.autograd.Function):
     @staticmethod
     def jvp(ctx, _solver, _over, _polish, *tangents):
         *ins, controls = ctx.saved_tensors
-        names = ("A", "B", "C", "Q", "R", "lower", "upper", "x0", "targets")
-        tan = {k: t.contiguous() for k, t in zip(names, tangents) if t is not None}
+        tan = {k: t.contiguous() for k, t in zip(MODEL_NAMES, tangents) if t is not None}
         if not tan:
             return torch.zeros_like(controls)
         return ctx.solver.solve_batch_general_forward(*ins, controls, tan, inputs=ctx.I, want_flags=False,
@@ -61,13 +166,12 @@ class _MpcGeneral(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_controls):
         *ins, controls = ctx.saved_tensors
-        names = ("A", "B", "C", "Q", "R", "lower", "upper", "x0", "targets")
-        want = tuple(k for k, need in zip(names, ctx.needs_input_grad[3:]) if need)
+        want = tuple(k for k, need in zip(MODEL_NAMES, ctx.needs_input_grad[3:]) if need)
         if not want:
             return (None,) * 12
         g = ctx.solver.solve_batch_general_backward(*ins, controls, grad_controls.contiguous(), inputs=ctx.I,
                                                     want=want, want_flags=False, **ctx.over)
-        return (None, None, None) + tuple(g.get(k) for k in names)
+        return (None, None, None) + tuple(g.get(k) for k in MODEL_NAMES)
 
 
 def mpc_general(solver, A, B, Cc, Q, R, lower, upper, x0, targets, polish=False, **over):
@@ -77,68 +181,14 @@ def mpc_general(solver, A, B, Cc, Q, R, lower, upper, x0, targets, polish=False,
     (horizon, eps, max_iter, algo, ...).  polish=True (or a (tol, max_rounds) pair; True is (1e-9, 8)) runs
     MpcSolver.polish_batch_general on the solved sequence before it is returned and saved, so a solve at dlib's eps
     0.01 is differentiated at the optimum; an instance the polish cannot verify keeps the solver's sequence."""
-    for t in (A, B, Cc, Q, R, lower, upper, x0, targets):
-        if not (t.is_cuda and t.dtype == torch.float64):
-            raise ValueError("mpc_general takes CUDA fp64 tensors")
+    _require_cuda_f64("mpc_general takes CUDA fp64 tensors", A, B, Cc, Q, R, lower, upper, x0, targets)
     return _MpcGeneral.apply(solver, over, polish, A, B, Cc, Q, R, lower, upper, x0, targets)
 
 
 class _MpcRollout(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, solver, steps, over, polish, A, B, Cc, Q, R, lower, upper, x0, targets, new_last_targets):
-        I = R.shape[0]
-        ins = [t.detach().contiguous() for t in (A, B, Cc, Q, R, lower, upper, x0, targets)]
-        nlt = None if new_last_targets is None else new_last_targets.detach().contiguous()
-        if polish:   # every step onto the verified optimum before the plant moves; the backward is the same
-            tol, rounds, newton_first = polish
-            forward = solver.rollout_newton if newton_first else solver.rollout_polished
-            controls, states, sequences, *_ = forward(steps, *ins, nlt, inputs=I, tol=tol, max_rounds=rounds,
-                                                      want_status=False, **over)
-        else:
-            controls, states, sequences, _ = solver.rollout_record(steps, *ins, nlt, inputs=I, **over)
-        ctx.solver, ctx.steps, ctx.over, ctx.I = solver, steps, over, I
-        ctx.has_nlt = nlt is not None
-        ctx.save_for_backward(*ins, *(() if nlt is None else (nlt,)), states, sequences)
-        ctx.save_for_forward(*ins, *(() if nlt is None else (nlt,)), states, sequences, controls)
-        return controls, states
-
-    @staticmethod
-    def jvp(ctx, _solver, _steps, _over, _polish, *tangents):
-        saved = list(ctx.saved_tensors)
-        ins, rest = saved[:9], saved[9:]
-        nlt = rest.pop(0) if ctx.has_nlt else None
-        states, sequences, controls = rest
-        names = ("A", "B", "C", "Q", "R", "lower", "upper", "x0", "targets", "new_last_targets")
-        tan = {k: t.contiguous() for k, t in zip(names, tangents) if t is not None}
-        if not tan:
-            return torch.zeros_like(controls), torch.zeros_like(states)
-        tu, tx = ctx.solver.rollout_forward(ctx.steps, *ins, nlt, sequences=sequences, states=states, tangents=tan,
-                                            inputs=ctx.I, want_flags=False, **ctx.over)
-        return tu[0], tx[0]
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_controls, grad_states):
-        saved = list(ctx.saved_tensors)
-        ins, rest = saved[:9], saved[9:]
-        nlt = rest.pop(0) if ctx.has_nlt else None
-        states, sequences = rest
-        names = ("A", "B", "C", "Q", "R", "lower", "upper", "x0", "targets", "new_last_targets")
-        want = tuple(k for k, need in zip(names, ctx.needs_input_grad[4:]) if need)
-        if not want:
-            return (None,) * 14
-        g = ctx.solver.rollout_backward(ctx.steps, *ins, nlt, sequences=sequences, states=states,
-                                        grad_controls=None if grad_controls is None else grad_controls.contiguous(),
-                                        grad_states=None if grad_states is None else grad_states.contiguous(),
-                                        inputs=ctx.I, want=want, want_flags=False, **ctx.over)
-        return (None, None, None, None) + tuple(g.get(k) for k in names)
-
-
-class _MpcRolloutPlant(torch.autograd.Function):
-    """_MpcRollout against a separate plant (tpc_mpc_rollout_plant and its backward / forward): four more inputs, Ap,
-    Bp, Cp (all or none) and the disturbance, each of which may be None."""
-    NAMES = ("A", "B", "C", "Q", "R", "lower", "upper", "x0", "targets", "new_last_targets", "Ap", "Bp", "Cp",
-             "disturbance")
+    """mpc_rollout: the nine arrays, then new_last_targets, Ap, Bp, Cp (all or none) and the disturbance, each of
+    which may be None.  A None input needs no gradient and has no tangent, so with no plant and no disturbance no
+    plant name reaches the solver and its methods take the entries without a plant."""
 
     @staticmethod
     def forward(ctx, solver, steps, over, polish, A, B, Cc, Q, R, lower, upper, x0, targets, new_last_targets, Ap, Bp,
@@ -147,7 +197,7 @@ class _MpcRolloutPlant(torch.autograd.Function):
         ins = [t.detach().contiguous() for t in (A, B, Cc, Q, R, lower, upper, x0, targets)]
         opt = [None if t is None else t.detach().contiguous() for t in (new_last_targets, Ap, Bp, Cp, disturbance)]
         nlt, plant, dist = opt[0], (None if Ap is None else tuple(opt[1:4])), opt[4]
-        if polish:
+        if polish:   # every step onto the verified optimum before the plant moves; the backward is the same
             tol, rounds, newton_first = polish
             forward = solver.rollout_newton if newton_first else solver.rollout_polished
             controls, states, sequences, *_ = forward(steps, *ins, nlt, inputs=I, tol=tol, max_rounds=rounds,
@@ -156,24 +206,20 @@ class _MpcRolloutPlant(torch.autograd.Function):
             controls, states, sequences, _ = solver.rollout_record(steps, *ins, nlt, inputs=I, plant=plant,
                                                                    disturbance=dist, **over)
         ctx.solver, ctx.steps, ctx.over, ctx.I = solver, steps, over, I
-        ctx.given = [t is not None for t in opt]
-        kept = [t for t in opt if t is not None]
-        ctx.save_for_backward(*ins, *kept, states, sequences)
-        ctx.save_for_forward(*ins, *kept, states, sequences, controls)
+        ctx.save_for_backward(*ins, *opt, states, sequences)     # (a None is saved as None)
+        ctx.save_for_forward(*ins, *opt, states, sequences, controls)
         return controls, states
 
     @staticmethod
     def _unpack(ctx):
-        saved = list(ctx.saved_tensors)
-        ins, rest = saved[:9], saved[9:]
-        opt = [rest.pop(0) if g else None for g in ctx.given]
-        plant = None if opt[1] is None else tuple(opt[1:4])
-        return ins, opt[0], plant, opt[4], rest
+        saved = ctx.saved_tensors
+        nlt, Ap, Bp, Cp, dist = saved[9:14]
+        return saved[:9], nlt, (None if Ap is None else (Ap, Bp, Cp)), dist, saved[14:]
 
     @staticmethod
     def jvp(ctx, _solver, _steps, _over, _polish, *tangents):
-        ins, nlt, plant, dist, (states, sequences, controls) = _MpcRolloutPlant._unpack(ctx)
-        tan = {k: t.contiguous() for k, t in zip(_MpcRolloutPlant.NAMES, tangents) if t is not None}
+        ins, nlt, plant, dist, (states, sequences, controls) = _MpcRollout._unpack(ctx)
+        tan = {k: t.contiguous() for k, t in zip(_ROLLOUT_NAMES, tangents) if t is not None}
         if not tan:
             return torch.zeros_like(controls), torch.zeros_like(states)
         tu, tx = ctx.solver.rollout_forward(ctx.steps, *ins, nlt, sequences=sequences, states=states, tangents=tan,
@@ -183,17 +229,15 @@ class _MpcRolloutPlant(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_controls, grad_states):
-        ins, nlt, plant, dist, (states, sequences) = _MpcRolloutPlant._unpack(ctx)
-        names = _MpcRolloutPlant.NAMES
-        want = tuple(k for k, need in zip(names, ctx.needs_input_grad[4:]) if need)
+        ins, nlt, plant, dist, (states, sequences) = _MpcRollout._unpack(ctx)
+        want = tuple(k for k, need in zip(_ROLLOUT_NAMES, ctx.needs_input_grad[4:]) if need)
         if not want:
             return (None,) * 18
         g = ctx.solver.rollout_backward(ctx.steps, *ins, nlt, sequences=sequences, states=states,
-                                        grad_controls=None if grad_controls is None else grad_controls.contiguous(),
-                                        grad_states=None if grad_states is None else grad_states.contiguous(),
+                                        grad_controls=_contiguous(grad_controls), grad_states=_contiguous(grad_states),
                                         inputs=ctx.I, want=want, want_flags=False, plant=plant, disturbance=dist,
                                         **ctx.over)
-        return (None, None, None, None) + tuple(g.get(k) for k in names)
+        return (None, None, None, None) + tuple(g.get(k) for k in _ROLLOUT_NAMES)
 
 
 def mpc_rollout(solver, steps, A, B, Cc, Q, R, lower, upper, x0, targets, new_last_targets=None, polish=False,
@@ -216,23 +260,18 @@ def mpc_rollout(solver, steps, A, B, Cc, Q, R, lower, upper, x0, targets, new_la
     plant=(Ap, Bp, Cp) [4, n] [2I, n] [2, n] and / or disturbance [steps*2, n]: the state moves with
     x <- Ap x + Bp u + Cp + d_k while every step's controller keeps A, B, C (tpc_mpc_rollout_plant); gradients and
     forward_ad tangents then reach Ap, Bp, Cp and the disturbance too, and those of A, B, C are what the controller's
-    belief alone contributes.  Both None is the function above, untouched."""
+    belief alone contributes.  Both None is the loop on the controller's own model, through the entries without a
+    plant."""
     if newton_first and not polish:
         raise ValueError("newton_first needs polish")
     if polish:
-        polish = ((1e-9, 8) if polish is True else tuple(polish)) + (bool(newton_first),)
-    for t in (A, B, Cc, Q, R, lower, upper, x0, targets) + (() if new_last_targets is None else (new_last_targets,)):
-        if not (t.is_cuda and t.dtype == torch.float64):
-            raise ValueError("mpc_rollout takes CUDA fp64 tensors")
-    if plant is not None or disturbance is not None:
-        Ap, Bp, Cp = plant if plant is not None else (None, None, None)
-        for t in (Ap, Bp, Cp, disturbance):
-            if t is not None and not (t.is_cuda and t.dtype == torch.float64):
-                raise ValueError("mpc_rollout takes CUDA fp64 tensors")
-        return _MpcRolloutPlant.apply(solver, int(steps), over, polish, A, B, Cc, Q, R, lower, upper, x0, targets,
-                                      new_last_targets, Ap, Bp, Cp, disturbance)
+        polish = _polish(polish) + (bool(newton_first),)
+    _require_cuda_f64("mpc_rollout takes CUDA fp64 tensors", A, B, Cc, Q, R, lower, upper, x0, targets,
+                      new_last_targets)
+    Ap, Bp, Cp = plant if plant is not None else (None, None, None)
+    _require_cuda_f64("mpc_rollout takes CUDA fp64 tensors", Ap, Bp, Cp, disturbance)
     return _MpcRollout.apply(solver, int(steps), over, polish, A, B, Cc, Q, R, lower, upper, x0, targets,
-                             new_last_targets)
+                             new_last_targets, Ap, Bp, Cp, disturbance)
 
 
 def mpc_compact(solver, v, delta_y, delta_phi, weights, step_size=0.1, wheelbase=0.21,
@@ -241,42 +280,23 @@ def mpc_compact(solver, v, delta_y, delta_phi, weights, step_size=0.1, wheelbase
 
     The model is built with torch ops from the reference controller's (src/trajectory_point_follower.cpp:326-371):
     A = [1, Tv; 0, 1], B = [0, Tv; Tv/l, -Tv/l], C = 0, x0 = 0, Q = (weight_y, weight_phi), R = (weight_steering_front,
-    weight_steering_rear), one target (delta_y, delta_phi) for every step -- and solved by mpc_general, so gradients
-    reach v, delta_y, delta_phi, the four weights (a tensor [4] or [4, n]), T, l and the bounds by the chain rule.
+    weight_steering_rear), one target (delta_y, delta_phi) for every step (compact_general_form) -- and solved by
+    mpc_general, so gradients reach v, delta_y, delta_phi, the four weights (a tensor [4] or [4, n]), T, l and the
+    bounds by the chain rule.
     The forward runs the general-form kernels, not solve_batch_compact's family: the controls agree with
     solve_batch_compact to the solvers' tolerance, not bit for bit.  polish: as in mpc_general."""
-    dev, n = v.device, v.shape[-1]
-    f64 = dict(dtype=torch.float64, device=dev)
-    H = solver._params(**over).horizon
-
-    def rows(x, k):
-        x = torch.as_tensor(x, **f64)
-        return (x[:, None] if x.dim() == 1 else x).expand(k, n)
-
-    T = torch.as_tensor(step_size, **f64)
-    l = torch.as_tensor(wheelbase, **f64)
-    Tv = T * v
-    one, zero = torch.ones(n, **f64), torch.zeros(n, **f64)
-    A = torch.stack([one, Tv, zero, one])
-    B = torch.stack([zero, Tv, Tv / l, -Tv / l])
-    w = rows(weights, 4)
-    targets = torch.stack([delta_y, delta_phi]).repeat(H, 1)
-    u = mpc_general(solver, A, B, torch.zeros(2, n, **f64), w[0:2], w[2:4], rows(lower, 2), rows(upper, 2),
-                    torch.zeros(2, n, **f64), targets, polish=polish, **over)
+    form = compact_general_form(v, delta_y, delta_phi, weights, step_size, wheelbase, lower, upper,
+                                solver._params(**over).horizon)
+    u = mpc_general(solver, *form.values(), polish=polish, **over)
     return u[0], u[1]
 
 
 class _MpcRolloutCompact(torch.autograd.Function):
     """mpc_rollout_compact: forward tpc_mpc_rollout_compact_exact; backward tpc_mpc_rollout_backward on the expansion
     ("expanded") or one call of tpc_mpc_rollout_compact_exact_backward ("fused")"""
-    PARAMS = ("weights", "step_size", "wheelbase", "lower", "upper")
-    SLICES = {"weights": slice(0, 4), "step_size": 4, "wheelbase": 5, "lower": slice(6, 8), "upper": slice(8, 10)}
-    BY_VALUE = ("weight_y", "weight_phi", "weight_steering_front", "weight_steering_rear", "step_size", "wheelbase",
-                "lower", "upper")
 
     @staticmethod
-    def forward(ctx, solver, steps, over, polish, v, delta_y, delta_phi, x0, weights, step_size, wheelbase, lower,
-                upper):
+    def forward(ctx, solver, steps, over, polish, v, delta_y, delta_phi, x0, *params):
         tol, rounds, fused = polish
         ins = [t.detach().contiguous() for t in (v, delta_y, delta_phi)]
         start = None if x0 is None else x0.detach().contiguous()
@@ -284,71 +304,47 @@ class _MpcRolloutCompact(torch.autograd.Function):
         controls, states, sequences, _, _ = solver.rollout_compact_exact(steps, *ins, start, tol=tol, max_rounds=rounds,
                                                                          want_status=False, **over)
         ctx.solver, ctx.steps, ctx.over = solver, steps, over
-        ctx.params = [None if t is None else t.detach() for t in (weights, step_size, wheelbase, lower, upper)]
-        ctx.has_x0 = start is not None
-        ctx.save_for_backward(*ins, states, sequences, *(() if start is None else (start,)))
+        ctx.given = [None if t is None else t.detach() for t in params]
+        ctx.save_for_backward(*ins, states, sequences, start)     # (a None is saved as None)
         return controls, states
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_controls, grad_states):
-        v, delta_y, delta_phi, states, sequences, *rest = ctx.saved_tensors
-        need = ctx.needs_input_grad[4:]      # v, delta_y, delta_phi, x0, then PARAMS
+        v, delta_y, delta_phi, states, sequences, x0 = ctx.saved_tensors
+        need = ctx.needs_input_grad[4:]      # v, delta_y, delta_phi, x0, then the five parameters
         if not any(need):
             return (None,) * 13
         solver, over = ctx.solver, ctx.over
+        grads = dict(sequences=sequences, states=states, grad_controls=_contiguous(grad_controls),
+                     grad_states=_contiguous(grad_states), want_flags=False)
         if ctx.fused:
             # one call: only the outputs someone needs; no status, so both routes differentiate the same instances
-            want = tuple(k for k, on in zip(("v", "delta_y", "delta_phi", "x0"), need[:4]) if on)
+            want = tuple(k for k, on in zip(_COMPACT_NAMES + ("x0",), need[:4]) if on)
             if any(need[4:]):
                 want += ("params",)
-            g = solver.rollout_compact_exact_backward(
-                ctx.steps, v, delta_y, delta_phi, rest[0] if ctx.has_x0 else None, sequences=sequences, states=states,
-                grad_controls=None if grad_controls is None else grad_controls.contiguous(),
-                grad_states=None if grad_states is None else grad_states.contiguous(), want=want, want_flags=False,
-                **over)
-            out = [g.get("v"), g.get("delta_y"), g.get("delta_phi"), g.get("x0")]
-            for name, t, on in zip(_MpcRolloutCompact.PARAMS, ctx.params, need[4:]):   # onto the given parameter tensors
-                if not on:
-                    out.append(None)
-                    continue
-                d = g["params"][_MpcRolloutCompact.SLICES[name]]
-                out.append(d.to(device=t.device, dtype=t.dtype).reshape(t.shape))
-            return (None, None, None, None) + tuple(out)
+            g = solver.rollout_compact_exact_backward(ctx.steps, v, delta_y, delta_phi, x0, want=want, **grads, **over)
+            return (None, None, None, None, g.get("v"), g.get("delta_y"), g.get("delta_phi"), g.get("x0"),
+                    *_scatter_params(g, ctx.given, need[4:]))
         p = solver._params(**over)
-        H, n = p.horizon, v.numel()
         f64 = dict(dtype=torch.float64, device=v.device)
-        defaults = ([p.weight_y, p.weight_phi, p.weight_steering_front, p.weight_steering_rear], p.step_size,
-                    p.wheelbase, list(p.lower), list(p.upper))
         with torch.enable_grad():
             # the leaves: the call's own inputs, and the parameters' values as the forward passed them
             leaves = [t.detach().requires_grad_(on) for t, on in zip((v, delta_y, delta_phi), need[:3])]
-            leaves.append(rest[0].detach().requires_grad_(need[3]) if ctx.has_x0 else None)
-            for t, d, on in zip(ctx.params, defaults, need[4:]):
+            leaves.append(None if x0 is None else x0.detach().requires_grad_(need[3]))
+            for t, d, on in zip(ctx.given, _param_defaults(p), need[4:]):
                 leaves.append(torch.as_tensor(d if t is None else t, **f64).detach().requires_grad_(on))
-            lv, ly, lp, lx, w, T, l, lo, hi = leaves
-            # mpc_compact's expansion, operation for operation
-            Tv = T * lv
-            one, zero = torch.ones(n, **f64), torch.zeros(n, **f64)
-            rows = lambda x: x[:, None].expand(x.shape[0], n)
-            arr = {"A": torch.stack([one, Tv, zero, one]), "B": torch.stack([zero, Tv, Tv / l, -Tv / l]),
-                   "C": torch.zeros(2, n, **f64), "Q": rows(w[0:2]), "R": rows(w[2:4]), "lower": rows(lo),
-                   "upper": rows(hi), "x0": torch.zeros(2, n, **f64) if lx is None else lx,
-                   "targets": torch.stack([ly, lp]).repeat(H, 1)}
+            lv, ly, lp, lx, *params = leaves
+            arr = compact_general_form(lv, ly, lp, *params, horizon=p.horizon, x0=lx)
             want = tuple(k for k, t in arr.items() if t.requires_grad)
             # (the general-form entry reads none of the compact model's ten values, two of which share its arguments' names)
-            over = {k: x for k, x in over.items() if k not in _MpcRolloutCompact.BY_VALUE}
-            g = solver.rollout_backward(ctx.steps, *[t.detach().contiguous() for t in arr.values()], None,
-                                        sequences=sequences, states=states,
-                                        grad_controls=None if grad_controls is None else grad_controls.contiguous(),
-                                        grad_states=None if grad_states is None else grad_states.contiguous(),
-                                        inputs=2, want=want, want_flags=False, **over)
+            over = {k: x for k, x in over.items() if k not in _BY_VALUE}
+            g = solver.rollout_backward(ctx.steps, *[t.detach().contiguous() for t in arr.values()], None, inputs=2,
+                                        want=want, **grads, **over)
             on = [t for t in leaves if t is not None and t.requires_grad]
             got = iter(torch.autograd.grad([arr[k] for k in want], on, [g[k] for k in want], allow_unused=True))
         out = [next(got) if t is not None and t.requires_grad else None for t in leaves]
-        for i, t in enumerate(ctx.params):     # onto the given parameter tensors
-            if out[4 + i] is not None:
-                out[4 + i] = out[4 + i].to(device=t.device, dtype=t.dtype).reshape(t.shape)
+        out[4:] = [d if d is None else _onto(d, t) for d, t in zip(out[4:], ctx.given)]
         return (None, None, None, None) + tuple(out)
 
 
@@ -367,10 +363,10 @@ def mpc_rollout_compact(solver, steps, v, delta_y, delta_phi, weights=None, step
     solver's own value (with `over`'s overrides); their values go into tpc_mpc_params by value, as in
     mpc_compact_exact.
     backward="expanded" (the default): tpc_mpc_rollout_backward on the expanded arrays at the recorded sequences and
-    states: mpc_compact's torch expansion (A = [1, Tv; 0, 1], B = [0, Tv; Tv/l, -Tv/l], ...) is built in the backward
-    only, and its chain rule carries the gradient to v, delta_y, delta_phi, x0 and every given parameter that requires
-    grad; only the expanded arrays that depend on such an input are differentiated.  Its gradients equal mpc_rollout's
-    torch graph on the expansion bit for bit.
+    states: mpc_compact's torch expansion (compact_general_form: A = [1, Tv; 0, 1], B = [0, Tv; Tv/l, -Tv/l], ...) is
+    built in the backward only, and its chain rule carries the gradient to v, delta_y, delta_phi, x0 and every given
+    parameter that requires grad; only the expanded arrays that depend on such an input are differentiated.  Its
+    gradients equal mpc_rollout's torch graph on the expansion bit for bit.
     backward="fused": one call of tpc_mpc_rollout_compact_exact_backward (MpcSolver.rollout_compact_exact_backward) on
     torch's current stream, which does not materialise the general form either: the reverse sweep over the steps on the
     model built from v, the chain rule folded in the kernel, the shared parameters' gradient summed over the batch on
@@ -379,28 +375,12 @@ def mpc_rollout_compact(solver, steps, v, delta_y, delta_phi, weights=None, step
     taken in another order).  Once-differentiable; no forward mode."""
     if backward not in ("expanded", "fused"):
         raise ValueError(f'backward must be "expanded" or "fused", got {backward!r}')
-    for t in (v, delta_y, delta_phi) + (() if x0 is None else (x0,)):
-        if not (t.is_cuda and t.dtype == torch.float64):
-            raise ValueError("mpc_rollout_compact takes CUDA fp64 tensors v, delta_y, delta_phi and x0")
+    _require_cuda_f64("mpc_rollout_compact takes CUDA fp64 tensors v, delta_y, delta_phi and x0", v, delta_y, delta_phi,
+                      x0)
     n = v.numel()
     if x0 is not None and tuple(x0.shape) != (2, n):
         raise ValueError(f"x0 must have shape [2, {n}]")
-    over = dict(over)
-    given = []
-    for name, t, shape in (("weights", weights, (4,)), ("step_size", step_size, ()), ("wheelbase", wheelbase, ()),
-                           ("lower", lower, (2,)), ("upper", upper, (2,))):
-        if t is None:
-            given.append(None)
-            continue
-        t = t if torch.is_tensor(t) else torch.as_tensor(t, dtype=torch.float64)
-        if tuple(t.shape) != shape:
-            raise ValueError(f"{name} must have shape {list(shape)}")
-        val = t.detach().to(device="cpu", dtype=torch.float64).tolist()
-        if name == "weights":
-            over.update(weight_y=val[0], weight_phi=val[1], weight_steering_front=val[2], weight_steering_rear=val[3])
-        else:
-            over[name] = tuple(val) if shape else val
-        given.append(t)
+    over, given, _ = _parse_params(over, (weights, step_size, wheelbase, lower, upper))
     tol, rounds = polish
     return _MpcRolloutCompact.apply(solver, int(steps), over, (float(tol), int(rounds), backward == "fused"), v,
                                     delta_y, delta_phi, x0, *given)
@@ -436,20 +416,19 @@ def _warm_forward(solver, warm, ins, over, **kw):
     return out
 
 
-class _MpcCompactExact(torch.autograd.Function):
-    PARAMS =("weights", "step_size", "wheelbase", "lower", "upper")
-    SLICES = {"weights": slice(0, 4), "step_size": 4, "wheelbase": 5, "lower": slice(6, 8), "upper": slice(8, 10)}
+def _compact_tangents(tangents):
+    return {k: t.contiguous() for k, t in zip(_COMPACT_NAMES, tangents) if t is not None}
 
+
+class _MpcCompactExact(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, solver, over, polish, v, delta_y, delta_phi, weights, step_size, wheelbase, lower, upper):
+    def forward(ctx, solver, over, polish, v, delta_y, delta_phi, *params):
         tol, rounds, fallback, warm = polish
         ins = [t.detach().contiguous() for t in (v, delta_y, delta_phi)]
         front, rear, sequence, status, _ = _warm_forward(solver, warm, ins, over, tol=tol, max_rounds=rounds,
                                                          fallback=fallback)
         ctx.solver, ctx.over = solver, over
-        # where each given parameter's gradient goes
-        ctx.like = [None if t is None else (t.device, t.dtype, t.shape)
-                    for t in (weights, step_size, wheelbase, lower, upper)]
+        ctx.given = [None if t is None else t.detach() for t in params]   # where each parameter's gradient goes
         ctx.save_for_backward(*ins, sequence, status)
         ctx.save_for_forward(*ins, sequence, status)
         return front, rear
@@ -457,13 +436,13 @@ class _MpcCompactExact(torch.autograd.Function):
     @staticmethod
     def jvp(ctx, _solver, _over, _polish, tv, tdy, tdphi, *tparams):
         v, delta_y, delta_phi, sequence, status = ctx.saved_tensors
-        tan = {k: t.contiguous() for k, t in zip(("v", "delta_y", "delta_phi"), (tv, tdy, tdphi)) if t is not None}
+        tan = _compact_tangents((tv, tdy, tdphi))
         if any(t is not None for t in tparams):
             # the given parameters' tangents, sliced into one row of the ten and moved to v's device
             row = torch.zeros(1, 10, dtype=torch.float64)
-            for name, t in zip(_MpcCompactExact.PARAMS, tparams):
+            for (_, _, where), t in zip(_COMPACT_PARAMS, tparams):
                 if t is not None:
-                    row[0, _MpcCompactExact.SLICES[name]] = t.detach().to(device="cpu", dtype=torch.float64)
+                    row[0, where] = t.detach().to(device="cpu", dtype=torch.float64)
             tan["params"] = row.to(v.device)
         if not tan:
             return torch.zeros_like(v), torch.zeros_like(v)
@@ -476,7 +455,7 @@ class _MpcCompactExact(torch.autograd.Function):
     def backward(ctx, grad_front, grad_rear):
         v, delta_y, delta_phi, sequence, status = ctx.saved_tensors
         need = ctx.needs_input_grad[3:]
-        want = tuple(k for k, on in zip(("v", "delta_y", "delta_phi"), need[:3]) if on)
+        want = tuple(k for k, on in zip(_COMPACT_NAMES, need[:3]) if on)
         if any(need[3:]):
             want += ("params",)
         if not want:
@@ -484,33 +463,25 @@ class _MpcCompactExact(torch.autograd.Function):
         g = ctx.solver.solve_batch_compact_exact_backward(
             v, delta_y, delta_phi, sequence, grad_front=grad_front.contiguous(), grad_rear=grad_rear.contiguous(),
             status=status, want=want, want_flags=False, **ctx.over)
-        out = [g.get("v"), g.get("delta_y"), g.get("delta_phi")]
-        for name, like, on in zip(_MpcCompactExact.PARAMS, ctx.like, need[3:]):
-            if not on:
-                out.append(None)
-                continue
-            d = g["params"][_MpcCompactExact.SLICES[name]]
-            out.append(d.to(device=like[0], dtype=like[1]).reshape(like[2]))
-        return (None, None, None) + tuple(out)
+        return (None, None, None, g.get("v"), g.get("delta_y"), g.get("delta_phi"),
+                *_scatter_params(g, ctx.given, need[3:]))
 
 
 class _MpcCompactExactRows(torch.autograd.Function):
     """mpc_compact_exact with at least one per-instance parameter: the rows entries on a [10, n] device tensor"""
 
     @staticmethod
-    def forward(ctx, solver, over, polish, defaults, v, delta_y, delta_phi, weights, step_size, wheelbase, lower,
-                upper):
+    def forward(ctx, solver, over, polish, defaults, v, delta_y, delta_phi, *params):
         tol, rounds, fallback, warm = polish
         ins = [t.detach().contiguous() for t in (v, delta_y, delta_phi)]
         n = ins[0].numel()
         # the ten rows, filled on the device by broadcasting: a given tensor as it is, the solver's value otherwise
         rows = torch.empty(10, n, dtype=torch.float64, device=ins[0].device)
         ctx.per_instance = []
-        for name, t in zip(_MpcCompactExact.PARAMS, (weights, step_size, wheelbase, lower, upper)):
-            sl = _MpcCompactExact.SLICES[name]
-            dst = rows[sl]
+        for (_, _, where), t, default in zip(_COMPACT_PARAMS, params, defaults):
+            dst = rows[where]
             if t is None:
-                src = torch.tensor(defaults[name], dtype=torch.float64).to(rows.device, non_blocking=True)
+                src = torch.tensor(default, dtype=torch.float64).to(rows.device, non_blocking=True)
             else:
                 src = t.detach().to(device=rows.device, dtype=torch.float64)
             per = t is not None and t.dim() == dst.dim()
@@ -519,8 +490,7 @@ class _MpcCompactExactRows(torch.autograd.Function):
         front, rear, sequence, status, _ = _warm_forward(solver, warm, ins, over, tol=tol, max_rounds=rounds,
                                                          fallback=fallback, params_rows=rows)
         ctx.solver, ctx.over = solver, over
-        ctx.like = [None if t is None else (t.device, t.dtype, t.shape)
-                    for t in (weights, step_size, wheelbase, lower, upper)]
+        ctx.given = [None if t is None else t.detach() for t in params]
         ctx.save_for_backward(*ins, rows, sequence, status)
         ctx.save_for_forward(*ins, rows, sequence, status)
         return front, rear
@@ -528,14 +498,14 @@ class _MpcCompactExactRows(torch.autograd.Function):
     @staticmethod
     def jvp(ctx, _solver, _over, _polish, _defaults, tv, tdy, tdphi, *tparams):
         v, delta_y, delta_phi, rows, sequence, status = ctx.saved_tensors
-        tan = {k: t.contiguous() for k, t in zip(("v", "delta_y", "delta_phi"), (tv, tdy, tdphi)) if t is not None}
+        tan = _compact_tangents((tv, tdy, tdphi))
         if any(t is not None for t in tparams):
             # the ten rows' tangent, by the forward's broadcasting: a shared parameter's next to a per-instance one's
             trows = torch.zeros(1, 10, v.numel(), dtype=torch.float64, device=v.device)
-            for name, t, per in zip(_MpcCompactExact.PARAMS, tparams, ctx.per_instance):
+            for (_, _, where), t, per in zip(_COMPACT_PARAMS, tparams, ctx.per_instance):
                 if t is not None:
                     src = t.detach().to(device=v.device, dtype=torch.float64)
-                    trows[0, _MpcCompactExact.SLICES[name]] = src if per else src.unsqueeze(-1)
+                    trows[0, where] = src if per else src.unsqueeze(-1)
             tan["params_rows"] = trows
         if not tan:
             return torch.zeros_like(v), torch.zeros_like(v)
@@ -548,7 +518,7 @@ class _MpcCompactExactRows(torch.autograd.Function):
     def backward(ctx, grad_front, grad_rear):
         v, delta_y, delta_phi, rows, sequence, status = ctx.saved_tensors
         need = ctx.needs_input_grad[4:]
-        want = tuple(k for k, on in zip(("v", "delta_y", "delta_phi"), need[:3]) if on)
+        want = tuple(k for k, on in zip(_COMPACT_NAMES, need[:3]) if on)
         if any(on and not per for on, per in zip(need[3:], ctx.per_instance)):
             want += ("params",)
         if any(on and per for on, per in zip(need[3:], ctx.per_instance)):
@@ -558,15 +528,9 @@ class _MpcCompactExactRows(torch.autograd.Function):
         g = ctx.solver.solve_batch_compact_exact_backward(
             v, delta_y, delta_phi, sequence, grad_front=grad_front.contiguous(), grad_rear=grad_rear.contiguous(),
             status=status, want=want, want_flags=False, params_rows=rows, **ctx.over)
-        out = [g.get("v"), g.get("delta_y"), g.get("delta_phi")]
-        for name, like, on, per in zip(_MpcCompactExact.PARAMS, ctx.like, need[3:], ctx.per_instance):
-            if not on:
-                out.append(None)
-                continue
-            # a per-instance parameter: its own rows; a shared one: the batch sum, as it was broadcast to everyone
-            d = g["params_rows" if per else "params"][_MpcCompactExact.SLICES[name]]
-            out.append(d.to(device=like[0], dtype=like[1]).reshape(like[2]))
-        return (None, None, None, None) + tuple(out)
+        # a per-instance parameter: its own rows; a shared one: the batch sum, as it was broadcast to everyone
+        return (None, None, None, None, g.get("v"), g.get("delta_y"), g.get("delta_phi"),
+                *_scatter_params(g, ctx.given, need[3:], ctx.per_instance))
 
 
 def mpc_compact_exact(solver, v, delta_y, delta_phi, weights=None, step_size=None, wheelbase=None, lower=None,
@@ -604,44 +568,10 @@ def mpc_compact_exact(solver, v, delta_y, delta_phi, weights=None, step_size=Non
     optimum to rounding.  Shared and per-instance parameters alike.  None is the call above."""
     if warm is not None and not isinstance(warm, CompactWarmStart):
         raise ValueError("warm must be a CompactWarmStart")
-    for t in (v, delta_y, delta_phi):
-        if not (t.is_cuda and t.dtype == torch.float64):
-            raise ValueError("mpc_compact_exact takes CUDA fp64 tensors v, delta_y, delta_phi")
-    specs = (("weights", weights, (4,)), ("step_size", step_size, ()), ("wheelbase", wheelbase, ()),
-             ("lower", lower, (2,)), ("upper", upper, (2,)))
-    n = v.numel()
-    # `weights` [4] at n == 4 is the shared shape: only a tensor one dimension longer than the shared shape is rows
-    if any(torch.is_tensor(t) and t.dim() == len(shape) + 1 for _, t, shape in specs):
-        given = []
-        for name, t, shape in specs:
-            if t is not None:
-                t = t if torch.is_tensor(t) else torch.as_tensor(t, dtype=torch.float64)
-                if tuple(t.shape) == shape + (n,):
-                    if not (t.is_cuda and t.dtype == torch.float64):
-                        raise ValueError(f"per-instance {name} must be a CUDA fp64 tensor")
-                elif tuple(t.shape) != shape:
-                    raise ValueError(f"{name} must have shape {list(shape)} or {list(shape + (n,))}")
-            given.append(t)
-        p = solver._params(**over)
-        defaults = {"weights": [p.weight_y, p.weight_phi, p.weight_steering_front, p.weight_steering_rear],
-                    "step_size": p.step_size, "wheelbase": p.wheelbase, "lower": list(p.lower), "upper": list(p.upper)}
-        return _MpcCompactExactRows.apply(solver, dict(over), (float(tol), int(max_rounds), fallback, warm), defaults, v,
-                                          delta_y, delta_phi, *given)
-    over = dict(over)
-    given = []
-    for name, t, shape in specs:
-        if t is None:
-            given.append(None)
-            continue
-        t = t if torch.is_tensor(t) else torch.as_tensor(t, dtype=torch.float64)
-        if tuple(t.shape) != shape:
-            raise ValueError(f"{name} must have shape {list(shape)}")
-        val = t.detach().to(device="cpu", dtype=torch.float64).tolist()
-        if name == "weights":
-            over.update(weight_y=val[0], weight_phi=val[1], weight_steering_front=val[2],
-                        weight_steering_rear=val[3])
-        else:
-            over[name] = tuple(val) if shape else val
-        given.append(t)
-    return _MpcCompactExact.apply(solver, over, (float(tol), int(max_rounds), fallback, warm), v, delta_y, delta_phi,
-                                  *given)
+    _require_cuda_f64("mpc_compact_exact takes CUDA fp64 tensors v, delta_y, delta_phi", v, delta_y, delta_phi)
+    over, given, rows = _parse_params(over, (weights, step_size, wheelbase, lower, upper), v.numel())
+    polish = (float(tol), int(max_rounds), fallback, warm)
+    if rows:
+        return _MpcCompactExactRows.apply(solver, over, polish, _param_defaults(solver._params(**over)), v, delta_y,
+                                          delta_phi, *given)
+    return _MpcCompactExact.apply(solver, over, polish, v, delta_y, delta_phi, *given)

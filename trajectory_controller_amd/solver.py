@@ -27,6 +27,24 @@ def _rows(I: int, H: int, steps: int = 0) -> dict:
             "new_last_targets": 2 * steps, "kkt_residual": 1, "Ap": 4, "Bp": 2 * I, "Cp": 2, "disturbance": 2 * steps}
 
 
+def _check_names(kind, given, allowed):
+    unknown = set(given) - set(allowed)
+    if unknown:
+        raise ValueError(f"unknown {kind} names {sorted(unknown)}")
+
+
+def _directions(tangents, ndim, expected):
+    """K of a dict of tangent arrays: an array of ndim(name) dimensions leads with K, one with a dimension fewer is
+    K = 1, and all agree"""
+    K = None
+    for name, t in tangents.items():
+        k = 1 if t.ndim == ndim(name) - 1 else t.shape[0] if t.ndim == ndim(name) else None
+        if k is None or (K is not None and k != K):
+            raise ValueError(f"tangent {name!r}: expected {expected} with one K for all")
+        K = k
+    return K
+
+
 class MpcSolver:
     """One tpc_mpc_handle bound to a HIP device (device=None: host-only, TPC_MPC_DEVICE_NONE).  Not thread-safe (like the handle)."""
 
@@ -281,9 +299,7 @@ class MpcSolver:
         "params_rows" is the gradient with respect to each instance's own ten parameters and "params" their sum."""
         p = self._params(**over)
         H = p.horizon
-        unknown = set(want) - set(self.COMPACT_GRAD_NAMES)
-        if unknown:
-            raise ValueError(f"unknown gradient names {sorted(unknown)}")
+        _check_names("gradient", want, self.COMPACT_GRAD_NAMES)
         ar = Arrays(v)
         NP = len(COMPACT_PARAM_NAMES)
         out = {k: ar.new(NP, per_instance=False) if k == "params" else ar.new(NP) if k == "params_rows" else ar.new()
@@ -321,9 +337,7 @@ class MpcSolver:
         last_flags at 0 and keeps a DEVICE call asynchronous."""
         p = self._params(**over)
         H = p.horizon
-        unknown = set(tangents) - set(self.COMPACT_TANGENT_NAMES)
-        if unknown:
-            raise ValueError(f"unknown tangent names {sorted(unknown)}")
+        _check_names("tangent", tangents, self.COMPACT_TANGENT_NAMES)
         tangents = {k: t for k, t in tangents.items() if t is not None}
         if not tangents:
             raise ValueError("tangents is empty: give at least one direction array")
@@ -331,13 +345,8 @@ class MpcSolver:
             raise ValueError('"params" is the shared parameters\' tangent: with params_rows give "params_rows"')
         if "params_rows" in tangents and params_rows is None:
             raise ValueError('"params_rows" needs params_rows')
-        K = None
-        for name, t in tangents.items():
-            one = 3 if name == "params_rows" else 2   # dimensions of a K-direction array
-            k = 1 if t.ndim == one - 1 else t.shape[0] if t.ndim == one else None
-            if k is None or (K is not None and k != K):
-                raise ValueError(f"tangent {name!r}: expected a leading K (or none for K = 1) with one K for all")
-            K = k
+        K = _directions(tangents, lambda name: 3 if name == "params_rows" else 2,
+                        "a leading K (or none for K = 1)")
         ar = Arrays(v)
         NP = len(COMPACT_PARAM_NAMES)
         at = {name: ar.read(t, K * NP, None, "elems") if name == "params"
@@ -504,9 +513,7 @@ class MpcSolver:
         (want_flags=False leaves last_flags at 0 and keeps a DEVICE call asynchronous)."""
         p = self._params(**over)
         H = p.horizon
-        unknown = set(want) - set(self.GRAD_NAMES)
-        if unknown:
-            raise ValueError(f"unknown gradient names {sorted(unknown)}")
+        _check_names("gradient", want, self.GRAD_NAMES)
         ar, I = self._general(A, R, inputs)
         rows = _rows(I, H)
         out = {k: ar.new(rows[k]) for k in want}
@@ -710,9 +717,7 @@ class MpcSolver:
         last_flags at 0 and keeps a DEVICE call asynchronous."""
         p = self._params(**over)
         H, S = p.horizon, int(steps)
-        unknown = set(want) - set(self.COMPACT_LOOP_GRAD_NAMES)
-        if unknown:
-            raise ValueError(f"unknown gradient names {sorted(unknown)}")
+        _check_names("gradient", want, self.COMPACT_LOOP_GRAD_NAMES)
         ar = Arrays(v)
         NP = len(COMPACT_PARAM_NAMES)
         rows = {"params_rows": NP, "x0": 2}
@@ -755,9 +760,7 @@ class MpcSolver:
             if plant_call:
                 want += ("disturbance",)
         plant_call = plant_call or bool(set(want) & set(self.PLANT_GRAD_NAMES))
-        unknown = set(want) - set(self.ROLLOUT_GRAD_NAMES) - set(self.PLANT_GRAD_NAMES)
-        if unknown:
-            raise ValueError(f"unknown gradient names {sorted(unknown)}")
+        _check_names("gradient", want, self.ROLLOUT_GRAD_NAMES + self.PLANT_GRAD_NAMES)
         ar, I = self._general(A, R, inputs)
         rows = _rows(I, H, steps)
         out = {k: ar.new(rows[k]) for k in want}
@@ -786,18 +789,11 @@ class MpcSolver:
     def _tangents(self, ar, rows, tangents):
         """(K, capi.Tangents, capi.PlantTangents) of `tangents`: names of TANGENT_NAMES and PLANT_TANGENT_NAMES ->
         arrays [K, c, n] (2-D [c, n]: K = 1) with c = rows[name]"""
-        unknown = set(tangents) - set(self.TANGENT_NAMES) - set(self.PLANT_TANGENT_NAMES)
-        if unknown:
-            raise ValueError(f"unknown tangent names {sorted(unknown)}")
+        _check_names("tangent", tangents, self.TANGENT_NAMES + self.PLANT_TANGENT_NAMES)
         tangents = {k: v for k, v in tangents.items() if v is not None}
         if not tangents:
             raise ValueError("tangents is empty: give at least one direction array")
-        K = None
-        for name, v in tangents.items():
-            k = 1 if v.ndim == 2 else v.shape[0] if v.ndim == 3 else None
-            if k is None or (K is not None and k != K):
-                raise ValueError(f"tangent {name!r}: expected [K, c, n] (or [c, n] for K = 1) with one K for all")
-            K = k
+        K = _directions(tangents, lambda name: 3, "[K, c, n] (or [c, n] for K = 1)")
         at = {name: ar.read(v, K * rows[name], None, "loose") for name, v in tangents.items()}
         tan = capi.Tangents(directions=K, reserved=0, **{"t" + name: at.get(name) for name in self.TANGENT_NAMES})
         ptan = capi.PlantTangents(tA=at.get("Ap"), tB=at.get("Bp"), tC=at.get("Cp"), tdisturbance=at.get("disturbance"))
