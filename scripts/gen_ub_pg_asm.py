@@ -20,7 +20,10 @@ bit for bit); where values live is decided in scripts/ubasm.py (the iteration) a
   * a refill pass takes its model scalars and step constants from the instance's record, where the coordinate-descent
     kernel left them (same operations, same bits as recomputing them: mpc_ub.h), so it contains no division.
 
-    python scripts/gen_ub_pg_asm.py [NA] > trajectory_controller_amd/csrc/mpc_ub_pg_asm.h
+    python scripts/gen_ub_pg_asm.py [NA [DIAG [EXECMASK [CHUNK [CHECKS [H [BATCH [RESERVE [SCHED]]]]]]]]] > trajectory_controller_amd/csrc/mpc_ub_pg_asm.h
+
+Shipped at N = 20: `3` (RESERVE 0, SCHED 3,5,8).  `3 0 0 0 2,5 20 3 0 0` writes the stream as it was before RESERVE and SCHED
+existed, byte for byte, so either part can be set against it alone (scripts/build_asm_variant.sh).
 """
 import os
 import sys
@@ -67,7 +70,31 @@ CHUNK = int(sys.argv[4]) if len(sys.argv) > 4 else 0
 CHECKS = [int(c) for c in (sys.argv[5] if len(sys.argv) > 5 else "2,5").split(",") if int(c) > 0]
 AORD = f"a{_n}"
 if CHUNK: _n += 1
+# RESERVE: tickets drawn ahead of the pass that uses them; count operand and returned first ticket live in AGPRs (no VGPR is
+# free inside the loop).  0 (shipped): the pass draws its own.  Both modes measured, neither gains (NOTEBOOK.md, profiles/
+# r22_refill_reserve_ab.txt: 1 is 19 % slower, 2 does not separate from 0).
+#   1: at the end of every pass (and in the prologue: 64) the atomic for the NEXT pass is issued, as many tickets as that pass's
+#      threshold, and not waited for; the pass starts with s_waitcnt vmcnt(0) and hands the reserved tickets out in rank order,
+#      lanes beyond them stay waiting for the following pass.  A lane is exhausted only by its own ticket >= the queue length
+#      and draws come in order from one counter, so once a lane is exhausted every later draw lies wholly past the end: what is
+#      out at DONE holds no instance, and DONE only waits for its return.
+#   2: the stop block that finds the pass due draws (as many as lanes wait), the loop runs ONE more iteration under the round
+#      trip, the pass finds the tickets there; a pass due with no lane at work, or for lanes a reserved pass left waiting, draws
+#      for itself.  A draw is always followed by the pass that consumes all of it: nothing is out at DONE.
+# Result stores of the stop blocks share vmcnt with an outstanding atomic: only passes and DONE wait on it.
+RESERVE = int(sys.argv[8]) if len(sys.argv) > 8 else 0
+# SCHED "b0,b1,b2[,p1,p2]": the refill threshold is an SGPR, re-chosen at each pass from the first ticket the pass consumed:
+# b0 below in.thr1, b1 below in.thr2, b2 from there; thr1, thr2 = p1 %, p2 % of the queue length (60, 85), which only the
+# device knows (the coordinate-descent kernel decides what enters the queue): mpc_ub_asm.h computes them next to n_queue.
+# "0": the literal BATCH
+SCHED = [int(c) for c in (sys.argv[9] if len(sys.argv) > 9 else ("3,5,8" if H == 20 and BATCH == 3 and not CHUNK else "0")).split(",")]
+SCHED = (SCHED + [60, 85])[:5] if len(SCHED) in (3, 5) else None
+assert not (CHUNK and (RESERVE or SCHED))
+assert not SCHED or (SCHED[0] == BATCH and all(1 <= b <= 64 for b in SCHED[:3]) and 0 <= SCHED[3] <= SCHED[4] <= 100)
+ARCNT, ARFIRST = f"a{_n}", f"a{_n + 1}"
+if RESERVE: _n += 2
 N_AGPR = _n
+SBATCH = "%[sbatch]" if SCHED else str(BATCH)
 P.A = AG
 P.S = {n: f"%[{n}]" for n in ("sgq0", "sgq1", "sgrs0", "sgrs1", "slo1", "sgeps", "shave", "sleft")}
 EXECMASK = int(sys.argv[3]) if len(sys.argv) > 3 else 0   # 1: the loop runs under EXEC = the lanes that carry an instance (measured SLOWER: 5.14-5.24 ms against 4.82-4.87,
@@ -117,9 +144,24 @@ def stop_block(cont_label, exit_label):
           f"s_mov_b64 exec, {P.S['sexec']}",
           "s_or_b64 %[stmp], %[shave], %[sexh]", "s_not_b64 %[stmp], %[stmp]",     # lanes waiting for a refill
           "s_bcnt1_i32_b64 %[sb], %[stmp]",
-          "s_cmp_lg_u32 %[scapf], 0", f"s_cbranch_scc1 {exit_label}",
-          f"s_cmp_ge_u32 %[sb], {BATCH}", f"s_cbranch_scc1 {exit_label}",
-          "s_cmp_eq_u64 %[shave], 0", f"s_cbranch_scc1 {exit_label}",
+          "s_cmp_lg_u32 %[scapf], 0", f"s_cbranch_scc1 {exit_label}"]
+    if RESERVE != 2:
+        return o + [f"s_cmp_ge_u32 %[sb], {SBATCH}", f"s_cbranch_scc1 {exit_label}",
+                    "s_cmp_eq_u64 %[shave], 0", f"s_cbranch_scc1 {exit_label}",
+                    f"s_branch {cont_label}"]
+    # RESERVE 2: a pass has fallen due while lanes still have work -- draw its tickets now, run ONE more iteration under the
+    # atomic's round trip, then leave for the pass: the count-down is moved so that it ends with the next iteration (scap and
+    # sleft shifted by the same amount keep `wave iterations so far = scap - sleft - 1` true; XEVEN moves scap back)
+    o += ["s_cmp_eq_u64 %[shave], 0", f"s_cbranch_scc1 {exit_label}",
+          f"s_cmp_ge_u32 %[sb], {SBATCH}", f"s_cbranch_scc0 {cont_label}",
+          "s_cmp_lg_u32 %[sres], 0", f"s_cbranch_scc1 {exit_label}",          # (one is out already: its pass comes first)
+          "s_mov_b64 exec, 1",
+          f"v_mov_b32 {t0.lo}, %[sb]", f"v_mov_b32 {t0.hi}, 0", "s_nop 1",
+          f"v_accvgpr_write_b32 {ARCNT}, {t0.lo}",
+          "s_mov_b32 %[sres], %[sb]",
+          "s_mov_b32 %[sdelta], %[sleft]", "s_sub_u32 %[scap], %[scap], %[sleft]", "s_mov_b32 %[sleft], 0", "s_nop 1",
+          f"global_atomic_add {ARFIRST}, {t0.hi}, {ARCNT}, %[pticket] sc0",
+          f"s_mov_b64 exec, {P.S['sexec']}",
           f"s_branch {cont_label}"]
     return o
 
@@ -131,6 +173,16 @@ def stamp_begin(k):
 def stamp_end(k):
     return (["s_memtime s[98:99]", "s_waitcnt lgkmcnt(0)", "s_sub_u32 s98, s98, s96", "s_add_u32 %[sdiag], %[sdiag], s98"]
             if DIAG == k else [])
+
+
+def reserve(count, sc):
+    """issues the ticket atomic for the wavefront's next pass (lane 0; `count` tickets) and does not wait for it"""
+    return ["s_mov_b64 exec, 1",
+            f"v_mov_b32 {sc[0].lo}, {count}", f"v_mov_b32 {sc[0].hi}, 0", "s_nop 1",
+            f"v_accvgpr_write_b32 {ARCNT}, {sc[0].lo}",
+            f"s_mov_b32 %[sres], {count}", "s_nop 4",
+            f"global_atomic_add {ARFIRST}, {sc[0].hi}, {ARCNT}, %[pticket] sc0",
+            "s_mov_b64 exec, -1"]
 
 
 def gen_body():
@@ -153,19 +205,53 @@ def gen_body():
     else:
         o += [f"v_mov_b32 {VK}, 0", f"v_mov_b32 {VBASE}, 0", f"v_mov_b32 {VCAP}, -1"]
     o += [f"v_mov_b64 {C['cgl0']}, %[sgrl0]", f"v_mov_b64 {C['cgl1']}, %[sgrl1]"]
+    if SCHED: o += [f"s_mov_b32 %[sbatch], {SCHED[0]}"]
+    if RESERVE == 1: o += reserve(64, sc)                  # the first pass: every lane waits
+    if RESERVE == 2: o += ["s_mov_b32 %[sres], 0", "s_mov_b32 %[sdelta], 0"]
     # ---------------- main: refill when due, else iterate
     o += ["MAIN%=:",
           "s_or_b64 %[stmp], %[shave], %[sexh]", "s_not_b64 %[swant], %[stmp]",
           "s_cmp_eq_u64 %[swant], 0", "s_cbranch_scc1 NOWANT%=",
           "s_bcnt1_i32_b64 %[scnt], %[swant]",
-          f"s_cmp_ge_u32 %[scnt], {BATCH}", "s_cbranch_scc1 REFILL%=",
+          f"s_cmp_ge_u32 %[scnt], {SBATCH}", "s_cbranch_scc1 REFILL%=",
           "s_cmp_eq_u64 %[shave], 0", "s_cbranch_scc1 REFILL%=",
           "s_branch ITER%=",
           "NOWANT%=:",
           "s_cmp_eq_u64 %[shave], 0", "s_cbranch_scc1 DONE%=",
           "s_branch ITER%="]
     # ---------------- refill pass (lane_pg_fused_kernel's protocol: one atomic for the wavefront's tickets)
-    if not CHUNK:
+    if RESERVE:
+        o += ["REFILL%=:"] + stamp_begin(4) + [
+              "s_add_u32 %[srefills], %[srefills], 1"]
+        if RESERVE == 2:   # no reservation (the first pass, a pass with no lane at work, lanes a reserved pass left waiting): draw now
+            o += ["s_cmp_lg_u32 %[sres], 0", "s_cbranch_scc1 RRES%=",
+                  "s_mov_b64 exec, 1",
+                  f"v_mov_b32 {sc[0].lo}, %[scnt]", f"v_mov_b32 {sc[0].hi}, 0", "s_nop 1",
+                  f"v_accvgpr_write_b32 {ARCNT}, {sc[0].lo}",
+                  "s_mov_b32 %[sres], %[scnt]", "s_nop 4",
+                  f"global_atomic_add {ARFIRST}, {sc[0].hi}, {ARCNT}, %[pticket] sc0",
+                  "s_mov_b64 exec, -1",
+                  "RRES%=:"]
+        o += stamp_begin(1) + [
+              "s_waitcnt vmcnt(0)"] + stamp_end(1) + [                    # the reservation (drawn a pass ago / an iteration ago)
+              f"v_accvgpr_read_b32 {sc[1].lo}, {ARFIRST}", "s_nop 1",
+              f"v_readfirstlane_b32 %[sfirst], {sc[1].lo}",               # (lane 0 drew it)
+              "s_min_u32 %[sb], %[scnt], %[sres]"] + (                     # lanes served: no more than tickets reserved
+              ["s_mov_b32 %[sres], 0"] if RESERVE == 2 else []) + [
+              "s_mov_b64 exec, %[swant]",
+              f"v_mbcnt_lo_u32_b32 {sc[0].lo}, exec_lo, 0", f"v_mbcnt_hi_u32_b32 {sc[0].lo}, exec_hi, {sc[0].lo}",   # rank among the waiting lanes
+              f"v_cmp_gt_u32_e64 vcc, %[sb], {sc[0].lo}",
+              "s_and_b64 exec, %[swant], vcc",                             # (the rest stay waiting for the following pass)
+              f"v_add_u32 {sc[0].lo}, %[sfirst], {sc[0].lo}",          # ticket
+              f"v_cmp_le_u32_e64 vcc, %[snq], {sc[0].lo}",              # past the queue's end: exhausted
+              "s_or_b64 %[sexh], %[sexh], vcc",
+              "s_andn2_b64 %[snew], exec, vcc",
+              "s_mov_b64 exec, %[snew]",
+              "s_cbranch_execz RDONE%=",
+              f"v_lshlrev_b32 {sc[0].lo}, 2, {sc[0].lo}"] + stamp_begin(2) + [
+              f"global_load_dword {vk}, {sc[0].lo}, %[porder]",
+              "s_waitcnt vmcnt(0)"] + stamp_end(2) + ([f"v_accvgpr_write_b32 {AK}, {vk}"] if PARK else [])
+    elif not CHUNK:
         o += ["REFILL%=:"] + stamp_begin(4) + [
               "s_add_u32 %[srefills], %[srefills], 1",
               "s_ff1_i32_b64 %[sa], %[swant]", "s_lshl_b64 exec, 1, %[sa]",
@@ -291,7 +377,13 @@ def gen_body():
           "s_ff1_i32_b64 %[sa], %[stmp]", "s_bitset0_b64 %[stmp], %[sa]",
           f"v_readlane_b32 %[sb], {vcap}, %[sa]", "s_min_u32 %[scap], %[scap], %[sb]",
           "s_branch RCAP%=",
-          "RDONE%=:", "s_mov_b64 exec, -1"] + stamp_end(4) + ["s_branch MAIN%="]
+          "RDONE%=:", "s_mov_b64 exec, -1"]
+    if SCHED:   # the next pass's batch, by where in the queue this one drew
+        o += [f"s_mov_b32 %[sbatch], {SCHED[0]}",
+              "s_cmp_ge_u32 %[sfirst], %[sthr1]", f"s_cselect_b32 %[sbatch], {SCHED[1]}, %[sbatch]",
+              "s_cmp_ge_u32 %[sfirst], %[sthr2]", f"s_cselect_b32 %[sbatch], {SCHED[2]}, %[sbatch]"]
+    if RESERVE == 1: o += reserve(SBATCH, sc)
+    o += stamp_end(4) + ["s_branch MAIN%="]
     # ---------------- iterate
     tailA = ["s_cbranch_vccnz SA%=", "s_cbranch_scc1 XODD%="]
     tailB = ["s_cbranch_vccnz SB%=", "s_cbranch_scc1 XEVEN%=", "s_branch LA%="]
@@ -312,7 +404,8 @@ def gen_body():
         o += [".p2align 3"] + P.backward("B", ["s_cbranch_scc1 XEVEN%=", "s_branch LA%="], notest_from=top, label="NTB")
     o += ["XODD%=:"] + [f"v_mov_b64 {V[q]}, {(Wz if q % 2 == 0 else Wy)[q // 2]}" for q in range(2 * NREG)]
     o += ["XEVEN%=:", "s_mov_b64 exec, -1"] + stamp_end(5) + [
-          "s_sub_u32 %[sit], %[scap], %[sleft]", "s_sub_u32 %[sit], %[sit], 1",       # wave iterations so far
+          "s_sub_u32 %[sit], %[scap], %[sleft]", "s_sub_u32 %[sit], %[sit], 1"] + (   # wave iterations so far
+          ["s_add_u32 %[scap], %[scap], %[sdelta]", "s_mov_b32 %[sdelta], 0"] if RESERVE == 2 else []) + [   # (the earliest cap, back where it was)
           "s_cmp_ge_u32 %[sit], %[scap]", "s_cbranch_scc0 MAIN%="]
     # ---------------- a lane may have reached max_iter (mpc.h:271): publish those, recompute the earliest cap exactly
     capreg = VCAP if not PARK else acc.hi
@@ -345,10 +438,18 @@ def gen():
                "#pragma once\n\nnamespace tpc {\n\n" % (H, n_iter, " (the compiler's loop: 708)" if H == 20 else "",
                                                       f"{NREG}..{H - 1}" if NA else "none"))
     out.append(f"constexpr int kUbAsmH{SUFFIX} = {H}, kUbAsmIterInstrs{SUFFIX} = {n_iter}, kUbAsmBatch{SUFFIX} = {BATCH};\n\n")
+    if SCHED:
+        out.append(f"// refill threshold by queue position: {SCHED[0]} / {SCHED[1]} / {SCHED[2]} lanes, changing at these percentages of the queue length\n"
+                   f"#define TPC_UB_ASM_SCHED{SUFFIX.upper()} 1\n"
+                   f"constexpr unsigned kUbAsmSchedMid{SUFFIX} = {SCHED[1]}, kUbAsmSchedLate{SUFFIX} = {SCHED[2]}, "
+                   f"kUbAsmSchedPct1{SUFFIX} = {SCHED[3]}, kUbAsmSchedPct2{SUFFIX} = {SCHED[4]};\n\n")
+    if RESERVE:
+        out.append(f"constexpr int kUbAsmReserve{SUFFIX} = {RESERVE};   // tickets drawn ahead of the pass that uses them: 1 at the end of the pass before, 2 when the pass falls due\n\n")
     if H == 20:
         out.append("struct UbAsmIn {\n"
                    "    const double* recs; const uint32_t* order; uint32_t* ticket; double* front; double* rear; int32_t* iters;\n"
                    "    uint32_t n_queue, max_iter;\n"
+                   + ("    uint32_t thr1, thr2;   // first tickets from which the refill threshold takes its middle and its late value\n" if SCHED else "") +
                    "    double gq0, gq1, grs0, grs1, grl0, grl1, lo0, lo1, hi0, hi1, s0, s1, xz0, xz1, geps;   // wave-uniform: MUST reach the asm in SGPRs (kernel arguments)\n"
                    "};\n")
     else:
@@ -358,7 +459,8 @@ def gen():
                + ("    uint32_t sdiag;\n" if DIAG else "") +
                "    uint64_t shave, sexh, swant, snew, stmp, sstop, sdonenow;\n"
                "    uint32_t scap, sleft, scnt, sfirst, sa, sb, scapf;\n"
-               + ("    uint32_t scnext, scend, scbase;\n" if CHUNK else "") +
+               + ("    uint32_t scnext, scend, scbase;\n" if CHUNK else "")
+               + ("    uint32_t sres;\n" if RESERVE else "") + ("    uint32_t sdelta;\n" if RESERVE == 2 else "") + ("    uint32_t sbatch;\n" if SCHED else "") +
                "    asm volatile(\n")
     for l in body:
         out.append(f'        "{l}\\n"\n')
@@ -368,11 +470,15 @@ def gen():
             '[sfirst] "=&s"(sfirst)', '[sa] "=&s"(sa)', '[sb] "=&s"(sb)', '[scapf] "=&s"(scapf)']
     if CHUNK:
         outs += ['[scnext] "=&s"(scnext)', '[scend] "=&s"(scend)', '[scbase] "=&s"(scbase)']
+    if RESERVE: outs += ['[sres] "=&s"(sres)']
+    if RESERVE == 2: outs += ['[sdelta] "=&s"(sdelta)']
+    if SCHED: outs += ['[sbatch] "=&s"(sbatch)']
     ins = ['[precs] "s"(in.recs)', '[porder] "s"(in.order)', '[pticket] "s"(in.ticket)', '[pfront] "s"(in.front)', '[prear] "s"(in.rear)',
            '[piters] "s"(in.iters)', '[snq] "s"(in.n_queue)', '[smaxit] "s"(in.max_iter)',
            '[sgq0] "s"(in.gq0)', '[sgq1] "s"(in.gq1)', '[sgrs0] "s"(in.grs0)', '[sgrs1] "s"(in.grs1)', '[sgrl0] "s"(in.grl0)', '[sgrl1] "s"(in.grl1)',
            '[slo0] "s"(in.lo0)', '[slo1] "s"(in.lo1)', '[shi0] "s"(in.hi0)', '[shi1] "s"(in.hi1)', '[ss0] "s"(in.s0)', '[ss1] "s"(in.s1)',
            '[sxz0] "s"(in.xz0)', '[sxz1] "s"(in.xz1)', '[sgeps] "s"(in.geps)']
+    if SCHED: ins += ['[sthr1] "s"(in.thr1)', '[sthr2] "s"(in.thr2)']
     clob = [f'"v{r}"' for r in range(NVGPR)] + [f'"a{r}"' for r in range(N_AGPR)] + ['"vcc"', '"scc"', '"memory"']
     if DIAG:
         outs.append('[sdiag] "=&s"(sdiag)')
